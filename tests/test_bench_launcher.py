@@ -52,3 +52,9 @@ def test_launcher_fails_fast_when_fewer_devices_than_ranks():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 2, (r.returncode, r.stderr[-500:])
     assert "HIP device(s) visible" in r.stderr and r.stdout.strip() == ""
+
+
+def test_full_and_dump_outputs_options_exist():
+    """A plain run times the headline only; `--full` runs the secondary figures, `--dump-outputs DIR` writes the last step's outputs."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -85,7 +85,7 @@ def test_c_abi_landmark_merge_on_rccl_world_size_1():
 def test_bench_under_torchrun_uses_rccl():
     env = dict(os.environ, ORBHIP_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29537",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batches-per-step", "2", "--no-cpu", "--no-pipelined"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batches-per-step", "2", "--no-cpu", "--no-pipelined", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -105,7 +105,7 @@ def test_bench_two_ranks_shared_gpu_merges_both_ranks_landmarks(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batches-per-step", "2", "--batch", "64",
-           "--ba-quick", "--cpu-sample", "4", "--cpu-all-seconds", "1"]
+           "--ba-quick", "--cpu-sample", "4", "--cpu-all-seconds", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,10 +1,10 @@
 #!/bin/bash
-# N runs of the default bench.py on one box: value, one-stream rate, host-fed fraction, LocalBA figures of every run (the run-to-run spread).
+# N runs of bench.py --full on one box: value, one-stream rate, host-fed fraction, LocalBA figures of every run (the run-to-run spread).
 # usage: bash tools/bench_repeats.sh [N=5] > profiles/<round>_bench_repeats.txt
 cd "$(dirname "$0")/.."
 N=${1:-5}
 for i in $(seq $N); do
-  timeout 900 python bench.py 2>/dev/null | tail -1 | python -c "
+  timeout 900 python bench.py --full 2>/dev/null | tail -1 | python -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 l = j['localba']; c = l['roofline']['cases']

@@ -9,10 +9,10 @@ export TMPDIR=/tmp
 R=${1:-r06}
 O=gpurun_out/$R; mkdir -p $O
 step() { echo "== $*"; }
-step bench;      timeout 900 python bench.py > $O/bench.json 2> $O/bench.err || tail -5 $O/bench.err
+step bench;      timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err || tail -5 $O/bench.err
 step bench trace
 rm -rf $O/benchprof
-rocprofv3 --kernel-trace --stats --output-format rocpd -d $O/benchprof -o run -- timeout 600 python bench.py --no-cpu --no-ba --no-pcie --streams 1 --no-pipelined --steps 3 --warmup 1 > $O/bench_traced.json 2> $O/benchprof.log || tail -5 $O/benchprof.log
+rocprofv3 --kernel-trace --stats --output-format rocpd -d $O/benchprof -o run -- timeout 600 python bench.py --full --no-cpu --no-ba --no-pcie --streams 1 --no-pipelined --steps 3 --warmup 1 > $O/bench_traced.json 2> $O/benchprof.log || tail -5 $O/benchprof.log
 db=$(find $O/benchprof -name "*.db" 2>/dev/null | head -1)
 if [ -n "$db" ]; then python tools/rocpd_stats.py $db $O/bench_kernel_stats.csv && python tools/kstats_print.py $O/bench_kernel_stats.csv | head -14; else echo "no trace database"; fi
 [ "$2" = quick ] && exit 0
@@ -62,9 +62,9 @@ timeout 600 python -m pytest tests/test_gpu_concurrency.py -q -s 2>&1 | grep -E 
 step mfma ubench
 [ -x tools/ubench/bin/mfma_f64 ] && timeout 120 tools/ubench/bin/mfma_f64 > $O/mfma_f64_ubench.txt 2>&1; tail -4 $O/mfma_f64_ubench.txt
 step rccl world size 1
-ORBHIP_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu --no-pipelined > $O/bench_rccl_ws1.json 2> $O/bench_rccl_ws1.err || tail -5 $O/bench_rccl_ws1.err
+ORBHIP_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu --no-pipelined --full > $O/bench_rccl_ws1.json 2> $O/bench_rccl_ws1.err || tail -5 $O/bench_rccl_ws1.err
 step 2 ranks shared gpu
-ORBHIP_BENCH_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu > $O/bench_2rank_shared.json 2> $O/bench_2rank.err || tail -5 $O/bench_2rank.err
+ORBHIP_BENCH_SHARED_GPU=1 timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu --full > $O/bench_2rank_shared.json 2> $O/bench_2rank.err || tail -5 $O/bench_2rank.err
 # (the 8-rank run sharing ONE GPU is not part of this script since round 6: eight processes x 8 - 12 hardware queues x persistent, flag-linked
 # launches oversubscribe the device - the run produced nothing twice and, run alone with a 1200-s limit, hit it and left the GPU
 # unresponsive.  The N = 8 code path is the N = 2 one: tests/test_sharding*.py on gloo, the 2-rank run above, the RCCL run at world size 1.
