@@ -93,6 +93,9 @@ struct Queries {
   explicit Queries(size_t n) : uv(2 * n, 0.f), radius(n, 0.f), angle(n, 0.f), lo(n, -1), hi(n, -1), pred(n, -1), valid(n, 0), desc(32 * n, 0) {}
   template <class MatT> void set_desc(size_t q, const MatT& d) { std::memcpy(&desc[32 * q], d.ptr(0), 32); }
 };
+// an owned copy of row r: m.row(r).clone() for cv::Mat (row() shares the keyframe's storage), m.row(r) where row() already copies
+template <class M> inline auto row_copy(const M& m, int r, int) -> decltype(m.row(r).clone()) { return m.row(r).clone(); }
+template <class M> inline M row_copy(const M& m, int r, long) { return m.row(r); }
 
 }  // namespace dropin
 
@@ -1295,6 +1298,119 @@ struct FrameOpsT {
       }
     return out;
   }
+
+  // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:256-315, what & ORBL_MP_DESC) and MapPoint::UpdateNormalAndDepth
+  // (:335-378, what & ORBL_MP_NORMAL_DEPTH) for a LIST of points in ONE library call (orbl_update_map_points): the loops of
+  // LocalMapping.cc:141-152, :386-388 (after the loop over the new points), :476-485 and the LocalBA write-back
+  // (src/CeresOptimizer.cc:590-598).  Per point the snapshot of the reference's methods - is_bad_, observations_ (std::map order),
+  // reference_keyframe_, world_pose_ under mutex_features_ (+ mutex_pose_ for the normal) - then keyframe->isBad() for the
+  // descriptor part only, GetCameraCenter(), and the octave of undistort_keypoints_[observations[reference_keyframe]] (operator[]
+  // on the local copy: index 0 when the reference keyframe is not in the list).  The results are written back under the
+  // reference's lock scopes: descriptor_ under mutex_features_ (:311-314), max / min_distance_ and normal_vector_ under mutex_pose_
+  // (:373-377).  Inside the reference tree these members are protected: MapPoint.h declares `template <class> friend struct
+  // FrameOpsT;`; the mutexes are taken when the type has them.  One call per distinct scale-factor table
+  // of the reference keyframes (every keyframe copies the one extractor's: one call).  NULL entries are skipped.
+  static void UpdateMapPoints(const std::vector<MapPoint*>& points, int what) {
+    const bool desc = (what & ORBL_MP_DESC) != 0, nd = (what & ORBL_MP_NORMAL_DEPTH) != 0;
+    if (points.empty() || !(desc || nd)) return;
+    struct Snap { bool bad = true; std::vector<std::pair<KeyFrame*, size_t> > obs; KeyFrame* ref = nullptr; double X[3] = {0, 0, 0}; int level = 0; };
+    std::vector<Snap> S(points.size());
+    std::vector<std::vector<float> > tables;                   // distinct scale-factor tables, and the points of each
+    std::vector<std::vector<size_t> > members(1);
+    for (size_t i = 0; i < points.size(); i++) {
+      MapPoint* mp = points[i];
+      Snap& s = S[i];
+      if (!mp) { members[0].push_back(i); continue; }           // (NULL entries of GetMapPointMatches(): skipped, as :479)
+      {
+        std::unique_lock<std::mutex> lock1 = lock_features(mp, 0);
+        std::unique_lock<std::mutex> lock2 = nd ? lock_pose(mp, 0) : std::unique_lock<std::mutex>();
+        s.bad = mp->is_bad_;
+        if (!s.bad) {
+          s.obs.assign(mp->observations_.begin(), mp->observations_.end());
+          if (nd) { s.ref = mp->reference_keyframe_; for (int k = 0; k < 3; k++) s.X[k] = mp->world_pose_[k]; }
+        }
+      }
+      if (!nd || s.bad || s.obs.empty()) { members[0].push_back(i); continue; }
+      if (!s.ref) throw std::runtime_error("UpdateMapPoints: a map point with observations has no reference keyframe");
+      size_t kp = 0;                                           // observations[reference_keyframe] (:369-371)
+      for (const auto& o : s.obs) if (o.first == s.ref) { kp = o.second; break; }
+      s.level = s.ref->undistort_keypoints_[kp].octave;
+      const std::vector<float> t(s.ref->scale_factors_.begin(), s.ref->scale_factors_.begin() + s.ref->n_scale_levels_);
+      size_t g = 0;
+      while (g < tables.size() && tables[g] != t) g++;
+      if (g == tables.size()) { tables.push_back(t); if (g > 0) members.push_back(std::vector<size_t>()); }
+      members[g].push_back(i);
+    }
+    if (tables.empty()) tables.push_back(std::vector<float>(1, 1.0f));
+    for (size_t g = 0; g < members.size(); g++) {
+      const std::vector<size_t>& idx = members[g];
+      if (idx.empty()) continue;
+      const int n = (int)idx.size();
+      std::vector<int32_t> off(n + 1, 0), obs_kf, ref_kf(n, -1), ref_level(n, 0);
+      std::vector<uint8_t> pt_good(n, 0), obs_desc, kf_good;
+      std::vector<double> X(3 * (size_t)n, 0.0), centers;
+      std::unordered_map<KeyFrame*, int> kf_at;
+      auto kf_index = [&](KeyFrame* kf) {
+        auto it = kf_at.find(kf);
+        if (it != kf_at.end()) return it->second;
+        const Vector3d O = kf->GetCameraCenter();
+        for (int k = 0; k < 3; k++) centers.push_back(O[k]);
+        const int at = (int)kf_at.size();
+        kf_at.emplace(kf, at);
+        return at;
+      };
+      for (int j = 0; j < n; j++) {
+        const Snap& s = S[idx[j]];
+        pt_good[j] = s.bad ? 0 : 1;
+        for (const auto& o : s.obs) {
+          if (nd) obs_kf.push_back(kf_index(o.first));
+          if (desc) {
+            kf_good.push_back(o.first->isBad() ? 0 : 1);                          // (:276)
+            const uint8_t* row = o.first->descriptors_.ptr((int)o.second);
+            obs_desc.insert(obs_desc.end(), row, row + 32);
+          }
+        }
+        off[j + 1] = off[j] + (int32_t)s.obs.size();
+        if (nd && !s.bad && !s.obs.empty()) { ref_kf[j] = kf_index(s.ref); ref_level[j] = s.level; for (int k = 0; k < 3; k++) X[3 * (size_t)j + k] = s.X[k]; }
+      }
+      const int nobs = off[n];
+      std::vector<int32_t> best(n, -1); std::vector<uint8_t> dout(32 * (size_t)n), wrote(n, 0);
+      std::vector<double> normal(3 * (size_t)n); std::vector<float> mm(2 * (size_t)n);
+      const std::vector<float>& table = tables[std::min(g, tables.size() - 1)];
+      dropin::check(orbl_update_map_points(n, off.data(), X.data(), ref_kf.data(), ref_level.data(), pt_good.data(), nobs, nd ? obs_kf.data() : nullptr,
+                                           desc ? obs_desc.data() : nullptr, desc ? kf_good.data() : nullptr, (int)kf_at.size(), centers.data(), table.data(),
+                                           (int)table.size(), what & (ORBL_MP_DESC | ORBL_MP_NORMAL_DEPTH), best.data(), dout.data(), normal.data(), mm.data(),
+                                           wrote.data()), "orbl_update_map_points");
+      for (int j = 0; j < n; j++) {
+        MapPoint* mp = points[idx[j]];
+        const Snap& s = S[idx[j]];
+        if (desc && best[j] >= 0) {
+          const std::pair<KeyFrame*, size_t>& o = s.obs[best[j]];
+          std::unique_lock<std::mutex> lock = lock_features(mp, 0);
+          mp->descriptor_ = dropin::row_copy(o.first->descriptors_, (int)o.second, 0);       // (:311-314) descriptors[best_index].clone()
+        }
+        if (nd && wrote[j]) {
+          Vector3d v;
+          for (int k = 0; k < 3; k++) v[k] = normal[3 * (size_t)j + k];
+          std::unique_lock<std::mutex> lock = lock_pose(mp, 0);                           // (:373-377)
+          mp->max_distance_ = mm[2 * (size_t)j + 1];
+          mp->min_distance_ = mm[2 * (size_t)j];
+          mp->normal_vector_ = v;
+        }
+      }
+    }
+  }
+
+ private:
+  // the reference's MapPoint::mutex_features_ / mutex_pose_ when the type has them (the mock data model of tests/cpp has none)
+  template <class P> static auto lock_features(P* p, int) -> decltype((void)p->mutex_features_, std::unique_lock<std::mutex>()) {
+    return std::unique_lock<std::mutex>(p->mutex_features_);
+  }
+  template <class P> static std::unique_lock<std::mutex> lock_features(P*, long) { return std::unique_lock<std::mutex>(); }
+  template <class P> static auto lock_pose(P* p, int) -> decltype((void)p->mutex_pose_, std::unique_lock<std::mutex>()) {
+    return std::unique_lock<std::mutex>(p->mutex_pose_);
+  }
+  template <class P> static std::unique_lock<std::mutex> lock_pose(P*, long) { return std::unique_lock<std::mutex>(); }
 };
 
 }  // namespace ORB_SLAM2

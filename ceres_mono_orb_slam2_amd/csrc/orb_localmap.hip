@@ -385,3 +385,6 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 }
 
 }  // extern "C"
+
+// MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth for a batch of points (orbl_update_map_points*)
+#include "orb_mappoint.inc"

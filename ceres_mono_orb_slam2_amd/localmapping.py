@@ -106,3 +106,68 @@ def fuse_batch(keyframes, q_uv, q_radius, q_level, mp_desc, inv_level_sigma2, si
     _lib.check(L.orbl_fuse_batch(C.cast(kf, C.c_void_p), T, _addr(uv), _addr(rad), _addr(lvl), M, _addr(md), _addr(ils), len(ils), _addr(bi), _addr(bd)),
                "orbl_fuse_batch")
     return bi[:T, :M], bd[:T, :M]
+
+
+MP_DESC = 1                          # ORBL_MP_DESC
+MP_NORMAL_DEPTH = 2                  # ORBL_MP_NORMAL_DEPTH
+
+
+def update_map_points(obs_off, obs_desc=None, obs_kf_good=None, X=None, ref_kf=None, ref_level=None, obs_kf=None, kf_center=None,
+                      scale_factors=None, pt_good=None, what=MP_DESC | MP_NORMAL_DEPTH, out=None):
+    """MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth for a batch of points (orbl_update_map_points).
+    obs_off[npts+1] CSR offsets into the observation arrays (list order = the point's std::map order); obs_desc[nobs,32],
+    obs_kf_good[nobs] (None = all good) for the descriptor; X[npts,3], ref_kf[npts], ref_level[npts], obs_kf[nobs],
+    kf_center[nkf,3], scale_factors[n_levels] for the normal and depth; pt_good[npts] (None = all good).
+    out: optional dict of preset output arrays (best_obs, desc, normal, min_max, nd_written); entries the call leaves unchanged
+    keep their values.  Returns that dict: best_obs[npts] int32 (-1 = descriptor unchanged), desc[npts,32] uint8,
+    normal[npts,3] float64, min_max[npts,2] float32 {min, max}, nd_written[npts] uint8."""
+    L = _lib.load()
+    off = _c(obs_off, np.int32).reshape(-1)
+    npts = len(off) - 1
+    nobs = int(off[-1]) if npts >= 0 and len(off) else 0
+    o = {} if out is None else out
+    o.setdefault("best_obs", np.full(max(npts, 0), -1, np.int32)); o.setdefault("desc", np.zeros((max(npts, 0), 32), np.uint8))
+    o.setdefault("normal", np.zeros((max(npts, 0), 3), np.float64)); o.setdefault("min_max", np.zeros((max(npts, 0), 2), np.float32))
+    o.setdefault("nd_written", np.zeros(max(npts, 0), np.uint8))
+    for k, dt in (("best_obs", np.int32), ("desc", np.uint8), ("normal", np.float64), ("min_max", np.float32), ("nd_written", np.uint8)):
+        assert o[k].dtype == dt and o[k].flags.c_contiguous, k
+    desc = _c(obs_desc, np.uint8).reshape(-1, 32) if obs_desc is not None else None
+    kg = _c(obs_kf_good, np.uint8) if obs_kf_good is not None else None
+    Xa = _c(X, np.float64).reshape(-1, 3) if X is not None else None
+    rk = _c(ref_kf, np.int32) if ref_kf is not None else None
+    rl = _c(ref_level, np.int32) if ref_level is not None else None
+    ok_ = _c(obs_kf, np.int32) if obs_kf is not None else None
+    kc = _c(kf_center, np.float64).reshape(-1, 3) if kf_center is not None else None
+    sf = _c(scale_factors, np.float32) if scale_factors is not None else None
+    pg = _c(pt_good, np.uint8) if pt_good is not None else None
+    vp, i32 = C.c_void_p, C.c_int
+    L.orbl_update_map_points.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    _lib.check(L.orbl_update_map_points(npts, _addr(off), _addr(Xa), _addr(rk), _addr(rl), _addr(pg), nobs, _addr(ok_), _addr(desc), _addr(kg),
+                                        len(kc) if kc is not None else 0, _addr(kc), _addr(sf), len(sf) if sf is not None else 0, int(what),
+                                        _addr(o["best_obs"]), _addr(o["desc"]), _addr(o["normal"]), _addr(o["min_max"]), _addr(o["nd_written"])),
+               "orbl_update_map_points")
+    return o
+
+
+def update_map_points_device(obs_off, obs_desc, obs_kf_good, X, ref_kf, ref_level, obs_kf, kf_center, scale_factors, pt_good, what, out):
+    """orbl_update_map_points_device on torch CUDA tensors (the same arguments as update_map_points; None where a pointer may be
+    NULL); out = dict of device tensors (best_obs, desc, normal, min_max, nd_written), written on the current stream."""
+    import torch
+    L = _lib.load()
+    npts = obs_off.numel() - 1
+    nobs = obs_desc.shape[0] if obs_desc is not None else (obs_kf.numel() if obs_kf is not None else 0)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_update_map_points_workspace(npts, C.byref(nbytes)), "orbl_update_map_points_workspace")
+    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=obs_off.device)
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    vp, i32 = C.c_void_p, C.c_int
+    L.orbl_update_map_points_device.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    _lib.check(L.orbl_update_map_points_device(npts, p(obs_off), p(X), p(ref_kf), p(ref_level), p(pt_good), nobs, p(obs_kf), p(obs_desc), p(obs_kf_good),
+                                               kf_center.shape[0] if kf_center is not None else 0, p(kf_center), p(scale_factors),
+                                               scale_factors.numel() if scale_factors is not None else 0, int(what), p(out.get("best_obs")), p(out.get("desc")),
+                                               p(out.get("normal")), p(out.get("min_max")), p(out.get("nd_written")), p(ws),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_update_map_points_device")
+    out["_workspace"] = ws                                       # (kept alive until the caller synchronises)
+    return out

@@ -384,6 +384,49 @@ int orbl_fuse_batch(const orbl_fuse_keyframe* keyframes, int n_keyframes, const 
 int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* keyframes, int n_keyframes, const float* q_uv, const float* q_radius, const int32_t* q_level,
                          int n_points, const uint8_t* mp_desc, int n_levels, int32_t* best_idx, int32_t* best_dist);
 
+/* ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:256-315) and MapPoint::UpdateNormalAndDepth (:335-378) for a BATCH of
+ * npts map points in ONE call: the per-point loops of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:141-152), the tail of
+ * CreateNewMapPoints (:386-388), the tail of SearchInNeighbors (:476-485) and the LocalBA write-back (src/CeresOptimizer.cc:590-598).
+ * Points are independent; a batch computes what the reference's loop of single calls computes.
+ *   what: ORBL_MP_DESC, ORBL_MP_NORMAL_DEPTH or both.
+ *   per point p: its observations are obs_off[p] .. obs_off[p+1] (CSR, obs_off[0] = 0, obs_off[npts] = nobs) in the caller's
+ *     std::map<KeyFrame*, size_t> iteration order; X[p][3] = world position; ref_kf[p] = index of GetReferenceKeyFrame() in kf_center;
+ *     ref_level[p] = the octave of that keyframe's keypoint observations[reference_keyframe] (:369-371; when the reference keyframe is
+ *     not in the list, std::map::operator[] on the method's local copy yields index 0: keypoint 0's octave); pt_good[p] (nullable =
+ *     all 1) = !isBad().
+ *   per observation e: obs_kf[e] = index of the keyframe in kf_center[nkf][3] (GetCameraCenter()), obs_desc[e][32] = that keyframe's
+ *     descriptor row (gathered by the caller, :272-279), obs_kf_good[e] (nullable = all 1) = !keyframe->isBad().
+ *   scale_factors[n_levels]: the reference keyframe's table (:372-373; every keyframe copies it from the same extractor).
+ * Descriptor (:256-315): the observations of good keyframes only, N of them; the row of the N x N Hamming matrix with the least
+ *   median (sorted_row[(N - 1) / 2], the diagonal zero included), first row on ties.  best_obs[p] = its position in the point's list
+ *   (0-based from obs_off[p]) and desc_out[p][32] = its bytes; best_obs[p] = -1 and desc_out[p] untouched when N = 0, the point is
+ *   bad or its list is empty.
+ * Normal and depth (:335-378): ALL observations (bad keyframes included): normal[p] = sum (X - O_i) / |X - O_i| / n in double, list
+ *   order; dist = (float)|X - O_ref|, min_max[p] = {max / scale_factors[n_levels - 1], max = dist * scale_factors[ref_level]} in
+ *   float; nd_written[p] = 1.  Bad points and empty lists: nd_written[p] = 0, normal[p] / min_max[p] untouched.
+ * Outputs of a part `what` does not select are not touched and may be NULL, as may the inputs only that part reads (ref_kf,
+ * ref_level, X, obs_kf, kf_center, scale_factors for the normal; obs_desc, obs_kf_good for the descriptor).
+ * Host pointers, synchronous.  ORBHIP_EINVAL before any device work for negative counts, offsets that do not run monotonically from
+ * 0 to nobs, keyframe indices outside [0, nkf) and levels outside [0, n_levels).                                                   */
+#define ORBL_MP_DESC 1
+#define ORBL_MP_NORMAL_DEPTH 2
+int orbl_update_map_points(int npts, const int32_t* obs_off, const double* X, const int32_t* ref_kf, const int32_t* ref_level, const uint8_t* pt_good,
+                           int nobs, const int32_t* obs_kf, const uint8_t* obs_desc, const uint8_t* obs_kf_good, int nkf, const double* kf_center,
+                           const float* scale_factors, int n_levels, int what, int32_t* best_obs, uint8_t* desc_out, double* normal, float* min_max,
+                           uint8_t* nd_written);
+/* The same with DEVICE pointers, enqueued on `stream` (callers that keep keyframe data resident; the orbm_hamming_best2_device
+ * pattern).  `workspace`: device memory of at least orbl_update_map_points_workspace(npts) bytes, not shared with concurrent calls.
+ * obs_desc must be 16-byte and desc_out 4-byte aligned.  Counts, NULL pointers and alignment are checked on the host; the data is
+ * not read there, so a point whose offsets, keyframe indices or level are out of range is left unchanged (best_obs -1,
+ * nd_written 0) instead of failing the call.  best_obs and nd_written are written for every point, the other outputs only where
+ * the host entry point writes them.                                                                                              */
+int orbl_update_map_points_device(int npts, const int32_t* d_obs_off, const double* d_X, const int32_t* d_ref_kf, const int32_t* d_ref_level,
+                                  const uint8_t* d_pt_good, int nobs, const int32_t* d_obs_kf, const uint8_t* d_obs_desc, const uint8_t* d_obs_kf_good,
+                                  int nkf, const double* d_kf_center, const float* d_scale_factors, int n_levels, int what, int32_t* d_best_obs,
+                                  uint8_t* d_desc_out, double* d_normal, float* d_min_max, uint8_t* d_nd_written, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_update_map_points_device needs for npts points (host arithmetic). */
+int orbl_update_map_points_workspace(int npts, size_t* bytes);
+
 /* ---- the per-frame Tracking step with the motion model, device-resident (src/Tracking.cc:616-646): Frame construction
  * (ORBextractor::operator(), AssignFeaturesToGrid; zero distortion: the undistorted keypoints are the raw ones, as for the
  * KITTI configurations), ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) (src/ORBmatcher.cc:1161-1271,
