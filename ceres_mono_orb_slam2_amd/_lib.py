@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ORBHIP_LIB") or os.path.join(_HERE, "lib", "liborbsla
 # every symbol include/orbslam_hip.h declares (tests check that the library exports them all)
 SYMBOLS = [
     "orbhip_last_error", "orbhip_device_count", "orbhip_version", "orbhip_set_default_device", "orbhip_get_default_device", "orbhip_set_thread_priority", "orbhip_copy_pinned_async", "orbl_create_new_map_points", "orbl_fuse_batch", "orbl_update_map_points", "orbl_update_map_points_device", "orbl_update_map_points_workspace", "orbt_relocalization_search_by_bow",
+    "orbt_initialize", "orbt_initialize_batch_device", "orbt_initialize_workspace",
     "orbx_create", "orbx_destroy", "orbx_get_levels", "orbx_set_opencv_variant", "orbx_get_tables", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_set_profiling", "orbx_get_stage_ms", "orbx_get_level_image", "orbx_get_level_candidates", "orbx_get_level_selected",
     "orbm_descriptor_distance", "orbm_hamming_best2_device", "orbm_hamming_best2", "orbm_match_frames_batch_device",
@@ -41,6 +42,17 @@ class BaLocalProblem(C.Structure):            # ba_local_problem
 
 class OrbHipError(RuntimeError):
     pass
+
+
+class InitReport(C.Structure):                # orbt_init_report
+    _fields_ = [("model", C.c_int32), ("reason", C.c_int32), ("score_h", C.c_float), ("score_f", C.c_float), ("rh", C.c_float),
+                ("best_h", C.c_int32), ("best_f", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("motion", C.c_int32),
+                ("n_good", C.c_int32 * 8), ("parallax", C.c_float * 8)]
+
+
+class InitTrace(C.Structure):                 # orbt_init_trace
+    _fields_ = [("H21", C.c_void_p), ("H12", C.c_void_p), ("F21", C.c_void_p), ("score_h", C.c_void_p), ("score_f", C.c_void_p),
+                ("motion_R", C.c_void_p), ("motion_t", C.c_void_p), ("inliers_h", C.c_void_p), ("inliers_f", C.c_void_p)]
 
 
 class BaOptions(C.Structure):
@@ -152,6 +164,9 @@ def load():
     L.ba_set_wait_limit_ms.argtypes = [C.c_double]
     L.orbhip_copy_pinned_async.argtypes = [vp, vp, C.c_size_t, vp]
     L.orbl_update_map_points_workspace.argtypes = [i32, vp]
+    L.orbt_initialize.argtypes = [vp, i32, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, C.POINTER(InitReport), C.POINTER(InitTrace)]
+    L.orbt_initialize_batch_device.argtypes = [i32, vp, vp, i32, vp, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbt_initialize_workspace.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]
     L.ba_solve_batch.argtypes = [vp, i32, C.POINTER(BaOptions), vp]
     L.ba_local_bundle_adjustment_batch.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, vp]
     _lib = L

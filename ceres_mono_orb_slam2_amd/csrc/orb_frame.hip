@@ -421,3 +421,6 @@ extern "C" int orbm_triangulate_matches(const double* Tcw1, const double* Tcw2, 
   cleanup();
   return 0;
 }
+
+// Initializer::Initialize for a batch of frame pairs (orbt_initialize*)
+#include "orb_init.inc"

@@ -505,3 +505,58 @@ def make_degenerate_ba(seed):
     return dict(kind=kind, K4=g["K4"], poses0=g["poses0"], cam_fixed=fixed, pts0=g["pts0"], obs_cam=oc, obs_pt=op, obs_uv=uv, obs_w=w,
                 obs_robust=rb, iterations=iters, oracle_obs=oracle_obs)
 
+
+
+def make_two_view(seed, kind="general", n_kps=1000, outlier_frac=0.0, noise=0.0, w=1241, h=376):
+    """Two views for Initializer::Initialize (orbt_initialize).  Frame 1 is the world frame; frame 2 = R X + t.
+    kind: "general" (depths 4-40 m, 0.8 m sideways baseline: F should win), "planar" (every point on one tilted plane: H should
+    win), "rotation" (mostly rotation: a 0.25 m baseline at 20-45 m, parallax below 1 degree: the parallax test rejects), "sparse" (general geometry, a quarter of the
+    keypoints matched: too few points for either model).  Keypoints are undistorted (x, y) float32; `noise` is the standard
+    deviation in pixels added to both frames, `outlier_frac` of the matches point at a random keypoint of frame 2.
+    Returns dict kps1[n_kps, 2], kps2[n2, 2], matches12[n_kps] (-1 = unmatched), K4, R (3 x 3), t (3), X[n_kps, 3] (frame-1
+    coordinates; NaN where unmatched), outlier[n_kps] bool."""
+    rng = np.random.default_rng(seed)
+    K4 = np.array([718.856, 718.856, 607.1928, 185.2157], np.float32)
+    fx, fy, cx, cy = (float(v) for v in K4)
+    if kind == "rotation":
+        R, t = quat_to_R(quat_from_rotvec(np.array([0.004, 0.02, -0.003]))), np.array([0.25, 0.0, 0.0])
+    else:
+        R, t = quat_to_R(quat_from_rotvec(np.array([0.01, -0.04, 0.005]))), np.array([0.8, 0.05, -0.3])
+    match_frac = 0.25 if kind == "sparse" else 0.9
+    n = int(n_kps)
+    u = rng.uniform(8, w - 8, 4 * n + 64); v = rng.uniform(8, h - 8, 4 * n + 64)
+    rx, ry = (u - cx) / fx, (v - cy) / fy
+    if kind == "planar":
+        z = 12.0 / (1.0 - 0.4 * rx + 0.2 * ry)                  # the plane z = 12 + 0.4 x - 0.2 y
+    elif kind == "rotation":
+        z = rng.uniform(20, 45, len(u))
+    else:
+        z = rng.uniform(4, 40, len(u))
+    X = np.stack([rx * z, ry * z, z], 1)
+    X2 = X @ R.T + t
+    u2 = fx * X2[:, 0] / X2[:, 2] + cx; v2 = fy * X2[:, 1] / X2[:, 2] + cy
+    inside = (X2[:, 2] > 0.5) & (u2 >= 0) & (u2 < w) & (v2 >= 0) & (v2 < h)
+    keep = np.nonzero(inside)[0][:n]
+    assert len(keep) == n, "make_two_view: too few points project into frame 2"
+    X, u, v, u2, v2 = X[keep], u[keep], v[keep], u2[keep], v2[keep]
+    matched = rng.random(n) < match_frac
+    n_extra = n // 10
+    n2 = int(matched.sum()) + n_extra
+    kps2 = np.empty((n2, 2))
+    order = rng.permutation(n2)                                  # frame 2's keypoint order is its own
+    kps2[order[:matched.sum()], 0] = u2[matched]; kps2[order[:matched.sum()], 1] = v2[matched]
+    kps2[order[matched.sum():], 0] = rng.uniform(0, w, n_extra); kps2[order[matched.sum():], 1] = rng.uniform(0, h, n_extra)
+    matches12 = np.full(n, -1, np.int32)
+    matches12[matched] = order[:matched.sum()]
+    outlier = np.zeros(n, bool)
+    mi = np.nonzero(matched)[0]
+    n_out = int(round(outlier_frac * len(mi)))
+    if n_out:
+        bad = rng.choice(mi, n_out, replace=False)
+        matches12[bad] = rng.integers(0, n2, n_out)
+        outlier[bad] = True
+    kps1 = np.stack([u, v], 1)
+    if noise > 0:
+        kps1 = kps1 + rng.normal(0, noise, kps1.shape); kps2 = kps2 + rng.normal(0, noise, kps2.shape)
+    Xo = np.where(matched[:, None], X, np.nan)
+    return dict(kps1=kps1.astype(np.float32), kps2=kps2.astype(np.float32), matches12=matches12, K4=K4, R=R, t=t, X=Xo, outlier=outlier)

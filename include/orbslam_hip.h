@@ -427,6 +427,69 @@ int orbl_update_map_points_device(int npts, const int32_t* d_obs_off, const doub
 /* *bytes = the workspace orbl_update_map_points_device needs for npts points (host arithmetic). */
 int orbl_update_map_points_workspace(int npts, size_t* bytes);
 
+/* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
+ * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
+ * frame 2 = the current one.
+ *   kps1[n1][2], kps2[n2][2]: undistorted keypoints {x, y}; matches12[n1]: frame-2 index or -1 (Tracking's init_matches_);
+ *   K4 = {fx, fy, cx, cy} (Frame::K_); sigma (> 0) and iterations: the Initializer's constructor arguments (1.0, 200 at the call site);
+ *   ransac_sets[iterations][8]: positions in the ascending list of matches (i1, matches12[i1]) - the sets :88-101 draw
+ *     (DUtils::Random, seeded once per process: the library cannot see that sequence, so the sets are an input).
+ * Outputs on success (report->reason == ORBT_INIT_OK): R21[9] (row-major), t21[3], P3D[n1][3] on the rows the winning motion
+ * accepted (the other rows keep their values), triangulated[n1] on every row.  On rejection the four are left untouched.
+ * report (always written): the chosen model (0 = H, 1 = F; -1 = none), the reason, both models' best scores and iterations
+ * (-1 = no hypothesis scored above 0), RH, the inlier count of the chosen model's winner, the winning motion (-1 = none) and
+ * nGood / parallax (degrees) per motion of the chosen model (4 used for F).
+ * Reasons (the first rule of the reference that rejects, in its order):                                                         */
+#define ORBT_INIT_OK 0
+#define ORBT_INIT_BAD_INPUT 1      /* device entry only: counts, offsets, matches12 or set entries out of range, fewer than 8 matches */
+#define ORBT_INIT_NO_MODEL 2       /* no hypothesis of the chosen model scored above 0 (the reference reads an uninitialised matrix) */
+#define ORBT_INIT_H_DEGENERATE 3   /* ReconstructH: d1 / d2 < 1.00001 or d2 / d3 < 1.00001 (:573) */
+#define ORBT_INIT_H_AMBIGUOUS 4    /* ReconstructH: secondBestGood >= 0.75 bestGood (:683) */
+#define ORBT_INIT_H_PARALLAX 5     /* ReconstructH: bestParallax < minParallax = 1 */
+#define ORBT_INIT_H_FEW 6          /* ReconstructH: bestGood <= 50 or bestGood <= 0.9 N */
+#define ORBT_INIT_F_FEW 7          /* ReconstructF: maxGood < max(int(0.9 N), 50) (:496) */
+#define ORBT_INIT_F_AMBIGUOUS 8    /* ReconstructF: more than one motion with nGood > 0.7 maxGood */
+#define ORBT_INIT_F_PARALLAX 9     /* ReconstructF: the first motion with nGood == maxGood has parallax <= 1 (no fall-through, :501-537) */
+#define ORBT_INIT_MAX_N 32768      /* keypoints per frame */
+#define ORBT_INIT_MAX_ITERATIONS 4096
+#define ORBT_INIT_MAX_PAIRS 65535
+typedef struct orbt_init_report {
+  int32_t model, reason;
+  float score_h, score_f, rh;
+  int32_t best_h, best_f;
+  int32_t n_matches, n_inliers;
+  int32_t motion;
+  int32_t n_good[8];
+  float parallax[8];
+} orbt_init_report;
+/* Optional per-call trace (host entry only; every member nullable): the per-iteration H21, H12, F21 [iterations][9] exactly as the
+ * scoring consumed them, the per-iteration scores [iterations], the chosen model's motions R [8][9] / t [8][3] (zero where the model
+ * has fewer or none were made) and the H and F winners' inlier masks [n_matches] (0 where the model has no winner).             */
+typedef struct orbt_init_trace {
+  double* H21; double* H12; double* F21;
+  float* score_h; float* score_f;
+  double* motion_R; double* motion_t;
+  uint8_t* inliers_h; uint8_t* inliers_f;
+} orbt_init_trace;
+/* Host pointers, synchronous.  ORBHIP_EINVAL before any device work for n1 / n2 outside [0, 32768], iterations outside [1, 4096],
+ * sigma <= 0 (or not finite), fewer than 8 matches, matches12 entries outside [-1, n2), set entries outside [0, n_matches) and NULL
+ * required pointers.  It is orbt_initialize_batch_device with one pair.                                                           */
+int orbt_initialize(const float* kps1, int n1, const float* kps2, int n2, const int32_t* matches12, const float* K4, float sigma, int iterations,
+                    const int32_t* ransac_sets, double* R21, double* t21, double* P3D, uint8_t* triangulated, orbt_init_report* report,
+                    const orbt_init_trace* trace);
+/* The same for npairs pairs with DEVICE pointers, enqueued on `stream`: pair p's keypoints are rows off1[p] .. off1[p+1] of
+ * kps1 [n1_total][2] (off2 / kps2 likewise; CSR, device arrays), its matches12, P3D and triangulated rows share kps1's offsets,
+ * K4[p][4], ransac_sets[p][iterations][8], R21[p][9], t21[p][3], report[p].  One sigma and iterations for all pairs.
+ * Counts, sigma and NULL pointers are checked on the host; the data is not read there, so a pair whose offsets, matches12 or set
+ * entries are out of range, or that has fewer than 8 matches, fails alone with ORBT_INIT_BAD_INPUT.  `workspace`: device memory of
+ * orbt_initialize_workspace() bytes, not shared with concurrent calls.  No allocation, no host synchronisation.                 */
+int orbt_initialize_batch_device(int npairs, const float* d_kps1, const int32_t* d_off1, int n1_total, const float* d_kps2, const int32_t* d_off2,
+                                 int n2_total, const int32_t* d_matches12, const float* d_K4, float sigma, int iterations, const int32_t* d_ransac_sets,
+                                 double* d_R21, double* d_t21, double* d_P3D, uint8_t* d_triangulated, orbt_init_report* d_report, void* d_workspace,
+                                 void* stream);
+/* *bytes = the workspace orbt_initialize_batch_device needs (host arithmetic); npairs in [1, 65535], n*_total <= 32768 npairs. */
+int orbt_initialize_workspace(int npairs, int n1_total, int n2_total, int iterations, size_t* bytes);
+
 /* ---- the per-frame Tracking step with the motion model, device-resident (src/Tracking.cc:616-646): Frame construction
  * (ORBextractor::operator(), AssignFeaturesToGrid; zero distortion: the undistorted keypoints are the raw ones, as for the
  * KITTI configurations), ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) (src/ORBmatcher.cc:1161-1271,
