@@ -560,3 +560,41 @@ def make_two_view(seed, kind="general", n_kps=1000, outlier_frac=0.0, noise=0.0,
         kps1 = kps1 + rng.normal(0, noise, kps1.shape); kps2 = kps2 + rng.normal(0, noise, kps2.shape)
     Xo = np.where(matched[:, None], X, np.nan)
     return dict(kps1=kps1.astype(np.float32), kps2=kps2.astype(np.float32), matches12=matches12, K4=K4, R=R, t=t, X=Xo, outlier=outlier)
+
+
+def make_reloc(seed, n=200, outlier_frac=0.0, noise=0.0, kind="general", w=1241, h=376, n_levels=8, scale_factor=1.2):
+    """One relocalisation candidate for PnPsolver (orbt_pnp_*): a ground-truth Tcw, n world points in front of a KITTI-like camera,
+    their float32 pixels, a per-point octave and its sigma2 (scale_factor^(2 octave)), `outlier_frac` of the pixels replaced by random
+    ones, `noise` = the standard deviation in pixels of the others.  kind: "general" (depths 4-40 m), "planar" (every point on one
+    tilted plane: EPnP's weak case), "few" (n is cut to 6 points: below the adjusted minimum of Tracking's parameters, 10).
+    Returns dict p3d[n, 3] float32 (world), p2d[n, 2] float32, octave[n], sigma2[n] float32, K4, Tcw (4 x 4), R, t, outlier[n] bool."""
+    rng = np.random.default_rng(seed)
+    K4 = np.array([718.856, 718.856, 607.1928, 185.2157], np.float32)
+    fx, fy, cx, cy = (float(v) for v in K4)
+    if kind == "few":
+        n = min(int(n), 6)
+    n = int(n)
+    R = quat_to_R(quat_from_rotvec(rng.uniform(-0.3, 0.3, 3)))
+    t = rng.uniform(-2.0, 2.0, 3)
+    u = rng.uniform(8, w - 8, n); v = rng.uniform(8, h - 8, n)
+    rx, ry = (u - cx) / fx, (v - cy) / fy
+    if kind == "planar":
+        z = 12.0 / (1.0 - 0.4 * rx + 0.2 * ry)                  # the plane z = 12 + 0.4 x - 0.2 y of the camera frame
+    else:
+        z = rng.uniform(4, 40, n)
+    Xc = np.stack([rx * z, ry * z, z], 1)
+    Xw = ((Xc - t) @ R).astype(np.float32)                       # Xc = R Xw + t
+    Xc32 = Xw.astype(np.float64) @ R.T + t                      # the pixels of the float32 points: noise-free means consistent
+    p2d = np.stack([fx * Xc32[:, 0] / Xc32[:, 2] + cx, fy * Xc32[:, 1] / Xc32[:, 2] + cy], 1)
+    if noise > 0:
+        p2d = p2d + rng.normal(0, noise, p2d.shape)
+    outlier = np.zeros(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.choice(n, n_out, replace=False)
+        p2d[bad, 0] = rng.uniform(0, w, n_out); p2d[bad, 1] = rng.uniform(0, h, n_out)
+        outlier[bad] = True
+    octave = rng.integers(0, n_levels, n).astype(np.int32)
+    sigma2 = (np.float32(scale_factor) ** (2 * octave)).astype(np.float32)
+    Tcw = np.eye(4); Tcw[:3, :3] = R; Tcw[:3, 3] = t
+    return dict(p3d=Xw, p2d=p2d.astype(np.float32), octave=octave, sigma2=sigma2, K4=K4, Tcw=Tcw, R=R, t=t, outlier=outlier)

@@ -319,8 +319,8 @@ int orbm_search_for_triangulation(const float* kps1, const uint8_t* desc1, const
  * frame an earlier orbt_* call of this thread left there.  Per candidate i: slot_owner[i][f] = the keyframe feature whose map
  * point vpMapPointMatches[f] holds (-1: none) after the rotation check, nmatches[i] = the return value (the caller discards the
  * candidate below 15, :1019).  What follows - PnPsolver::iterate per candidate, then PoseOptimization /
- * SearchByProjection(F, KF, found, th, ORBdist) rounds (:1040-1120) - starts from a PnP pose and stays with the caller: PnP is out of
- * scope, the rounds are ba_pose_optimization and the reloc_kf form of orbm_search_by_projection.             */
+ * SearchByProjection(F, KF, found, th, ORBdist) rounds (:1040-1120) - is made of further calls: orbt_pnp_iterate_batch_device runs
+ * one PnPsolver::iterate of every candidate, the rounds are ba_pose_optimization and the reloc_kf form of orbm_search_by_projection. */
 typedef struct orbt_reloc_keyframe {
   const uint8_t* desc; const uint8_t* valid; const float* angle; int n;      /* descriptors, 1 = usable map point (not NULL, not isBad()), keypoint angles */
   const uint32_t* fv_node; const uint32_t* fv_off; const uint32_t* fv_idx; int fv_n;      /* the keyframe's FeatureVector (orbv_transform's layout) */
@@ -489,6 +489,77 @@ int orbt_initialize_batch_device(int npairs, const float* d_kps1, const int32_t*
                                  void* stream);
 /* *bytes = the workspace orbt_initialize_batch_device needs (host arithmetic); npairs in [1, 65535], n*_total <= 32768 npairs. */
 int orbt_initialize_workspace(int npairs, int n1_total, int n2_total, int iterations, size_t* bytes);
+
+/* ---- PnPsolver (src/PnPsolver.cc; called from Tracking::Relocalization, src/Tracking.cc:1003-1060): EPnP inside RANSAC, one
+ * `iterate` call per candidate and library call, for a batch of candidates.
+ *   p3d[n][3]: the matched map points' world positions narrowed to float (mvP3Dw, :93-94); p2d[n][2]: the undistorted keypoints
+ *   (mvP2D); max_err[n] = level_sigma2[octave] * th2 (mvMaxError, :155-157); K4 = {fx, fy, cx, cy}.  The caller compacts the non-NULL,
+ *   non-bad matches (:79-102) and scatters the returned mask through mvKeyPointIndices (:232-237).
+ *   min_inliers: the ADJUSTED mRansacMinInliers of orbt_pnp_ransac_params (>= 4).
+ *   sets[n_sets][4]: the minimal sets, indices into the n points, distinct inside a set - what :192-203 draws from DUtils::Random
+ *     (process-global, drawn lazily between candidates: the library cannot see that sequence, so the sets are an input).  One
+ *     `iterate(nIterations, ...)` call of the reference runs while `mnIterations < mRansacMaxIts || nCurrentIterations < nIterations`
+ *     (:183), so the caller supplies n_sets = max(mRansacMaxIts - mnIterations, nIterations) sets and advances mnIterations by
+ *     result->consumed; a call always ends with a refined pose or with every set used.
+ *   best_count / best_mask[n] / best_Tcw[16] (row-major 4 x 4): mnBestInliers, mvbBestInliers, mBestTcw - in/out, zero / zeros /
+ *     anything before the first call.  best_count must equal the number of non-zero mask bytes.
+ * Per iteration (:183-242): compute_pose on the set (EPnP, double), CheckInliers (:313-345, the reference's float / double mix); with
+ * count >= min_inliers a count STRICTLY above best_count becomes the state, then Refine (:263-310) refits on the BEST mask and returns
+ * its pose when the refit has STRICTLY more than min_inliers inliers.
+ * result (always written except Tcw on BAD_INPUT): status, consumed = the sets the reference would have used before returning,
+ * Tcw (row-major; identity where the reference returns identity), n_inliers, n_refits = Refine calls made (one per distinct best mask:
+ * a mask that failed is not refitted again, the outcome is the same).  inliers[n]: the refined mask (REFINED), the best mask
+ * (EXHAUSTED_BEST) or zeros.  The state is as of iteration `consumed`; sets after it leave no trace in any output.
+ * Parity: EPnP takes rows 8-11 of cvSVD's Ut of the 12 x 12 MtM; with 4 points MtM has a null space of dimension >= 4 and those rows
+ * are an arbitrary basis of it, so a hypothesis' pose depends on the eigen-solver and equality with an OpenCV build is not attainable
+ * hypothesis by hypothesis ("PnP RANSAC").  tests/nppnp.py restates this implementation's operation order. */
+#define ORBT_PNP_REFINED 0         /* Refine succeeded at iteration consumed - 1: Tcw = mRefinedTcw, inliers = mvbRefinedInliers */
+#define ORBT_PNP_EXHAUSTED_BEST 1  /* every set used, best_count >= min_inliers: Tcw = mBestTcw, inliers = mvbBestInliers, bNoMore */
+#define ORBT_PNP_EXHAUSTED_NONE 2  /* every set used, no hypothesis reached min_inliers: identity, bNoMore */
+#define ORBT_PNP_TOO_FEW 3         /* n < min_inliers (:174-178): identity, bNoMore, consumed = 0, the state untouched */
+#define ORBT_PNP_BAD_INPUT 4       /* device entry only: offsets, n_sets, min_inliers < 4, a set entry out of range or repeated, a state that does not match */
+#define ORBT_PNP_MAX_N 32768       /* points per candidate */
+#define ORBT_PNP_MAX_ITERATIONS 4096
+#define ORBT_PNP_MAX_CANDIDATES 65535
+typedef struct orbt_pnp_params {
+  int32_t n, min_inliers, max_iterations;      /* N, the adjusted mRansacMinInliers and mRansacMaxIts */
+  float epsilon;                               /* the adjusted mRansacEpsilon */
+} orbt_pnp_params;
+typedef struct orbt_pnp_result {
+  int32_t status, consumed, n_inliers, n_refits;
+  double Tcw[16];
+} orbt_pnp_result;
+/* Optional per-call trace (host entry only; every member nullable), rows [n_sets]: per consumed iteration the hypothesis' R [9] and
+ * t [3], the approximation compute_pose chose (1..3, :523-525), its mean reprojection error and the inlier count (zeros beyond
+ * `consumed`); per Refine call k < n_refits the iteration that made it, its R, t and count (iteration -1 beyond n_refits).          */
+typedef struct orbt_pnp_trace {
+  double* R; double* t; int32_t* approx; double* rep_error; int32_t* count;
+  int32_t* refit_iteration; double* refit_R; double* refit_t; int32_t* refit_count;
+} orbt_pnp_trace;
+/* SetRansacParameters' arithmetic (:122-153) on the host: out->min_inliers = max(int(n * epsilon), min_inliers, min_set),
+ * out->epsilon = max(epsilon, min_inliers / n), out->max_iterations = max(1, min(ceil(log(1 - p) / log(1 - epsilon^3)),
+ * max_iterations)), 1 when min_inliers == n or when the quotient is not a number (n < min_inliers).  ORBHIP_EINVAL for min_set != 4
+ * (the reference uses no other value and EPnP on fewer points is undefined), n outside [0, 32768], probability outside (0, 1),
+ * epsilon outside (0, 1], min_inliers < 0, max_iterations < 1.                                                                   */
+int orbt_pnp_ransac_params(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon, orbt_pnp_params* out);
+/* One candidate, host pointers, synchronous.  ORBHIP_EINVAL before any device work for n outside [0, 32768], n_sets outside
+ * [0, 4096], min_inliers < 4, NULL required pointers and, when n >= min_inliers, set entries outside [0, n), an index repeated inside
+ * a set, or a best_count that is not the number of non-zero best_mask bytes.  It is orbt_pnp_iterate_batch_device with one candidate. */
+int orbt_pnp_iterate(const float* p3d, const float* p2d, const float* max_err, int n, const float* K4, int min_inliers, const int32_t* sets, int n_sets,
+                     int32_t* best_count, uint8_t* best_mask, double* best_Tcw, orbt_pnp_result* result, uint8_t* inliers, const orbt_pnp_trace* trace);
+/* The same for n_candidates candidates with DEVICE pointers, enqueued on `stream`: candidate c's points are rows off[c] .. off[c+1]
+ * of p3d / p2d / max_err / best_mask / inliers (CSR, device array of n_candidates + 1), K4[c][4], min_inliers[c], n_sets[c] <=
+ * iterations, sets[c][iterations][4], best_count[c], best_Tcw[c][16], result[c].  Counts and NULL pointers are checked on the host;
+ * the data is not read there, so a candidate with bad offsets, n_sets, min_inliers, set entries or state fails alone with
+ * ORBT_PNP_BAD_INPUT (its result gets the status, everything else of it stays as it was).  `workspace`: device memory of
+ * orbt_pnp_iterate_workspace() bytes, not shared with concurrent calls.  No allocation, no host synchronisation.                 */
+int orbt_pnp_iterate_batch_device(int n_candidates, const float* d_p3d, const float* d_p2d, const float* d_max_err, const int32_t* d_off, int n_total,
+                                  const float* d_K4, const int32_t* d_min_inliers, const int32_t* d_n_sets, int iterations, const int32_t* d_sets,
+                                  int32_t* d_best_count, uint8_t* d_best_mask, double* d_best_Tcw, orbt_pnp_result* d_result, uint8_t* d_inliers,
+                                  void* d_workspace, void* stream);
+/* *bytes = the workspace orbt_pnp_iterate_batch_device needs (host arithmetic); n_candidates in [1, 65535], n_total <= 32768
+ * n_candidates, iterations in [1, 4096].                                                                                         */
+int orbt_pnp_iterate_workspace(int n_candidates, int n_total, int iterations, size_t* bytes);
 
 /* ---- the per-frame Tracking step with the motion model, device-resident (src/Tracking.cc:616-646): Frame construction
  * (ORBextractor::operator(), AssignFeaturesToGrid; zero distortion: the undistorted keypoints are the raw ones, as for the
