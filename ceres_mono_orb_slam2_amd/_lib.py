@@ -13,6 +13,7 @@ SYMBOLS = [
     "orbhip_last_error", "orbhip_device_count", "orbhip_version", "orbhip_set_default_device", "orbhip_get_default_device", "orbhip_set_thread_priority", "orbhip_copy_pinned_async", "orbl_create_new_map_points", "orbl_fuse_batch", "orbl_update_map_points", "orbl_update_map_points_device", "orbl_update_map_points_workspace", "orbt_relocalization_search_by_bow",
     "orbt_initialize", "orbt_initialize_batch_device", "orbt_initialize_workspace",
     "orbt_pnp_ransac_params", "orbt_pnp_iterate", "orbt_pnp_iterate_batch_device", "orbt_pnp_iterate_workspace",
+    "orbt_sim3_ransac_params", "orbt_sim3_iterate", "orbt_sim3_iterate_batch_device", "orbt_sim3_iterate_workspace",
     "orbx_create", "orbx_destroy", "orbx_get_levels", "orbx_set_opencv_variant", "orbx_get_tables", "orbx_max_keypoints", "orbx_extract",
     "orbx_extract_batch_device", "orbx_set_profiling", "orbx_get_stage_ms", "orbx_get_level_image", "orbx_get_level_candidates", "orbx_get_level_selected",
     "orbm_descriptor_distance", "orbm_hamming_best2_device", "orbm_hamming_best2", "orbm_match_frames_batch_device",
@@ -67,6 +68,19 @@ class PnpResult(C.Structure):                 # orbt_pnp_result
 class PnpTrace(C.Structure):                  # orbt_pnp_trace
     _fields_ = [("R", C.c_void_p), ("t", C.c_void_p), ("approx", C.c_void_p), ("rep_error", C.c_void_p), ("count", C.c_void_p),
                 ("refit_iteration", C.c_void_p), ("refit_R", C.c_void_p), ("refit_t", C.c_void_p), ("refit_count", C.c_void_p)]
+
+
+class Sim3Params(C.Structure):                # orbt_sim3_params
+    _fields_ = [("n", C.c_int32), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Sim3Result(C.Structure):                # orbt_sim3_result
+    _fields_ = [("status", C.c_int32), ("consumed", C.c_int32), ("n_inliers", C.c_int32), ("scale", C.c_float), ("T12", C.c_double * 16),
+                ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class Sim3Trace(C.Structure):                 # orbt_sim3_trace
+    _fields_ = [("R", C.c_void_p), ("t", C.c_void_p), ("scale", C.c_void_p), ("count", C.c_void_p), ("relgap", C.c_void_p)]
 
 
 class BaOptions(C.Structure):
@@ -185,6 +199,11 @@ def load():
     L.orbt_pnp_iterate.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, C.POINTER(i32), vp, vp, C.POINTER(PnpResult), vp, C.POINTER(PnpTrace)]
     L.orbt_pnp_iterate_batch_device.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbt_pnp_iterate_workspace.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
+    L.orbt_sim3_ransac_params.argtypes = [i32, f64, i32, i32, C.POINTER(Sim3Params)]
+    L.orbt_sim3_iterate.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, C.POINTER(i32), vp, vp, vp, C.POINTER(C.c_float),
+                                    C.POINTER(Sim3Result), vp, C.POINTER(Sim3Trace)]
+    L.orbt_sim3_iterate_batch_device.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbt_sim3_iterate_workspace.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
     L.ba_solve_batch.argtypes = [vp, i32, C.POINTER(BaOptions), vp]
     L.ba_local_bundle_adjustment_batch.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, vp]
     _lib = L

@@ -1579,3 +1579,4 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
 }  // extern "C"
 
 #include "orb_pnp.inc"                  /* PnPsolver::iterate with EPnP for a batch of candidates: orbt_pnp_* */
+#include "orb_sim3solver.inc"          /* Sim3Solver::iterate (Horn inside RANSAC) for a batch of loop candidates: orbt_sim3_* */

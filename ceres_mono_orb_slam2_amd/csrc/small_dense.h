@@ -1,7 +1,9 @@
-// small_dense.h -- dense helpers for per-lane estimators (orb_init.inc: Initializer; orb_pnp.inc: PnPsolver / EPnP; a later Sim3Solver):
-// 3 x 3 products / inverse / SVD, the one-sided Jacobi in the operation order of null_vector4_dev (tri_math.h) for compile-time
-// shapes in registers (i_jacobi) and for run-time shapes behind a strided view (d_jacobi: 12 x 12 eigenvectors, small least squares).
-// The summation order of every function is fixed here and restated in tests/npinit.py (jacobi, svd3, inv3) and tests/nppnp.py.
+// small_dense.h -- dense helpers for per-lane estimators (orb_init.inc: Initializer; orb_pnp.inc: PnPsolver / EPnP; orb_sim3solver.inc:
+// Sim3Solver): 3 x 3 products / inverse / SVD, the one-sided Jacobi in the operation order of null_vector4_dev (tri_math.h) for
+// compile-time shapes in registers (i_jacobi) and for run-time shapes behind a strided view (d_jacobi: 12 x 12 eigenvectors, small least
+// squares), and the two-sided Jacobi for a symmetric 4 x 4 with signed eigenvalues (i_jacobi_sym4: Horn's N).
+// The summation order of every function is fixed here and restated in tests/npinit.py (jacobi, svd3, inv3), tests/nppnp.py and
+// tests/npsim3solver.py (jacobi_sym4).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -70,6 +72,54 @@ __device__ inline void i_jacobi(double (&U)[M][N], double (&V)[N][N]) {
         }
 #pragma unroll
         for (int i = 0; i < N; i++) {
+          const double vp = V[i][p], vq = V[i][q];
+          V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
+        }
+      }
+    if (!rotated) break;
+  }
+}
+
+// Two-sided cyclic Jacobi for a SYMMETRIC 4 x 4: A <- J^T A J pair by pair until A is diagonal, V accumulates the rotations, so that on
+// return A[k][k] is an eigenvalue WITH ITS SIGN and column k of V its eigenvector.  (The one-sided i_jacobi above yields singular values:
+// for a matrix whose eigenvalues come in pairs +-lambda - Horn's N from three points - its column for |lambda| is an arbitrary mix of the
+// two eigenvectors.)  Fixed order: at most 30 sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a pair is rotated when
+// |A[p][q]| > 1e-18 ||A||_F of the input (the comparison is false for a NaN, so a non-finite matrix is left alone); a sweep without a
+// rotation ends the run.
+__device__ inline void i_jacobi_sym4(double (&A)[4][4], double (&V)[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
+  double fro = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) fro += A[i][j] * A[i][j];
+  const double tiny = 1e-18 * sqrt(fro);
+  for (int sweep = 0; sweep < 30; sweep++) {
+    bool rotated = false;
+#pragma unroll
+    for (int p = 0; p < 3; p++)
+#pragma unroll
+      for (int q = p + 1; q < 4; q++) {
+        const double apq = A[p][q];
+        if (!(fabs(apq) > tiny)) continue;
+        rotated = true;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[p][p] = A[p][p] - t * apq; A[q][q] = A[q][q] + t * apq;
+        A[p][q] = 0.0; A[q][p] = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          if (r == p || r == q) continue;
+          const double arp = A[r][p], arq = A[r][q];
+          const double np_ = c * arp - s * arq, nq_ = s * arp + c * arq;
+          A[r][p] = np_; A[p][r] = np_; A[r][q] = nq_; A[q][r] = nq_;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
           const double vp = V[i][p], vq = V[i][q];
           V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
         }

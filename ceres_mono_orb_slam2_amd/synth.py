@@ -598,3 +598,56 @@ def make_reloc(seed, n=200, outlier_frac=0.0, noise=0.0, kind="general", w=1241,
     sigma2 = (np.float32(scale_factor) ** (2 * octave)).astype(np.float32)
     Tcw = np.eye(4); Tcw[:3, :3] = R; Tcw[:3, 3] = t
     return dict(p3d=Xw, p2d=p2d.astype(np.float32), octave=octave, sigma2=sigma2, K4=K4, Tcw=Tcw, R=R, t=t, outlier=outlier)
+
+
+def make_loop_candidate(seed, n=200, outlier_frac=0.0, noise=0.0, scale=1.0, kind="general", w=1241, h=376, n_levels=8, scale_factor=1.2):
+    """One loop candidate for Sim3Solver (orbt_sim3_*): n map points of one scene seen from two keyframes whose maps differ by a known
+    Sim(3), X1c = scale * R12 X2c + t12.  X2c are points in front of a KITTI-like camera 2 (depths 4-40 m), X1c their images under the
+    ground truth; `noise` is the standard deviation of a Gaussian added to both point sets as a fraction of the point's depth,
+    `outlier_frac` of the X1c are replaced by unrelated points in front of camera 1.  Every correspondence has an octave per keyframe
+    and its sigma2 (scale_factor^(2 octave), float32).  kind: "general"; "planar" (every point on one tilted plane); "few" (n is cut
+    to 12: below LoopClosing's min_inliers of 20); "degenerate" (a quarter of the correspondences repeat one point, in both sets: a set
+    that draws two copies has a rotation that is not unique, one that draws three has no scale).
+    Returns dict X1c[n, 3], X2c[n, 3] float64, octave1, octave2[n] int32, sigma2_1, sigma2_2[n] float32, K1, K2 (fx, fy, cx, cy)
+    float32, R, t, scale (the ground truth), outlier[n] bool."""
+    rng = np.random.default_rng(seed)
+    K1 = np.array([718.856, 718.856, 607.1928, 185.2157], np.float32)
+    K2 = np.array([721.5377, 721.5377, 609.5593, 172.854], np.float32)
+    if kind == "few":
+        n = min(int(n), 12)
+    n = int(n)
+    R = quat_to_R(quat_from_rotvec(rng.uniform(-0.15, 0.15, 3)))
+    t = rng.uniform(-0.5, 0.5, 3) * float(scale)
+
+    def cloud(K, m):
+        fx, fy, cx, cy = (float(v) for v in K)
+        u = rng.uniform(60, w - 60, m); v = rng.uniform(40, h - 40, m)
+        rx, ry = (u - cx) / fx, (v - cy) / fy
+        if kind == "planar":
+            z = 12.0 / (1.0 - 0.4 * rx + 0.2 * ry)
+        else:
+            z = rng.uniform(4, 40, m)
+        return np.stack([rx * z, ry * z, z], 1)
+    X2 = cloud(K2, n)
+    if kind == "degenerate":
+        rep = rng.choice(n, n // 4, replace=False)
+        X2[rep] = X2[rep[0]]
+    X1 = float(scale) * (X2 @ R.T) + t
+    if noise > 0:
+        X1 = X1 + rng.normal(0, 1, X1.shape) * (noise * X1[:, 2:3])
+        X2 = X2 + rng.normal(0, 1, X2.shape) * (noise * X2[:, 2:3])
+        if kind == "degenerate":
+            X1[rep] = X1[rep[0]]
+            X2[rep] = X2[rep[0]]
+    outlier = np.zeros(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.choice(n, n_out, replace=False)
+        X1[bad] = cloud(K1, n_out) * float(scale)
+        outlier[bad] = True
+    o1 = rng.integers(0, n_levels, n).astype(np.int32)
+    o2 = rng.integers(0, n_levels, n).astype(np.int32)
+    s1 = (np.float32(scale_factor) ** (2 * o1)).astype(np.float32)
+    s2 = (np.float32(scale_factor) ** (2 * o2)).astype(np.float32)
+    return dict(X1c=np.ascontiguousarray(X1, np.float64), X2c=np.ascontiguousarray(X2, np.float64), octave1=o1, octave2=o2, sigma2_1=s1, sigma2_2=s2,
+                K1=K1, K2=K2, R=R, t=t, scale=float(scale), outlier=outlier)

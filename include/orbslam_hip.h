@@ -561,6 +561,85 @@ int orbt_pnp_iterate_batch_device(int n_candidates, const float* d_p3d, const fl
  * n_candidates, iterations in [1, 4096].                                                                                         */
 int orbt_pnp_iterate_workspace(int n_candidates, int n_total, int iterations, size_t* bytes);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc; called from LoopClosing::ComputeSim3, src/LoopClosing.cc:269-317): Horn's closed-form Sim(3)
+ * from three correspondences inside RANSAC, one `iterate` call per candidate and library call, for a batch of loop candidates.
+ *   X1c[n][3], X2c[n][3] double: the matched map points in each keyframe's camera frame, Rcw * Xw + tcw (X3Dsc1_, X3Dsc2_, :100-104).
+ *   max_err1[n], max_err2[n] float: max_errors_1_ / _2_ - the reference keeps them in std::vector<size_t>, so they hold
+ *     9.210 * level_sigma2[octave] TRUNCATED to an integer (:93-94); the caller passes the truncated values.
+ *   K1[4], K2[4] = {fx, fy, cx, cy} of the two keyframes; fix_scale = is_fixed_scale_ (scale = 1.0f).
+ *   The caller compacts the matches by the constructor's skip rules (:73-85) and scatters the returned mask through
+ *   matched_indices_1_ (:200-203).
+ *   min_inliers: ransac_min_inliers_ (>= 3).
+ *   sets[n_sets][3]: the minimal sets, indices into the n correspondences, distinct inside a set - what :169-182 draws from
+ *     DUtils::Random (process-global, drawn lazily between candidates: the library cannot see that sequence, so the sets are an input).
+ *     One `iterate(n_iterations, ...)` call of the reference runs while `n_iterations_ < ransac_max_iterations_ &&
+ *     n_current_iterations < n_iterations` (:164-165, an AND), so the caller supplies n_sets = min(ransac_max_iterations_ -
+ *     n_iterations_, n_iterations) sets, advances n_iterations_ by result->consumed, and sets is_no_more when the call ends without
+ *     success and n_iterations_ has reached ransac_max_iterations_ (:209).
+ *   best_count / best_mask[n] / best_R[9] (row-major) / best_t[3] / best_scale: n_best_inliers_, is_best_inliers_, best_rotation_,
+ *     best_translation_, best_scale_ - in/out, zero / zeros / anything before the first call.  best_count must equal the number of
+ *     non-zero mask bytes.
+ * Per set (:184-206): ComputeSim3 (double; the scale narrowed to float as scale_12_i_ is), CheckInliers (:365-385) with the reference's
+ * float / double mix; a count >= best_count becomes the state (ties go to the LATER set), and the call returns when such a count is
+ * STRICTLY above min_inliers.  A degenerate triple gives a non-finite hypothesis whose count is 0; like the reference it can enter the
+ * state while best_count is 0.
+ * result (always written except the pose on BAD_INPUT): status, consumed = the sets the reference would have used before returning,
+ * n_inliers, T12 (row-major [s R | t]; identity where the reference returns identity), R, t, scale = the state after the call (what
+ * GetEstimatedRotation / Translation / Scale return).  inliers[n]: the best mask (FOUND) or zeros.  Sets after `consumed` leave no
+ * trace in any output.
+ * The eigenvector of Horn's 4 x 4 N comes from a two-sided Jacobi (the reference: Eigen::EigenSolver); the rotation is unique where
+ * the two largest eigenvalues are apart, and tests/npsim3solver.py restates this implementation's operation order (DESIGN.md section 2,
+ * "Sim3 RANSAC"). */
+#define ORBT_SIM3_FOUND 0          /* set consumed - 1 reached more than min_inliers inliers: T12 = best_T12_, inliers = is_best_inliers_ */
+#define ORBT_SIM3_NOT_FOUND 1      /* every given set used without success: identity, no inliers; the state holds the best so far */
+#define ORBT_SIM3_TOO_FEW 2        /* n < min_inliers (:153-156): identity, is_no_more, consumed = 0, the state untouched */
+#define ORBT_SIM3_BAD_INPUT 3      /* device entry only: offsets, n_sets, min_inliers < 3, a set entry out of range or repeated, a state that does not match */
+#define ORBT_SIM3_MAX_N 32768      /* correspondences per candidate */
+#define ORBT_SIM3_MAX_ITERATIONS 4096
+#define ORBT_SIM3_MAX_CANDIDATES 65535
+typedef struct orbt_sim3_params {
+  int32_t n, min_inliers, max_iterations, reserved;   /* N_, ransac_min_inliers_ and the adjusted ransac_max_iterations_ */
+} orbt_sim3_params;
+typedef struct orbt_sim3_result {
+  int32_t status, consumed, n_inliers;
+  float scale;
+  double T12[16], R[9], t[3];
+} orbt_sim3_result;
+/* Optional per-call trace (host entry only; every member nullable), rows [n_sets]: per consumed set the hypothesis' R [9], t [3],
+ * scale (the float, widened), the inlier count and relgap = (l3 - l2) / l3 of the two largest eigenvalues of N (zeros beyond
+ * `consumed`). */
+typedef struct orbt_sim3_trace {
+  double* R; double* t; double* scale; int32_t* count; double* relgap;
+} orbt_sim3_trace;
+/* SetRansacParameters' arithmetic (:131-142) on the host: epsilon = (float)min_inliers / n, out->max_iterations = max(1,
+ * min(ceil(log(1 - p) / log(1 - epsilon^3)), max_iterations)), 1 when min_inliers == n.  For n < min_inliers the reference's quotient
+ * is not a number (log of a negative); out->max_iterations = 1 then - iterate never uses the value in that case.  ORBHIP_EINVAL for n
+ * outside [0, 32768], probability outside (0, 1), min_inliers < 0, max_iterations < 1. */
+int orbt_sim3_ransac_params(int n, double probability, int min_inliers, int max_iterations, orbt_sim3_params* out);
+/* One candidate, host pointers, synchronous.  ORBHIP_EINVAL before any device work for n outside [0, 32768], n_sets outside
+ * [0, 4096], min_inliers < 3, NULL required pointers and, when n >= min_inliers, set entries outside [0, n), an index repeated inside
+ * a set, or a best_count that is not the number of non-zero best_mask bytes.  It is orbt_sim3_iterate_batch_device with one candidate. */
+int orbt_sim3_iterate(const double* X1c, const double* X2c, const float* max_err1, const float* max_err2, int n, const float* K1, const float* K2,
+                      int fix_scale, int min_inliers, const int32_t* sets, int n_sets, int32_t* best_count, uint8_t* best_mask, double* best_R,
+                      double* best_t, float* best_scale, orbt_sim3_result* result, uint8_t* inliers, const orbt_sim3_trace* trace);
+/* The same for n_candidates candidates with DEVICE pointers, enqueued on `stream`: candidate c's correspondences are rows off[c] ..
+ * off[c+1] of X1c / X2c / max_err1 / max_err2 / best_mask / inliers (CSR, device array of n_candidates + 1), K1[c][4], K2[c][4],
+ * fix_scale[c], min_inliers[c], n_sets[c] <= iterations, sets[c][iterations][3], best_count[c], best_R[c][9], best_t[c][3],
+ * best_scale[c], result[c].  X1c / X2c with `off` are the P3D1c / P3D2c / offsets arguments of ba_optimize_sim3_batch_device, and
+ * best_R / best_t / best_scale / inliers stay on the device per candidate, so a caller goes on to SearchBySim3 and OptimizeSim3
+ * without a round trip.  Counts and NULL pointers are checked on the host; the data is not read there, so a candidate with bad
+ * offsets, n_sets, min_inliers, set entries or state fails alone with ORBT_SIM3_BAD_INPUT (its result gets the status, everything else
+ * of it stays as it was).  `workspace`: device memory of orbt_sim3_iterate_workspace() bytes, not shared with concurrent calls.  No
+ * allocation, no host synchronisation. */
+int orbt_sim3_iterate_batch_device(int n_candidates, const double* d_X1c, const double* d_X2c, const float* d_max_err1, const float* d_max_err2,
+                                   const int32_t* d_off, int n_total, const float* d_K1, const float* d_K2, const int32_t* d_fix_scale,
+                                   const int32_t* d_min_inliers, const int32_t* d_n_sets, int iterations, const int32_t* d_sets, int32_t* d_best_count,
+                                   uint8_t* d_best_mask, double* d_best_R, double* d_best_t, float* d_best_scale, orbt_sim3_result* d_result,
+                                   uint8_t* d_inliers, void* d_workspace, void* stream);
+/* *bytes = the workspace orbt_sim3_iterate_batch_device needs (host arithmetic); n_candidates in [1, 65535], n_total <= 32768
+ * n_candidates, iterations in [1, 4096]. */
+int orbt_sim3_iterate_workspace(int n_candidates, int n_total, int iterations, size_t* bytes);
+
 /* ---- the per-frame Tracking step with the motion model, device-resident (src/Tracking.cc:616-646): Frame construction
  * (ORBextractor::operator(), AssignFeaturesToGrid; zero distortion: the undistorted keypoints are the raw ones, as for the
  * KITTI configurations), ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) (src/ORBmatcher.cc:1161-1271,
