@@ -5,6 +5,9 @@
 #ifndef NB
 #define NB 32
 #endif
+#if defined(ORBHIP_CHOL_PROF) && !defined(ORBHIP_TEST_HOOKS)
+#define ORBHIP_TEST_HOOKS                /* the profiling build carries the test hooks too (tools/factor_ab.py) */
+#endif
 // Phase timing of the factorisation step kernels (tools/chol_phase_prof.py builds a scratch library with -DORBHIP_CHOL_PROF):
 // wave 0 of workgroup 0 of problem 0 stamps s_memrealtime (100 MHz) at the phase boundaries; sums per step index.
 #if defined(ORBHIP_SCHUR_PROF) && !defined(ORBHIP_CHOL_PROF)
@@ -34,19 +37,6 @@ __device__ __forceinline__ double bcast_lane(double v, int lane) {      // lane 
   lo = __builtin_amdgcn_readlane(lo, lane); hi = __builtin_amdgcn_readlane(hi, lane);
   return __hiloint2double(hi, lo);
 }
-// 1/sqrt(x) in fp64: hardware v_rsq_f64 estimate + two Newton steps (~1 ulp); avoids the long fp64 sqrt + divide
-// sequences on the 32-step critical path of the diagonal factorisation.
-__device__ __forceinline__ double rsqrt_f64(double x) {
-  // y += y * (0.5 - (x/2) y^2) with explicit fmas: 3 dependent operations per step (the file is built with
-  // -ffp-contract=off, so the textbook y * (1.5 - 0.5 x y y) would be 5 dependent multiplies / subtracts)
-  const double hx = 0.5 * x;
-  double y = __builtin_amdgcn_rsq(x);
-  double r = fma(-(hx * y), y, 0.5);
-  y = fma(y, r, y);
-  r = fma(-(hx * y), y, 0.5);
-  y = fma(y, r, y);
-  return y;
-}
 // ---- 32x32 diagonal block: inverse of its Cholesky factor, by 1, 2 or 4 cooperating waves (round 6) ------------------------------
 // What the chain needs from a diagonal block D is X = L^-1 (D = L L^T); L itself is never read.  Measured on gfx950
 // (tools/ubench/f64_latency.hip, profiles/r06_f64_latency.txt): a lone wave issues ONE instruction per ~4.5 cycles whatever it is,
@@ -68,8 +58,12 @@ __device__ __forceinline__ double rsqrt_f64(double x) {
 //     publishes the lanes' multipliers (s_M) next to the column entries (s_C) and raises a counter in LDS; a wave first applies the
 //     columns before its own block as they appear, then runs the chain over its block and hands it to the next wave.  Every entry
 //     receives the same fmas in the same order and every pivot the same formula whatever NW is: the 1-, 2- and 4-wave forms give the
-//     same bits (tools/factor_ab.py compares them), so the kernels pick NW by the waves they have idle.
+//     same bits (tests/test_gpu_diag_factor.py compares them on every class of block), so the kernels pick NW by the waves they have idle.
 // A non-positive / non-finite pivot is reported (the block's inverse is then garbage; the caller discards the step).
+// Measured on gfx950 against correctly rounded values (tests/test_gpu_diag_factor.py, 1 034 731 doubles over [2^-1021, 2^1021], every
+// power of two and its neighbours): w of piv_recip IS the correctly rounded reciprocal on all of them (0 ulp), rsqrt_cubic is within 1 ulp
+// (off by one on 13.8 %), both exact on powers of two; X against an mp reference: at most 2.04 x LAPACK's residual and 1.56 x its
+// forward error per class of block (Wishart, condition 1e2 .. 1e13, graded, Jacobi-scaled, padded), asserted <= 4 x.
 #define CHOL_SB() __builtin_amdgcn_sched_barrier(0)
 #define CHOL_PIN(x) asm volatile("" : "+v"(x))
 __device__ __forceinline__ void piv_recip(const double d, double& r0, double& u, double& w) {
@@ -310,6 +304,41 @@ __global__ __launch_bounds__(256) void k_factor_nw(const double* __restrict__ A,
   const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
   for (int i = tid; i < NB * NB; i += 256) X[i] = s_X[i / NB][i % NB];
   if (tid == 0) { ticks[0] = t1 - t0; ticks[1] = (unsigned long long)s_bad; }
+}
+#endif
+#ifdef ORBHIP_TEST_HOOKS
+// test hook (tests/test_gpu_diag_factor.py): nblk DIFFERENT blocks factored back to back by one workgroup, the way k_chol_wg walks the
+// columns of a system - one barrier between staging a block and its factor, one between the factor and the readers of X, the counter
+// base NB * b, the scratch of the previous block (s_C, s_M, s_R) left as it is.  A bad pivot is recorded per block and the walk goes on.
+template <int NW>
+__global__ __launch_bounds__(256) void k_factor_batch_nw(const double* __restrict__ A, double* __restrict__ X, int* __restrict__ bad, int nblk) {
+  __shared__ double s_L[NB][NB + 1], s_X[NB][NB + 1];
+  __shared__ __attribute__((aligned(16))) double s_C[NB * 64], s_M[NB * 64], s_R[2 * NB];
+  __shared__ int s_col;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  if (tid == 0) s_col = 0;
+  __syncthreads();
+  for (int b = 0; b < nblk; b++) {
+    const double* Ab = A + (size_t)b * NB * NB;
+    for (int i = tid; i < NB * NB; i += 256) s_L[i / NB][i % NB] = (i % NB <= i / NB) ? Ab[i] : 0.0;
+    __syncthreads();
+    if (w < NW) {
+      const int fail = diag_factor_invert_nw<NW>(s_L, s_X, s_C, s_M, s_R, &s_col, NB * b, w);
+      if (fail && lane == 0) bad[b] = 1;                         // (zeroed by the host)
+    }
+    __syncthreads();
+    double* Xb = X + (size_t)b * NB * NB;
+    for (int i = tid; i < NB * NB; i += 256) Xb[i] = s_X[i / NB][i % NB];
+  }
+}
+// test hook: the two scalar maps of the factor, element-wise (w of piv_recip, rsqrt_cubic)
+__global__ __launch_bounds__(256) void k_factor_scalar_maps(const double* __restrict__ x, double* __restrict__ w_out, double* __restrict__ y_out, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double r0, u, w;
+  piv_recip(x[i], r0, u, w);
+  w_out[i] = w;
+  y_out[i] = rsqrt_cubic(x[i]);
 }
 #endif
 // G = groups of 16 L21 rows per wave.  Every workgroup repeats the diagonal factor, so a lockstep batch (throughput-bound)

@@ -1685,6 +1685,43 @@ int ba_debug_chol_prof(unsigned long long* out, int reset) {     // [128][10]: t
 }
 #endif
 
+#ifdef ORBHIP_TEST_HOOKS
+// test hooks (tests/test_gpu_diag_factor.py; not in the product build).  Host pointers.  A: nblk blocks of 32 x 32, row-major; X: their
+// inverse factors; bad: a flag per block.  One workgroup walks the blocks back to back (k_factor_batch_nw).
+int ba_debug_factor_batch_nw(const double* A, double* X, int* bad, int nblk, int nw) {
+  if (!A || !X || !bad || nblk < 1 || nblk > (1 << 20) || (nw != 1 && nw != 2 && nw != 4)) return -1;
+  const size_t bytes = (size_t)nblk * NB * NB * sizeof(double);
+  double *dA = nullptr, *dX = nullptr; int* db = nullptr;
+  ORBHIP_CHECK_HIP(hipMalloc(&dA, bytes)); ORBHIP_CHECK_HIP(hipMalloc(&dX, bytes)); ORBHIP_CHECK_HIP(hipMalloc(&db, sizeof(int) * nblk));
+  ORBHIP_CHECK_HIP(hipMemcpy(dA, A, bytes, hipMemcpyHostToDevice));
+  ORBHIP_CHECK_HIP(hipMemset(dX, 0xff, bytes));
+  ORBHIP_CHECK_HIP(hipMemset(db, 0, sizeof(int) * nblk));
+  if (nw == 1) hipLaunchKernelGGL(k_factor_batch_nw<1>, dim3(1), dim3(256), 0, 0, dA, dX, db, nblk);
+  else if (nw == 2) hipLaunchKernelGGL(k_factor_batch_nw<2>, dim3(1), dim3(256), 0, 0, dA, dX, db, nblk);
+  else hipLaunchKernelGGL(k_factor_batch_nw<4>, dim3(1), dim3(256), 0, 0, dA, dX, db, nblk);
+  ORBHIP_CHECK_HIP(hipGetLastError());
+  ORBHIP_CHECK_HIP(hipDeviceSynchronize());
+  ORBHIP_CHECK_HIP(hipMemcpy(X, dX, bytes, hipMemcpyDeviceToHost));
+  ORBHIP_CHECK_HIP(hipMemcpy(bad, db, sizeof(int) * nblk, hipMemcpyDeviceToHost));
+  (void)hipFree(dA); (void)hipFree(dX); (void)hipFree(db);
+  return 0;
+}
+int ba_debug_factor_scalar_maps(const double* x, double* w, double* y, long long n) {      // w = piv_recip's w, y = rsqrt_cubic, element-wise
+  if (!x || !w || !y || n < 1 || n > (1ll << 28)) return -1;
+  const size_t bytes = (size_t)n * sizeof(double);
+  double *dx = nullptr, *dw = nullptr, *dy = nullptr;
+  ORBHIP_CHECK_HIP(hipMalloc(&dx, bytes)); ORBHIP_CHECK_HIP(hipMalloc(&dw, bytes)); ORBHIP_CHECK_HIP(hipMalloc(&dy, bytes));
+  ORBHIP_CHECK_HIP(hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_factor_scalar_maps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, dw, dy, n);
+  ORBHIP_CHECK_HIP(hipGetLastError());
+  ORBHIP_CHECK_HIP(hipDeviceSynchronize());
+  ORBHIP_CHECK_HIP(hipMemcpy(w, dw, bytes, hipMemcpyDeviceToHost));
+  ORBHIP_CHECK_HIP(hipMemcpy(y, dy, bytes, hipMemcpyDeviceToHost));
+  (void)hipFree(dx); (void)hipFree(dw); (void)hipFree(dy);
+  return 0;
+}
+#endif
+
 #if defined(ORBHIP_SCHUR_PROF) && !defined(ORBHIP_CHOL_PROF)
 int ba_debug_chol_prof(unsigned long long* out, int reset) {     // k_ba_schur phase stamps of problem 0: [row a][column], [9] = launches
   ORBHIP_CHECK_HIP(hipDeviceSynchronize());

@@ -1,35 +1,31 @@
 """The 32 x 32 diagonal factor + inverse of the Cholesky chain (diag_factor_invert_nw, csrc/ba_cholesky.inc) with 1, 2 and 4 cooperating
-waves: builds ba_solver.hip with -DORBHIP_CHOL_PROF into a scratch library, runs the three forms on random SPD blocks, compares the
-inverses bit for bit (the forms must agree), against numpy, and prints the time per factor (s_memrealtime, 100 MHz)."""
-import ctypes as C, os, subprocess, sys
+waves: builds ba_solver.hip with -DORBHIP_CHOL_PROF (which implies the test hooks, -DORBHIP_TEST_HOOKS) into a scratch library - the
+build line and the blocks are those of the tests (tests/npfactor.py) -, runs the three forms on SPD blocks, compares the inverses bit
+for bit (the forms must agree), against numpy, and prints the time per factor (s_memrealtime, 100 MHz).  The accuracy of the factor
+is ASSERTED by tests/test_gpu_diag_factor.py against an mp reference; this tool is for the timing."""
+import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
+import npfactor
 out = os.path.join(ROOT, "gpurun_out", "cholprof"); os.makedirs(out, exist_ok=True)
 so = os.path.join(out, "liborbslam_hip_factor.so")
-csrc = os.path.join(ROOT, "ceres_mono_orb_slam2_amd", "csrc")
-srcs = [os.path.join(csrc, f) for f in ("ba_solver.hip", "capi_common.hip")]
 so_st = os.path.join(out, "liborbslam_hip_factor_stamps.so")                       # the same with per-wave time stamps inside the factor (they cost ~0.3 us)
 if not os.path.exists(so) or os.environ.get("REBUILD"):
     for target, extra in ((so, []), (so_st, ["-DORBHIP_DF_STAMP"])):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-                               "-DORBHIP_CHOL_PROF"] + extra + ["-I", os.path.join(ROOT, "include"), "-shared", "-o", target] + srcs)
+        npfactor.build_hook_library(target, ["-DORBHIP_CHOL_PROF"] + extra)
 if "--build-only" in sys.argv:
     sys.exit(0)
 L = C.CDLL(so)
 L.ba_debug_factor_nw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
 L.ba_debug_df_stamps.argtypes = [C.c_void_p, C.c_int]
-rng = np.random.default_rng(5)
 bad = 0
+# twelve Wishart blocks, three badly scaled ones (what Jacobi scaling leaves is milder), and at index 11 a non-positive pivot (at
+# position 20): every form must report it
+blocks = npfactor.blocks("W")[:11] + [npfactor.blocks("S")[20]] + npfactor.blocks("W")[11:12] + npfactor.blocks("G")[:3]
 best = {1: 1e9, 2: 1e9, 4: 1e9}
 worst = 0.0
-for trial in range(16):
-    M = rng.standard_normal((32, 48))
-    A = M @ M.T + (0.5 if trial % 3 else 1e-6) * np.eye(32)
-    if trial >= 12:                                                             # badly scaled rows / columns (what Jacobi scaling leaves is milder)
-        sc = 10.0 ** rng.uniform(-6, 6, 32); A = A * sc[:, None] * sc[None, :]
-    if trial == 11: A[20, 20] = -1.0                                            # a non-positive pivot: every form must report it
-    A = np.ascontiguousarray(A)
+for trial, A in enumerate(blocks):
     n = 200
     X = {}; flag = {}; us = {}
     for nw in (1, 2, 4):
