@@ -19,6 +19,10 @@ SYMBOLS = [
     "orbm_descriptor_distance", "orbm_hamming_best2_device", "orbm_hamming_best2", "orbm_match_frames_batch_device",
     "orbm_search_for_initialization", "orbm_search_by_projection", "orbm_search_by_sim3", "orbm_search_by_bow", "orbm_search_for_triangulation",
     "orbv_create", "orbv_destroy", "orbv_load_text", "orbv_parse_text", "orbv_free_parsed", "orbv_transform", "orbv_descend_device", "orbv_score_l1",
+    "orbv_db_create", "orbv_db_destroy", "orbv_db_clear", "orbv_db_add", "orbv_db_erase", "orbv_db_size", "orbv_db_set_best_covisibles", "orbv_db_get_state",
+    "orbv_db_min_score", "orbv_db_detect_loop_candidates", "orbv_db_detect_relocalization_candidates", "orbv_db_detect_loop_candidates_begin",
+    "orbv_db_detect_relocalization_candidates_begin", "orbv_db_detect_candidates_finish", "orbv_db_pending_fields", "orbv_db_detect_loop_candidates_batch_device",
+    "orbv_db_detect_relocalization_candidates_batch_device", "orbv_db_detect_workspace",
     "orbm_undistort_keypoints", "orbm_assign_features_to_grid", "orbm_features_in_area", "orbm_is_in_frustum", "orbm_is_in_frustum_gates",
     "orbm_triangulate_matches", "orbt_track_with_motion_model", "orbt_track_local_map", "orbt_track_reference_keyframe", "orbt_last_call_ms",
     "ba_pose_optimization", "ba_pose_optimization_batch_device", "ba_solve", "ba_check_outlier",
@@ -81,6 +85,16 @@ class Sim3Result(C.Structure):                # orbt_sim3_result
 
 class Sim3Trace(C.Structure):                 # orbt_sim3_trace
     _fields_ = [("R", C.c_void_p), ("t", C.c_void_p), ("scale", C.c_void_p), ("count", C.c_void_p), ("relgap", C.c_void_p)]
+
+
+class DbQueryInfo(C.Structure):              # orbv_db_query_info
+    _fields_ = [("max_common", C.c_int32), ("n_sharing", C.c_int32), ("n_scored", C.c_int32), ("n_kept", C.c_int32), ("n_cand", C.c_int32),
+                ("status", C.c_int32), ("best_acc", C.c_float), ("min_common", C.c_int32)]
+
+
+class DbTrace(C.Structure):                  # orbv_db_trace
+    _fields_ = [("info", C.POINTER(DbQueryInfo)), ("kept_slot", C.c_void_p), ("kept_score", C.c_void_p), ("kept_acc", C.c_void_p),
+                ("kept_best", C.c_void_p), ("kept_cap", C.c_int32), ("reserved", C.c_int32)]
 
 
 class BaOptions(C.Structure):
@@ -206,6 +220,25 @@ def load():
     L.orbt_sim3_iterate_workspace.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
     L.ba_solve_batch.argtypes = [vp, i32, C.POINTER(BaOptions), vp]
     L.ba_local_bundle_adjustment_batch.argtypes = [vp, i32, vp, i32, C.POINTER(i32), vp, vp]
+    i64 = C.c_int64
+    L.orbv_db_create.argtypes = [i32, i32, C.POINTER(vp)]
+    L.orbv_db_destroy.argtypes = [vp]
+    L.orbv_db_clear.argtypes = [vp]
+    L.orbv_db_add.argtypes = [vp, i32, vp, vp, i32]
+    L.orbv_db_erase.argtypes = [vp, i32]
+    L.orbv_db_size.argtypes = [vp]
+    L.orbv_db_set_best_covisibles.argtypes = [vp, i32, vp, i32]
+    L.orbv_db_get_state.argtypes = [vp, vp, i32, vp, vp]
+    L.orbv_db_min_score.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(f32)]
+    L.orbv_db_detect_loop_candidates.argtypes = [vp, vp, vp, i32, vp, i32, f32, i64, vp, i32, C.POINTER(i32), C.POINTER(DbTrace)]
+    L.orbv_db_detect_relocalization_candidates.argtypes = [vp, vp, vp, i32, i64, vp, i32, C.POINTER(i32), C.POINTER(DbTrace)]
+    L.orbv_db_detect_loop_candidates_begin.argtypes = [vp, vp, vp, i32, vp, i32, f32, i64, vp, i32, C.POINTER(i32)]
+    L.orbv_db_detect_relocalization_candidates_begin.argtypes = [vp, vp, vp, i32, i64, vp, i32, C.POINTER(i32)]
+    L.orbv_db_detect_candidates_finish.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(DbTrace)]
+    L.orbv_db_detect_loop_candidates_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, sz, vp]
+    L.orbv_db_detect_relocalization_candidates_batch_device.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, i32, vp, sz, vp]
+    L.orbv_db_pending_fields.argtypes = [vp, C.POINTER(DbQueryInfo), vp, vp, i32]
+    L.orbv_db_detect_workspace.argtypes = [vp, i32, C.POINTER(sz)]
     _lib = L
     return L
 

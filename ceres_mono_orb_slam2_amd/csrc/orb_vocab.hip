@@ -296,3 +296,5 @@ double orbv_score_l1(const uint32_t* w1, const double* v1, int n1, const uint32_
 }
 
 }  // extern "C"
+
+#include "orb_kfdb.inc"   // KeyFrameDatabase: orbv_db_*

@@ -651,3 +651,51 @@ def make_loop_candidate(seed, n=200, outlier_frac=0.0, noise=0.0, scale=1.0, kin
     s2 = (np.float32(scale_factor) ** (2 * o2)).astype(np.float32)
     return dict(X1c=np.ascontiguousarray(X1, np.float64), X2c=np.ascontiguousarray(X2, np.float64), octave1=o1, octave2=o2, sigma2_1=s1, sigma2_2=s2,
                 K1=K1, K2=K2, R=R, t=t, scale=float(scale), outlier=outlier)
+
+
+def make_place_sequence(seed, n_kf=300, n_words=10000, n_feat=1000, step=25, flip=0.25, revisit=60):
+    """Keyframes along a path, for KeyFrameDatabase (loop detection / relocalisation).  Landmark l has a fixed word; keyframe i sees the
+    sliding window of landmarks [i * step, i * step + n_feat), a share `flip` of its words redrawn per view; its BowVector is tf-idf
+    weighted (a fixed idf per word, summed per occurrence) and L1-normalised.  The landmarks seen by the last `revisit` keyframes are NEW
+    landmarks that carry the words of the start of the path (landmark l0 + k has the word of landmark k, l0 = first landmark of keyframe
+    n_kf - revisit): keyframe i >= n_kf - revisit looks like place i - (n_kf - revisit) but shares no landmark with it.  Covisibility
+    (shared landmarks, max(0, n_feat - |i - j| * step)) therefore follows the sequence index alone.
+    Returns dict(bows = [(words uint32 ascending, values float64)], true_place int[n_kf] (-1 outside the revisit), n_kf, n_words, step, n_feat)
+    with connected(i, upto) / best_covisibles(i, upto) through the functions place_connected / place_best_covisibles below."""
+    rng = np.random.default_rng(seed)
+    n_land = (n_kf - 1) * step + n_feat
+    word_of = rng.integers(0, n_words, n_land)
+    t0 = n_kf - revisit
+    if revisit > 0:
+        l0 = t0 * step
+        word_of[l0:] = word_of[:n_land - l0]
+    idf = np.log(1.0e5 / rng.integers(1, 2000, n_words).astype(np.float64))
+    bows = []
+    for i in range(n_kf):
+        w = word_of[i * step:i * step + n_feat].copy()
+        redraw = rng.random(n_feat) < flip
+        w[redraw] = rng.integers(0, n_words, int(redraw.sum()))
+        words, counts = np.unique(w, return_counts=True)
+        v = counts.astype(np.float64) * idf[words]
+        norm = 0.0
+        for x in np.abs(v).tolist():                      # BowVector::normalize(L1): the sum in ascending word order
+            norm += x
+        bows.append((words.astype(np.uint32), v / norm))
+    true_place = np.full(n_kf, -1, np.int64)
+    if revisit > 0:
+        true_place[t0:] = np.arange(n_kf - t0)
+    return dict(bows=bows, true_place=true_place, n_kf=n_kf, n_words=n_words, n_feat=n_feat, step=step)
+
+
+def place_connected(seq, i, upto=None, min_weight=15):
+    """The keyframes j <= upto (default: all) that share at least min_weight landmarks with keyframe i (KeyFrame::GetConnectedKeyFrames with
+    the reference's threshold of 15), best first: by (weight descending, |i - j|, j)."""
+    hi = seq["n_kf"] - 1 if upto is None else upto
+    reach = (seq["n_feat"] - min_weight) // seq["step"]
+    js = [j for j in range(max(0, i - reach), min(hi, i + reach) + 1) if j != i]
+    return sorted(js, key=lambda j: (abs(i - j), j))      # the weight falls with |i - j|
+
+
+def place_best_covisibles(seq, i, upto=None, n=10):
+    """KeyFrame::GetBestCovisibilityKeyFrames(n) of keyframe i in the graph of the keyframes 0 .. upto."""
+    return place_connected(seq, i, upto)[:n]

@@ -14,6 +14,7 @@ class ORBVocabulary:
         nd = np.ascontiguousarray(node_desc, np.uint8).reshape(-1, 32); co = np.ascontiguousarray(child_off, np.uint32)
         ch = np.ascontiguousarray(children, np.uint32); wi = np.ascontiguousarray(word_id, np.int32); wt = np.ascontiguousarray(weight, np.float64)
         self.depth = int(L)
+        self._n_words = int(wi.max()) + 1 if len(wi) else 0          # words are numbered 0 .. n_words - 1 (inner nodes carry -1)
         self._h = C.c_void_p()
         _lib.check(self._L.orbv_create(_lib.ptr(nd), _lib.ptr(co), _lib.ptr(ch), _lib.ptr(wi), _lib.ptr(wt), len(wi), int(L), int(device),
                                        C.byref(self._h)), "orbv_create")
@@ -27,7 +28,17 @@ class ORBVocabulary:
         _lib.check(self._L.orbv_load_text(str(path).encode(), int(device), C.byref(self._h)), "orbv_load_text")
         with open(path, "rb") as f:                     # header line "k L scoring weighting" (orbv_load_text validated it)
             self.depth = int(f.readline().split()[1])
+        self._n_words = None; self._path = str(path)
         return self
+
+    @property
+    def n_words(self):
+        """ORBVocabulary::size(): the number of words (what KeyFrameDatabase sizes its inverted file with)."""
+        if self._n_words is None:                       # text file: one line per node, "parent is_leaf ..."; the leaves are the words
+            with open(self._path, "rb") as f:
+                f.readline()
+                self._n_words = sum(1 for line in f if line.split()[1:2] == [b"1"])
+        return self._n_words
 
     def __del__(self):
         if getattr(self, "_h", None):

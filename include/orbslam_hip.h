@@ -264,6 +264,94 @@ int orbv_descend_device(orbv_ctx* ctx, const uint8_t* d_desc, int n, int levelsu
 /* L1Scoring::score (lib/DBoW2/DBoW2/ScoringObject.cpp:23-68) between two BowVectors in the layout above (host arithmetic). */
 double orbv_score_l1(const uint32_t* w1, const double* v1, int n1, const uint32_t* w2, const double* v2, int n2);
 
+/* ---- KeyFrameDatabase (src/KeyFrameDatabase.cc, all of it; DESIGN.md section 2 "KeyFrameDatabase"): the loop and relocalisation
+ * candidates, computed by scanning every stored BowVector against the query on the device.  A keyframe is a `slot` (a non-negative
+ * index the caller chooses; the tables grow to the largest one).  BowVectors are ascending word ids below n_words with double values,
+ * as orbv_transform returns them.  Lists come back in the reference's order: first touch while the query's words are walked in
+ * ascending id and each word's list in `add` order, i.e. by (smallest word shared with the query, `add` sequence number).
+ * Scores are float(L1Scoring::score), bit for bit.
+ *
+ * A database is used by one host thread at a time.  create / clear / size keep host state only and work without a device; every other
+ * entry returns ORBHIP_ENODEV without one, after its arguments have been checked (ORBHIP_EINVAL first).  add / erase /
+ * set_best_covisibles / clear complete before they return; they must not be called while a _batch_device call is still in flight.
+ *
+ * Query stamps: the reference stamps keyframes with the query's id and compares against fields that start at 0.  Every query takes a
+ * query_id; per kind (loop, relocalisation) an id that is not positive or not greater than the last one used is ORBHIP_EINVAL.  An
+ * id counts as used once a call's arguments have passed, whatever happens later in that call.  A batch uses first_query_id ..
+ * first_query_id + n_queries - 1.  clear forgets the ids and all per-slot state.                                                  */
+typedef struct orbv_db orbv_db;
+typedef struct orbv_db_query_info {       /* per query (the batched entries write one per query to device memory) */
+  int32_t max_common;                     /* maxCommonWords over the sharing list */
+  int32_t n_sharing;                      /* length of keyframes_sharing_words */
+  int32_t n_scored;                       /* keyframes above minCommonWords (nscores) */
+  int32_t n_kept;                         /* length of score_and_matches (loop: score >= minScore) */
+  int32_t n_cand;                         /* candidates returned (or wanted, when status is ORBHIP_ECAP) */
+  int32_t status;                         /* 0, or ORBHIP_ECAP: n_cand > cap, no candidate of this query was written */
+  float best_acc;                         /* bestAccScore (0 when nothing was kept) */
+  int32_t min_common;                     /* int(max_common * 0.8f) */
+} orbv_db_query_info;
+/* Optional trace of a host query: info and the kept list in order - slot, score, accumulated score, best keyframe of its neighbourhood.
+ * Every pointer nullable; ORBHIP_ECAP (nothing written) when n_kept > kept_cap.                                                    */
+typedef struct orbv_db_trace {
+  orbv_db_query_info* info;
+  int32_t* kept_slot; float* kept_score; float* kept_acc; int32_t* kept_best;
+  int32_t kept_cap, reserved;
+} orbv_db_trace;
+int orbv_db_create(int n_words, int device, orbv_db** out);
+int orbv_db_destroy(orbv_db* db);
+int orbv_db_clear(orbv_db* db);
+/* ORBHIP_EINVAL for a slot that is in the database, words that do not ascend, a word id not below n_words.  A slot erased and added
+ * again goes to the back of every word's list (it gets a new sequence number); its reloc_query / reloc_score stay, as the fields of the
+ * reference's KeyFrame do.  Erasing a slot that is not in the database does nothing.  orbv_db_size returns the number of keyframes in
+ * the database.  Erased BowVectors are compacted away once they are more than half of the stored ones.                             */
+int orbv_db_add(orbv_db* db, int slot, const uint32_t* words, const double* values, int n);
+int orbv_db_erase(orbv_db* db, int slot);
+int orbv_db_size(const orbv_db* db);
+/* GetBestCovisibilityKeyFrames(10) of a slot, resident: n <= 10 slots in that order.  A neighbour that is not in the database when a
+ * query runs contributes nothing.                                                                                                 */
+int orbv_db_set_best_covisibles(orbv_db* db, int slot, const int32_t* neigh, int n);
+/* reloc_query_ / reloc_score_ of the listed slots (the reference never initialises reloc_score_; here both start at 0). */
+int orbv_db_get_state(orbv_db* db, const int32_t* slots, int n, int64_t* reloc_query, float* reloc_score);
+/* LoopClosing::DetectLoop's minScore (src/LoopClosing.cc:127-139): the lowest float score of the query against the listed slots (the
+ * covisible keyframes that are not bad), starting from 1.0f.  ORBHIP_EINVAL for a slot that is not in the database.              */
+int orbv_db_min_score(orbv_db* db, const uint32_t* words, const double* values, int n, const int32_t* slots, int n_slots, float* min_score);
+/* DetectLoopCandidates(keyframe, minScore) / DetectRelocalizationCandidates(frame): host pointers, one call, one synchronisation.
+ * connected = the slots of keyframe->GetConnectedKeyFrames().  Neighbours come from the resident table.  ORBHIP_ECAP, with nothing
+ * written, when the candidates exceed cap.  A query BowVector of more than 4096 words is searched in global memory instead of LDS
+ * (slower, same result).                                                                                                         */
+int orbv_db_detect_loop_candidates(orbv_db* db, const uint32_t* words, const double* values, int n, const int32_t* connected, int n_connected, float min_score,
+                                   int64_t query_id, int32_t* cand, int cap, int32_t* n_cand, const orbv_db_trace* trace);
+int orbv_db_detect_relocalization_candidates(orbv_db* db, const uint32_t* words, const double* values, int n, int64_t query_id, int32_t* cand, int cap,
+                                             int32_t* n_cand, const orbv_db_trace* trace);
+/* The same in two halves, for callers whose covisibility graph lives in host objects: _begin returns the kept list (score_and_matches)
+ * in order; the caller supplies GetBestCovisibilityKeyFrames(10) of exactly those keyframes as rows[n_kept][10] / row_n[n_kept] (slots);
+ * _finish accumulates over them and returns the candidates.  The same kernels as the one-call forms.  add / erase / clear /
+ * set_best_covisibles or another query between the halves cancel the pending query (_finish: ORBHIP_EINVAL).                       */
+int orbv_db_detect_loop_candidates_begin(orbv_db* db, const uint32_t* words, const double* values, int n, const int32_t* connected, int n_connected,
+                                         float min_score, int64_t query_id, int32_t* kept, int kept_cap, int32_t* n_kept);
+int orbv_db_detect_relocalization_candidates_begin(orbv_db* db, const uint32_t* words, const double* values, int n, int64_t query_id, int32_t* kept,
+                                                   int kept_cap, int32_t* n_kept);
+int orbv_db_detect_candidates_finish(orbv_db* db, const int32_t* rows, const int32_t* row_n, int32_t* cand, int cap, int32_t* n_cand, const orbv_db_trace* trace);
+/* Between _begin and _finish: the fields the reference writes to the keyframes it touches, per slot 0 .. S-1 (S = highest slot ever used + 1;
+ * ORBHIP_ECAP when cap < S): n_common[s] = n_loop_words_ / n_reloc_words_ (0: the query did not stamp the slot - it shares no word, is not in
+ * the database, or is connected to the loop query), score[s] = loop_score_ / reloc_score_ where n_common[s] > info->min_common (not meaningful
+ * elsewhere).  *info: the counters known so far.                                                                                    */
+int orbv_db_pending_fields(orbv_db* db, orbv_db_query_info* info, int32_t* n_common, float* score, int cap);
+/* n_queries queries with DEVICE pointers, enqueued on `stream` (no allocation, no host synchronisation): query q's BowVector is
+ * entries q_off[q] .. q_off[q+1] of q_words / q_values, its connected slots conn_off[q] .. conn_off[q+1] of conn, its minScore
+ * min_score[q]; out info[q] and cand[q][cap] (n_cand of them).  The scan and the scores are batched over the queries; ordering,
+ * accumulation and the relocalisation state run per query in stream order, so the result and the state left behind are those of
+ * n_queries single calls in the same order, bit for bit.  The BowVectors are not read on the host: they must ascend.
+ * `workspace`: device memory of orbv_db_detect_workspace() bytes (which grows with the database: ask again after add), 256-byte
+ * aligned, not shared with concurrent calls.                                                                                      */
+int orbv_db_detect_loop_candidates_batch_device(orbv_db* db, int n_queries, const int32_t* d_q_off, const uint32_t* d_q_words, const double* d_q_values,
+                                                const int32_t* d_conn_off, const int32_t* d_conn, const float* d_min_score, int64_t first_query_id,
+                                                orbv_db_query_info* d_info, int32_t* d_cand, int cap, void* d_workspace, size_t workspace_bytes, void* stream);
+int orbv_db_detect_relocalization_candidates_batch_device(orbv_db* db, int n_queries, const int32_t* d_q_off, const uint32_t* d_q_words,
+                                                          const double* d_q_values, int64_t first_query_id, orbv_db_query_info* d_info, int32_t* d_cand,
+                                                          int cap, void* d_workspace, size_t workspace_bytes, void* stream);
+int orbv_db_detect_workspace(const orbv_db* db, int n_queries, size_t* bytes);
+
 /* ---- the steps either side of extract -> match: undistortion, the 64 x 48 frame grid, window candidates,
  * frustum test.  kps4 = n x {x, y, octave, angle} floats of the UNDISTORTED keypoints; bounds = {min_x, max_x, min_y, max_y}
  * (Frame::ComputeImageBounds, src/Frame.cc:357-385).  Host pointers; the arithmetic runs on the device.                  */
