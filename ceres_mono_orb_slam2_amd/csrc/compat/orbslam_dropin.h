@@ -1401,7 +1401,100 @@ struct FrameOpsT {
     }
   }
 
+  // LocalMapping::KeyFrameCulling (src/LocalMapping.cc:576-637, monocular) in ONE library call (orbl_keyframe_culling), the body of
+  // that member function: `FrameOpsHip::KeyFrameCulling(current_keyframe_);`.  The candidates are GetVectorCovisibleKeyFrames() in
+  // order; the map is flattened through the reference's own accessors, so under its lock scopes (GetMapPointMatches(), isBad(),
+  // Observations(), GetObservations() take mutex_features_ / mutex_connections_ themselves; do_not_erase_ is read under
+  // mutex_connections_ as KeyFrame::SetBadFlag reads it, src/KeyFrame.cc:462-468 - protected there: the friend declaration of
+  // INTEGRATION.md section 4).  The library call reproduces the loop's order dependence (a culled keyframe's SetBadFlag() erases
+  // observations and may turn points bad before the next candidate counts); then SetBadFlag() runs on the flagged keyframes in list
+  // order, which applies exactly the state the call assumed.  Returns the number of keyframes flagged.
+  // PRECONDITION, checked while flattening: the map is consistent - a candidate holds point p in slot i iff p's observations contain
+  // (candidate, i), and every observation's index is a keypoint of its keyframe.  On a violation nothing is called and nothing is
+  // changed: returns -1 (the caller falls back to its own loop).
+  // (A member template over the keyframe type, KF = Types::KeyFrame at the call site: it is instantiated only where it is called, so a
+  // data model without SetBadFlag() / do_not_erase_ can still instantiate the rest of FrameOpsT explicitly.)
+  template <class KF> static int KeyFrameCulling(KF* current_keyframe, int th_obs = 3, double ratio = 0.9) {
+    const std::vector<KF*> cands = current_keyframe->GetVectorCovisibleKeyFrames();          // (:581-582)
+    const int ncand = (int)cands.size();
+    if (ncand == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    auto kf_index = [&](KF* kf) { return kf_at.emplace(kf, (int)kf_at.size()).first->second; };
+    std::unordered_map<MapPoint*, int> pt_at;
+    std::vector<MapPoint*> pts;
+    std::vector<std::vector<MapPoint*> > matches(ncand);
+    std::vector<int32_t> cand_kf(ncand), slot_off(ncand + 1, 0), slot_pt, slot_level, slot_index;
+    std::vector<uint8_t> cand_flags(ncand, 0);
+    for (int c = 0; c < ncand; c++) {
+      KF* kf = cands[c];
+      if (kf_at.count(kf)) return -1;                               // (a keyframe listed twice)
+      cand_kf[c] = kf_index(kf);
+      bool keep;
+      { std::unique_lock<std::mutex> lock = lock_connections(kf, 0); keep = kf->do_not_erase_; }
+      cand_flags[c] = (uint8_t)((kf->id_ == 0 ? 1 : 0) | (keep ? 2 : 0));
+      matches[c] = kf->GetMapPointMatches();                        // (:589)
+      for (size_t i = 0; i < matches[c].size(); i++) {
+        MapPoint* mp = matches[c][i];
+        if (!mp) continue;
+        if (i >= kf->undistort_keypoints_.size()) return -1;
+        auto it = pt_at.find(mp);
+        if (it == pt_at.end()) { it = pt_at.emplace(mp, (int)pts.size()).first; pts.push_back(mp); }
+        slot_pt.push_back(it->second); slot_level.push_back(kf->undistort_keypoints_[i].octave); slot_index.push_back((int32_t)i);
+      }
+      slot_off[c + 1] = (int32_t)slot_pt.size();
+    }
+    const int npts = (int)pts.size();
+    std::vector<int32_t> obs_off(npts + 1, 0), obs_kf, obs_level, pt_nobs(npts, 0);
+    std::vector<uint8_t> pt_bad(npts, 0);
+    std::vector<std::map<int, size_t> > own(npts);                  // per point: candidate -> the index its observation names
+    for (int p = 0; p < npts; p++) {
+      MapPoint* mp = pts[p];
+      pt_bad[p] = mp->isBad() ? 1 : 0;                              // (:598)
+      if (!pt_bad[p]) {
+        pt_nobs[p] = mp->Observations();                            // (:606)
+        const auto observations = mp->GetObservations();            // (:608-609)
+        for (const auto& o : observations) {
+          if (o.second >= o.first->undistort_keypoints_.size()) return -1;
+          const int k = kf_index(o.first);
+          if (k < ncand) own[p][k] = o.second;                      // (candidates were numbered first: index = list position)
+          obs_kf.push_back(k); obs_level.push_back(o.first->undistort_keypoints_[o.second].octave);   // (:617-618)
+        }
+      }
+      obs_off[p + 1] = (int32_t)obs_kf.size();
+    }
+    // consistency, both directions: every slot of a good point is the point's observation by that candidate, and every observation by a
+    // candidate is one of its slots
+    std::vector<size_t> n_slots_of(npts, 0);
+    for (int c = 0; c < ncand; c++)
+      for (int s = slot_off[c]; s < slot_off[c + 1]; s++) {
+        const int p = slot_pt[s];
+        if (pt_bad[p]) continue;
+        auto it = own[p].find(c);
+        if (it == own[p].end() || it->second != (size_t)slot_index[s]) return -1;
+        n_slots_of[p]++;
+      }
+    for (int p = 0; p < npts; p++) {
+      if (pt_bad[p]) continue;
+      if (n_slots_of[p] != own[p].size()) return -1;
+      for (const auto& o : own[p]) if (o.second >= matches[o.first].size() || matches[o.first][o.second] != pts[p]) return -1;
+    }
+    std::vector<uint8_t> culled(ncand, 0);
+    std::vector<int32_t> n_redundant(ncand, 0), n_map_points(ncand, 0);
+    dropin::check(orbl_keyframe_culling(ncand, cand_kf.data(), cand_flags.data(), slot_off.data(), slot_pt.data(), slot_level.data(), (int)kf_at.size(), npts,
+                                        obs_off.data(), obs_kf.data(), obs_level.data(), pt_bad.data(), pt_nobs.data(), th_obs, ratio, culled.data(),
+                                        n_redundant.data(), n_map_points.data(), nullptr, nullptr, nullptr), "orbl_keyframe_culling");
+    int n = 0;
+    for (int c = 0; c < ncand; c++)
+      if (culled[c]) { cands[c]->SetBadFlag(); n++; }                // (:633-635)
+    return n;
+  }
+
  private:
+  // the reference's KeyFrame::mutex_connections_ when the type has it
+  template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {
+    return std::unique_lock<std::mutex>(p->mutex_connections_);
+  }
+  template <class P> static std::unique_lock<std::mutex> lock_connections(P*, long) { return std::unique_lock<std::mutex>(); }
   // the reference's MapPoint::mutex_features_ / mutex_pose_ when the type has them (the mock data model of tests/cpp has none)
   template <class P> static auto lock_features(P* p, int) -> decltype((void)p->mutex_features_, std::unique_lock<std::mutex>()) {
     return std::unique_lock<std::mutex>(p->mutex_features_);

@@ -388,3 +388,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 
 // MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth for a batch of points (orbl_update_map_points*)
 #include "orb_mappoint.inc"
+// LocalMapping::KeyFrameCulling for the whole candidate list, order-dependent state included (orbl_keyframe_culling*)
+#include "orb_kfculling.inc"

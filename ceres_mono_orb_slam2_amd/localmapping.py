@@ -1,5 +1,5 @@
 """Host mirror of the LocalMapping thread's device-resident steps (include/orbslam_hip.h: orbl_*; reference
-src/LocalMapping.cc:196-396 CreateNewMapPoints, :398-505 SearchInNeighbors).  Thin ctypes layer: arrays in, arrays out."""
+src/LocalMapping.cc:196-396 CreateNewMapPoints, :398-505 SearchInNeighbors, :576-637 KeyFrameCulling).  Thin ctypes layer: arrays in, arrays out."""
 import ctypes as C
 
 import numpy as np
@@ -171,3 +171,74 @@ def update_map_points_device(obs_off, obs_desc, obs_kf_good, X, ref_kf, ref_leve
                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_update_map_points_device")
     out["_workspace"] = ws                                       # (kept alive until the caller synchronises)
     return out
+
+
+class CullingResult:
+    """What orbl_keyframe_culling reports: culled[ncand] uint8, n_redundant[ncand] / n_map_points[ncand] int32 as seen at each
+    candidate's turn, and the final state pt_bad[npts] uint8, pt_nobs[npts] int32, obs_erased[nobs] uint8 (None where not asked for);
+    status: the device form's d_status tensor (None in the host form)."""
+    __slots__ = ("culled", "n_redundant", "n_map_points", "pt_bad", "pt_nobs", "obs_erased", "status", "_workspace")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def keyframe_culling(cand_kf, cand_flags, slot_off, slot_pt, slot_level, nkf, obs_off, obs_kf, obs_level, pt_bad=None, pt_nobs=None,
+                     th_obs=3, ratio=0.9, final_state=True, out=None):
+    """LocalMapping::KeyFrameCulling for the whole candidate list with the reference's sequential semantics (orbl_keyframe_culling;
+    include/orbslam_hip.h states the inputs).  cand_kf[ncand], cand_flags[ncand] (None = all 0; bit 0: id_ == 0, bit 1:
+    do_not_erase_), slot_off[ncand + 1], slot_pt / slot_level[nslots], obs_off[npts + 1], obs_kf / obs_level[nobs], pt_bad[npts]
+    (None = none bad), pt_nobs[npts] (None = the list lengths).  final_state=False passes NULL for the three state outputs.
+    out: optional dict of preset output arrays (every element is overwritten).  Returns a CullingResult."""
+    L = _lib.load()
+    ck = _c(cand_kf, np.int32).reshape(-1); ncand = len(ck)
+    cf = _c(cand_flags, np.uint8).reshape(-1) if cand_flags is not None else None
+    so = _c(slot_off, np.int32).reshape(-1); sp = _c(slot_pt, np.int32).reshape(-1); sl = _c(slot_level, np.int32).reshape(-1)
+    oo = _c(obs_off, np.int32).reshape(-1); ok_ = _c(obs_kf, np.int32).reshape(-1); ol = _c(obs_level, np.int32).reshape(-1)
+    npts = len(oo) - 1
+    assert len(so) == ncand + 1 and npts >= 0 and (cf is None or len(cf) == ncand) and len(sp) == len(sl) and len(ok_) == len(ol)
+    assert len(sp) >= (so[-1] if ncand else 0) and len(ok_) >= (oo[-1] if npts else 0)     # (the library checks the rest)
+    pb = _c(pt_bad, np.uint8).reshape(-1) if pt_bad is not None else None
+    pn = _c(pt_nobs, np.int32).reshape(-1) if pt_nobs is not None else None
+    assert (pb is None or len(pb) == npts) and (pn is None or len(pn) == npts)
+    o = {} if out is None else out
+    o.setdefault("culled", np.zeros(ncand, np.uint8)); o.setdefault("n_redundant", np.zeros(ncand, np.int32)); o.setdefault("n_map_points", np.zeros(ncand, np.int32))
+    if final_state:
+        o.setdefault("pt_bad", np.zeros(npts, np.uint8)); o.setdefault("pt_nobs", np.zeros(npts, np.int32)); o.setdefault("obs_erased", np.zeros(len(ok_), np.uint8))
+    for k, dt, n in (("culled", np.uint8, ncand), ("n_redundant", np.int32, ncand), ("n_map_points", np.int32, ncand), ("pt_bad", np.uint8, npts),
+                     ("pt_nobs", np.int32, npts), ("obs_erased", np.uint8, len(ok_))):
+        assert o.get(k) is None or (o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == n), k
+    _lib.check(L.orbl_keyframe_culling(ncand, _addr(ck), _addr(cf), _addr(so), _addr(sp), _addr(sl), int(nkf), npts, _addr(oo), _addr(ok_), _addr(ol), _addr(pb),
+                                       _addr(pn), int(th_obs), float(ratio), _addr(o["culled"]), _addr(o["n_redundant"]), _addr(o["n_map_points"]),
+                                       _addr(o.get("pt_bad")), _addr(o.get("pt_nobs")), _addr(o.get("obs_erased"))), "orbl_keyframe_culling")
+    return CullingResult(**o)
+
+
+def keyframe_culling_device(cand_kf, cand_flags, slot_off, slot_pt, slot_level, nkf, obs_off, obs_kf, obs_level, pt_bad=None, pt_nobs=None,
+                            th_obs=3, ratio=0.9, final_state=True, out=None):
+    """orbl_keyframe_culling_device on torch CUDA tensors (int32 / uint8 as in keyframe_culling; None where a pointer may be NULL),
+    enqueued on the current stream.  out: optional dict of preset device tensors.  Returns a CullingResult of device tensors whose
+    status (uint32 as int32[1]) is 0 when every entry was in range; the workspace is kept alive by the result."""
+    import torch
+    L = _lib.load()
+    dev = cand_kf.device
+    ncand, nslots, npts, nobs = cand_kf.numel(), slot_pt.numel(), obs_off.numel() - 1, obs_kf.numel()
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_keyframe_culling_workspace(ncand, nslots, npts, nobs, C.byref(nbytes)), "orbl_keyframe_culling_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    o = {} if out is None else out
+    for k, dt, n in (("culled", torch.uint8, ncand), ("n_redundant", torch.int32, ncand), ("n_map_points", torch.int32, ncand)) + \
+            ((("pt_bad", torch.uint8, npts), ("pt_nobs", torch.int32, npts), ("obs_erased", torch.uint8, nobs)) if final_state else ()):
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_keyframe_culling_device(ncand, p(cand_kf), p(cand_flags), nslots, p(slot_off), p(slot_pt), p(slot_level), int(nkf), npts, nobs, p(obs_off),
+                                              p(obs_kf), p(obs_level), p(pt_bad), p(pt_nobs), int(th_obs), float(ratio), p(o["culled"]), p(o["n_redundant"]),
+                                              p(o["n_map_points"]), p(o.get("pt_bad")), p(o.get("pt_nobs")), p(o.get("obs_erased")), p(status), p(ws),
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_keyframe_culling_device")
+    return CullingResult(status=status, _workspace=ws, **o)

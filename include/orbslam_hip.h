@@ -515,6 +515,50 @@ int orbl_update_map_points_device(int npts, const int32_t* d_obs_off, const doub
 /* *bytes = the workspace orbl_update_map_points_device needs for npts points (host arithmetic). */
 int orbl_update_map_points_workspace(int npts, size_t* bytes);
 
+/* ---- LocalMapping::KeyFrameCulling (src/LocalMapping.cc:576-637, monocular) for the WHOLE candidate list in ONE call, with the exact
+ * sequential semantics of the reference's loop: a culled keyframe's SetBadFlag() (src/KeyFrame.cc:460-480) erases its observations,
+ * MapPoint::EraseObservation (src/MapPoint.cc:140-162) turns a point with <= 2 observations left bad, and every LATER candidate counts
+ * under that state.
+ *   candidates, in the order of GetVectorCovisibleKeyFrames(): cand_kf[c] = keyframe index in [0, nkf); cand_flags[c] (nullable = all
+ *     0): bit 0 = id_ == 0 (:588, skipped), bit 1 = do_not_erase_ (SetBadFlag only notes do_to_be_erased_: nothing changes).
+ *   slots: slot_off[ncand + 1] (CSR, slot_off[0] = 0); for every non-null entry of the candidate's GetMapPointMatches(), in slot order,
+ *     slot_pt[s] = point index in [0, npts) and slot_level[s] = undistort_keypoints_[i].octave.
+ *   points: obs_off[npts + 1] (CSR) into obs_kf[e] (the observing keyframe) and obs_level[e] (the octave of that keyframe's keypoint);
+ *     pt_bad[p] (nullable = all 0) = isBad(): the lists of bad points are ignored; pt_nobs[p] (nullable = the list length) =
+ *     Observations().
+ *   th_obs (3 at the call site, >= 1), ratio (0.9).
+ * Per candidate c, in order, k = cand_kf[c]:
+ *   1. bit 0 set: culled = n_redundant = n_map_points = 0, next candidate.
+ *   2. every slot (p, l) whose point is not bad NOW: n_map_points++; if nobs[p] > th_obs and at least th_obs LIVE observations of p
+ *      have obs_kf != k and obs_level <= l + 1: n_redundant++.
+ *   3. culled = (double)n_redundant > ratio * (double)n_map_points (one IEEE double multiply).
+ *   4. culled and bit 1 clear: every point of a slot of c that is not bad and still has a live observation by k (once per point, however
+ *      often it is listed) loses that observation and nobs[p]--; when nobs[p] <= 2 the point turns bad and ALL its observations die.
+ *      A list that names keyframe k more than once: its first such entry is the keyframe's observation.
+ * Outputs: culled[ncand], n_redundant[ncand], n_map_points[ncand] as seen at each candidate's turn; nullable final state
+ * pt_bad_out[npts], pt_nobs_out[npts], obs_erased[nobs] (1 = the observation died).  Every output element is written.
+ * PRECONDITION for equality with the reference: the map is consistent - keyframe k holds point p in slot i iff p's observations
+ * contain (k, i).  The caller then applies SetBadFlag() to the keyframes with culled = 1, in list order.
+ * Host pointers, synchronous.  ORBHIP_EINVAL before any device work for negative counts, offsets that do not ascend from 0, indices
+ * outside [0, nkf) / [0, npts), negative levels, th_obs < 1, a ratio that is not finite; ORBHIP_ENODEV without a GPU.              */
+int orbl_keyframe_culling(int ncand, const int32_t* cand_kf, const uint8_t* cand_flags, const int32_t* slot_off, const int32_t* slot_pt, const int32_t* slot_level,
+                          int nkf, int npts, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_level, const uint8_t* pt_bad,
+                          const int32_t* pt_nobs, int th_obs, double ratio, uint8_t* culled, int32_t* n_redundant, int32_t* n_map_points, uint8_t* pt_bad_out,
+                          int32_t* pt_nobs_out, uint8_t* obs_erased);
+/* The same with DEVICE pointers, enqueued on `stream` (nslots = slot_off[ncand], nobs = obs_off[npts] given by the caller).  Counts,
+ * NULL pointers and 4-byte alignment of the 32-bit arrays are checked on the host; the data is bounds-checked on the device: an entry
+ * that is out of range (offsets, keyframe or point index, negative level) is treated as ABSENT - a slot or observation that is not
+ * there, a candidate skipped with zeros - and sets a bit in *d_status (nullable; zeroed first; 1 = offsets, 2 = index, 4 = level).
+ * `d_workspace`: at least orbl_keyframe_culling_workspace(...) bytes of device memory, 4-byte aligned, not shared with concurrent calls. */
+int orbl_keyframe_culling_device(int ncand, const int32_t* d_cand_kf, const uint8_t* d_cand_flags, int nslots, const int32_t* d_slot_off,
+                                 const int32_t* d_slot_pt, const int32_t* d_slot_level, int nkf, int npts, int nobs, const int32_t* d_obs_off,
+                                 const int32_t* d_obs_kf, const int32_t* d_obs_level, const uint8_t* d_pt_bad, const int32_t* d_pt_nobs, int th_obs, double ratio,
+                                 uint8_t* d_culled, int32_t* d_n_redundant, int32_t* d_n_map_points, uint8_t* d_pt_bad_out, int32_t* d_pt_nobs_out,
+                                 uint8_t* d_obs_erased, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_keyframe_culling_device needs (host arithmetic): nine 32-bit arrays - four per slot, two per observation,
+ * three per point - each rounded up to 256 bytes; ncand does not enter. */
+int orbl_keyframe_culling_workspace(int ncand, int nslots, int npts, int nobs, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
