@@ -173,8 +173,8 @@ __global__ __launch_bounds__(256) void k_pose_lm(const double* __restrict__ K4s,
         POSE_T(6);
         if (!ok || !(mcc > 0.0)) {
           if (tid == 0) {
-            if (++s_invalid >= 5) { s_term = 5; s_done = 1; }
-            s_radius = radius / s_dec; s_dec *= 2;
+            if (++s_invalid >= 5) { s_term = 5; s_done = 1; }                 // HandleInvalidStep returns BEFORE StepIsInvalid: the radius stays
+            else { s_radius = radius / s_dec; s_dec *= 2; }
           }
         } else {
           double d[3], cand[7];
@@ -371,8 +371,8 @@ __global__ __launch_bounds__(256) void k_sim3_lm(const double* __restrict__ K1s,
           }
         }
         if (!ok || !(mcc > 0.0)) {
-          if (++s_invalid >= 5) { s_term = 5; s_done = 1; }
-          s_radius /= s_dec; s_dec *= 2;
+          if (++s_invalid >= 5) { s_term = 5; s_done = 1; }                   // (as k_pose_lm: the fifth invalid step ends the solve, the radius stays)
+          else { s_radius /= s_dec; s_dec *= 2; }
         } else {
           s_invalid = 0; s_valid = 1; s_mcc = mcc;
           double d[7];

@@ -154,3 +154,10 @@ def test_golden_sim3_fixture():
         assert _close(S, g["p%d_s12" % i], RTOL_X) and s["iterations"] == int(g["p%d_iters" % i]) and s["successful_steps"] == 0
         assert _close(s["final_cost"], g["p%d_cost" % i][1], RTOL_COST)
     assert _close(optimizer.sim3_exp(g["exp_in"]), g["exp_out"], 1e-14)
+
+
+@pytest.mark.parametrize("n,seed", [(127, 300), (127, 301), (128, 300), (128, 301), (129, 301), (255, 300), (255, 301), (256, 300), (256, 301), (257, 300), (257, 301)])
+def test_optimize_sim3_sizes_at_the_workgroup_stride(oracle, n, seed):
+    """k_sim3_lm walks its 2 n residual blocks in strides of 256: n = 127 .. 129 and 255 .. 257 put 2 n just below, on and just above
+    one and two strides.  Near starts where the oracle accepts no step, so the strict regime applies: everything identical, 1e-9."""
+    _check(oracle, synth.make_sim3_problem(seed, n=n, scale=1.02, perturb=(0.002, 0.01, 0.003)), expect="strict")

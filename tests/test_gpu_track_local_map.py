@@ -128,3 +128,46 @@ def test_track_local_map_needs_the_resident_frame_and_handles_empty_maps(oracle)
             err.append(str(e))
     t = threading.Thread(target=other); t.start(); t.join()
     assert err and "no frame resident" in err[0]
+
+
+def test_track_local_map_4000_features_pose_solve_streams_its_observations(oracle):
+    """A 4000-feature frame (the initialisation extractor's size) with ~90 % of its keypoints bound to map points: more than 2048
+    correspondences, so the pose solve behind the device-resident call takes k_pose_lm's streaming path (csrc/ba_small_lm.inc: the
+    observations stay in registers only up to 2048).  Empty local map, caller-supplied slots: each keypoint back-projected at a depth
+    of 4 - 60 m under a true pose from a pixel 1 px x scale off, 3 % wrong associations, the predicted pose perturbed as _scenario's.
+    Expected: the oracle's PoseOptimization over the slots in feature order, as _expected composes it."""
+    from ceres_mono_orb_slam2_amd import ORBextractor, tracking
+    rng = np.random.default_rng(20)
+    img = synth.make_frame(20, 1241, 376, "checker")
+    ex = ORBextractor(4000, 1.2, 8, 20, 7)
+    E = oracle.OracleExtractor(4000)
+    pose_true = np.concatenate([0.3 * rng.standard_normal(3), synth.quat_from_rotvec(0.05 * rng.standard_normal(3))])
+    pose_pred = np.concatenate([pose_true[:3] + 0.02 * rng.standard_normal(3), synth.quat_mul(synth.quat_from_rotvec(2e-3 * rng.standard_normal(3)), pose_true[3:])])
+    T = oracle.pose7_to_matrix4d(pose_pred)
+    z = np.zeros
+    got1 = tracking.track_with_motion_model(ex, img, K4, BOUNDS, T, z((0, 3)), z((0, 32), np.uint8), z(0, np.int32), z(0, np.float32), z(0, np.uint8))
+    kps = got1["kps"]
+    nk = len(kps)
+    assert np.array_equal(kps, E.extract(img)[0]) and nk > 3000
+    octave = kps["octave"].astype(int)
+    px = np.stack([kps["x"], kps["y"]], 1).astype(np.float64) + rng.standard_normal((nk, 2)) * E.scale[octave][:, None]
+    depth = rng.uniform(4, 60, nk)
+    pc = np.stack([(px[:, 0] - K4[2]) / K4[0] * depth, (px[:, 1] - K4[3]) / K4[1] * depth, depth], 1)
+    slot_X = (pc - pose_true[:3]) @ synth.quat_to_R(pose_true[3:])              # X = R^T (pc - t)
+    slot_X[rng.random(nk) < 0.03] *= 1.4                                       # wrong associations -> outliers
+    slot_state = np.ones(nk, np.uint8)
+    slot_state[rng.random(nk) < 0.1] = 3
+    slot_state[rng.random(nk) < 0.1] = 0
+    got = tracking.track_local_map(ex, K4, BOUNDS, T, F32(np.log(F32(1.2))), z((0, 3)), z((0, 3)), z(0, np.float32), z(0, np.float32), z((0, 32), np.uint8), z(0, np.uint8),
+                                   slot_X, slot_state)
+    feat = np.nonzero(slot_state != 0)[0]
+    uv = np.stack([kps["x"], kps["y"]], 1).astype(np.float32)
+    ninl, pose, out, s = oracle.pose_optimization(K4.astype(np.float64), oracle.matrix4d_to_pose7(T), slot_X[feat], uv[feat].astype(np.float64), E.inv_sigma2[octave[feat]])
+    outl = np.zeros(nk, bool); outl[feat] = out.astype(bool)
+    print("TrackLocalMap, 4000 features: %d keypoints, %d correspondences, %d inliers, oracle %s" % (nk, got["n_correspondences"], got["n_inliers"], s))
+    assert got["n_correspondences"] == len(feat) and got["n_correspondences"] > 2048
+    assert got["nmatches"] == 0 and (got["owner"] == -1).all()
+    assert np.array_equal(got["outlier"], outl)
+    assert got["n_inliers"] == int(ninl) and 0.8 * len(feat) < ninl < len(feat)
+    assert np.allclose(got["pose7"], pose, rtol=0, atol=1e-7)
+    assert s["successful_steps"] >= 2 and np.abs(pose[:3] - pose_true[:3]).max() < 0.02
