@@ -34,6 +34,27 @@ int frame_area_candidates_enqueue(const FrameGridDev& g, const float* d_kps4, co
                                   uint32_t* d_cand_idx, uint32_t cap, int idx_stride, hipStream_t s);
 // exclusive scan of d_cnt[0..n) into d_off[0..n] (one workgroup); enqueue only
 int frame_scan_enqueue(const int* d_cnt, int n, uint32_t* d_off, hipStream_t s);
+// cv::undistortPoints(src, dst, K, dist, noArray(), K) for one point: 5 fixed-point iterations in double (OpenCV 2.4 / 3.2,
+// SURVEY Appendix A), distortion (k1, k2, p1, p2, k3); result rounded to float like the CV_32F destination.  ONE statement of the
+// operation order for k_undistort (orb_frame.hip), the resident frame of orb_track.hip and the host's orbt_image_bounds: the three
+// are bit-equal on the same inputs (un-contracted build, IEEE double division on both sides).
+__host__ __device__ __forceinline__ void undistort_point(const float px, const float py, const double fx, const double fy, const double cx, const double cy,
+                                                         const double k1, const double k2, const double p1, const double p2, const double k3, float& ox, float& oy) {
+  const double ifx = 1. / fx, ify = 1. / fy;
+  double x = ((double)px - cx) * ifx, y = ((double)py - cy) * ify;
+  const double x0 = x, y0 = y;
+  for (int j = 0; j < 5; j++) {
+    const double r2 = x * x + y * y;
+    const double icdist = 1. / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
+    const double deltaX = 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
+    const double deltaY = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+    x = (x0 - deltaX) * icdist;
+    y = (y0 - deltaY) * icdist;
+  }
+  ox = (float)(fx * x + cx);
+  oy = (float)(fy * y + cy);
+}
+
 // Frame::isInFrustum (src/Frame.cc:191-241) + MapPoint::PredictScale (src/MapPoint.cc:406-420) for one map point, in the reference's
 // float / double mix (k_frustum of orb_frame.hip and the TrackLocalMap step of orb_track.hip share it)
 struct FrustumCam { double R[9], t[3], Ow[3]; float fx, fy, cx, cy, min_x, max_x, min_y, max_y, cos_limit, log_scale; int nlevels; };

@@ -22,25 +22,15 @@
 namespace orbhip {
 
 // ---------------------------------------------------------------------------- undistort
-// cv::undistortPoints(src, dst, K, dist, noArray(), K): 5 fixed-point iterations in double (OpenCV 2.4 / 3.2,
-// SURVEY Appendix A), distortion (k1, k2, p1, p2, k3); result rounded to float like the CV_32F destination.
+// cv::undistortPoints(src, dst, K, dist, noArray(), K): undistort_point (orb_frame.h) per keypoint
 __global__ void k_undistort(const float* __restrict__ xy, int n, double fx, double fy, double cx, double cy, double k1, double k2,
                             double p1, double p2, double k3, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double ifx = 1. / fx, ify = 1. / fy;
-  double x = ((double)xy[2 * i] - cx) * ifx, y = ((double)xy[2 * i + 1] - cy) * ify;
-  const double x0 = x, y0 = y;
-  for (int j = 0; j < 5; j++) {
-    const double r2 = x * x + y * y;
-    const double icdist = 1. / (1 + ((k3 * r2 + k2) * r2 + k1) * r2);
-    const double deltaX = 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
-    const double deltaY = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
-    x = (x0 - deltaX) * icdist;
-    y = (y0 - deltaY) * icdist;
-  }
-  out[2 * i] = (float)(fx * x + cx);
-  out[2 * i + 1] = (float)(fy * y + cy);
+  float ox, oy;
+  undistort_point(xy[2 * i], xy[2 * i + 1], fx, fy, cx, cy, k1, k2, p1, p2, k3, ox, oy);
+  out[2 * i] = ox;
+  out[2 * i + 1] = oy;
 }
 
 // ---------------------------------------------------------------------------- grid

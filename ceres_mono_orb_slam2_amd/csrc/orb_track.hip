@@ -57,15 +57,22 @@ struct TrkIn {                                               // the packed const
   float K4[4], bounds[4], th;
   float scale[16], inv_sigma2[16];
   int nq, check_ori, nlevels, pad;
+  double dist[5];                                            // (k1, k2, p1, p2, k3) widened from float, read by k_trk_prepare<true> only; appended: the offsets above stay
 };
 
 // ---- one workgroup: queries, the frame's float records, its grid ------------------------------------------------------
+// DIST: the camera has lens distortion (Frame::UndistortKeyPoints, src/Frame.cc:329-355, between the extractor and AssignFeaturesToGrid
+// src/Frame.cc:115-155): every keypoint is undistorted (undistort_point, orb_frame.h) before its record and its cell are made, and the
+// undistorted {x, y} also go to und_xy (the call's download block).  A keypoint that leaves the grid (PosInGrid false, :313-317) is in
+// no cell and keeps its record.  DIST == false is the kernel as it always was (und_xy is not touched).
+template <bool DIST>
 __global__ __launch_bounds__(1024) void k_trk_prepare(const TrkIn* __restrict__ in, const double* __restrict__ last_Xw,
                                                       const int32_t* __restrict__ last_octave, const uint8_t* __restrict__ last_valid,
                                                       const orbx_keypoint* __restrict__ kps, const int32_t* __restrict__ d_count, int cap,
                                                       float* __restrict__ q_uv, float* __restrict__ q_radius, int32_t* __restrict__ q_lo,
                                                       int32_t* __restrict__ q_hi, uint8_t* __restrict__ q_valid, float* __restrict__ kps4,
-                                                      uint32_t* __restrict__ cell_off, uint32_t* __restrict__ cell_idx, const int nq, uint32_t* __restrict__ list_total) {
+                                                      uint32_t* __restrict__ cell_off, uint32_t* __restrict__ cell_idx, const int nq, uint32_t* __restrict__ list_total,
+                                                      float* __restrict__ und_xy) {
   __shared__ int s_cnt[TRK_NCELL];
   __shared__ int s_off[TRK_NCELL + 1];
   __shared__ unsigned short s_cell[TRK_MAXKP];
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(1024) void k_trk_prepare(const TrkIn* __restrict__ 
     }
     q_uv[2 * i] = u; q_uv[2 * i + 1] = vv; q_radius[i] = rad; q_lo[i] = oc - 1; q_hi[i] = oc + 1; q_valid[i] = v;
   }
-  // the frame: {x, y, octave, angle} of the (undistorted == raw: zero distortion) keypoints and their grid cells (src/Frame.cc:158-173, :309-320)
+  // the frame: {x, y, octave, angle} of the undistorted keypoints (the raw ones without distortion) and their grid cells (src/Frame.cc:158-173, :309-320)
   const float winv = (float)FRAME_GRID_COLS / (I.bounds[1] - I.bounds[0]), hinv = (float)FRAME_GRID_ROWS / (I.bounds[3] - I.bounds[2]);
   __syncthreads();
 #pragma unroll
@@ -119,11 +126,25 @@ __global__ __launch_bounds__(1024) void k_trk_prepare(const TrkIn* __restrict__ 
     const int i = tid + 1024 * kk;
     if (i >= n) continue;
     const orbx_keypoint k = kp[kk];
-    *(float4*)&kps4[4 * i] = make_float4(k.x, k.y, (float)k.octave, k.angle);
-    const int px = (int)roundf((k.x - I.bounds[0]) * winv), py = (int)roundf((k.y - I.bounds[2]) * hinv);
-    unsigned short id = 0xFFFF;
-    if (!(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS)) { id = (unsigned short)(px * FRAME_GRID_ROWS + py); atomicAdd(&s_cnt[id], 1); }
-    s_cell[i] = id;
+    if constexpr (DIST) {
+      float ux, uy;                                               // (constant indices into the private copy: a dynamic one puts the struct into scratch, see above)
+      undistort_point(k.x, k.y, (double)I.K4[0], (double)I.K4[1], (double)I.K4[2], (double)I.K4[3], I.dist[0], I.dist[1], I.dist[2], I.dist[3], I.dist[4], ux, uy);
+      *(float4*)&kps4[4 * i] = make_float4(ux, uy, (float)k.octave, k.angle);
+      *(float2*)&und_xy[2 * i] = make_float2(ux, uy);
+      unsigned short id = 0xFFFF;
+      // a non-finite coordinate is outside, said explicitly: what (int) makes of it is the target's business
+      if (isfinite(ux) && isfinite(uy)) {
+        const int px = (int)roundf((ux - I.bounds[0]) * winv), py = (int)roundf((uy - I.bounds[2]) * hinv);
+        if (!(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS)) { id = (unsigned short)(px * FRAME_GRID_ROWS + py); atomicAdd(&s_cnt[id], 1); }
+      }
+      s_cell[i] = id;
+    } else {
+      *(float4*)&kps4[4 * i] = make_float4(k.x, k.y, (float)k.octave, k.angle);
+      const int px = (int)roundf((k.x - I.bounds[0]) * winv), py = (int)roundf((k.y - I.bounds[2]) * hinv);
+      unsigned short id = 0xFFFF;
+      if (!(px < 0 || px >= FRAME_GRID_COLS || py < 0 || py >= FRAME_GRID_ROWS)) { id = (unsigned short)(px * FRAME_GRID_ROWS + py); atomicAdd(&s_cnt[id], 1); }
+      s_cell[i] = id;
+    }
   }
   __syncthreads();
   // exclusive scan of the 3072 cell counts: three per thread, wave scan, wave totals through LDS
@@ -1095,8 +1116,48 @@ struct TrkFrame {
   const orbx_ctx* producer = nullptr;      // the extractor that produced the resident frame: its level count / scale tables / capacity are the frame's
   unsigned long long producer_gen = 0;     // ... and its generation: a context destroyed and re-created at the same address is NOT that extractor
   bool made_by(const orbx_ctx* c) const { return producer == c && producer_gen == orbhip::orbx_ctx_generation(c); }
+  // lens distortion: the coefficients that built the frame (dist_on false: none), where k_trk_prepare<true> wrote the undistorted
+  // {x, y} inside blk, and the host's copy of undistort_keypoints_[i].pt from the producing call's download (orbt_last_undistorted_keypoints)
+  bool dist_on = false; float dist[5] = {0, 0, 0, 0, 0}; size_t oUnd = 0; std::vector<float> und_xy;
 };
 thread_local TrkFrame g_trk_frame;
+
+// orbt_set_distortion: the coefficients of the calling thread's extractors, keyed by the context and its generation (a context
+// re-created at the same address starts without distortion).  Extractors without distortion have no entry.
+struct TrkDist { const orbx_ctx* ctx; unsigned long long gen; float d[5]; };
+thread_local std::vector<TrkDist> g_trk_dist;
+const float* trk_distortion_of(const orbx_ctx* c) {
+  std::vector<TrkDist>& V = g_trk_dist;
+  for (size_t i = 0; i < V.size(); i++) {
+    if (V[i].ctx != c) continue;
+    if (V[i].gen == orbhip::orbx_ctx_generation(c)) return V[i].d;
+    V.erase(V.begin() + (long)i);                             // an earlier context that lived at this address: its entry goes
+    return nullptr;                                            // (only c itself is known to be alive: the other entries' contexts cannot be looked at)
+  }
+  return nullptr;
+}
+void trk_fill_distortion(TrkIn& I, const float* d) {
+  for (int k = 0; k < 5; k++) I.dist[k] = d ? (double)d[k] : 0.0;
+}
+// the coefficients `d` (nullptr: none) are the ones the resident frame was built with: a call that goes on with that frame (orbt_track_local_map,
+// img == NULL) after orbt_set_distortion changed them would mix two cameras - its bounds belong to the new coefficients, the grid to the old
+bool trk_same_distortion(const TrkFrame& TF, const float* d) {
+  if (!d) return !TF.dist_on;
+  return TF.dist_on && std::memcmp(TF.dist, d, sizeof(TF.dist)) == 0;
+}
+template <typename... A> void trk_prepare_launch(bool dist, hipStream_t s, A... a) {
+  if (dist) hipLaunchKernelGGL(k_trk_prepare<true>, dim3(1), dim3(1024), 0, s, a...);
+  else hipLaunchKernelGGL(k_trk_prepare<false>, dim3(1), dim3(1024), 0, s, a...);
+}
+// the producing call's downloaded block -> TF.und_xy (h_und NULL: no distortion, the raw coordinates)
+void trk_keep_undistorted(TrkFrame& TF, const float* d, const uint8_t* h_kps, const uint8_t* h_und, int n) {
+  TF.dist_on = d != nullptr;
+  for (int k = 0; k < 5; k++) TF.dist[k] = d ? d[k] : 0.f;
+  TF.und_xy.resize(2 * (size_t)n);
+  if (h_und) { std::memcpy(TF.und_xy.data(), h_und, 8 * (size_t)n); return; }
+  const orbx_keypoint* kp = (const orbx_keypoint*)h_kps;
+  for (int i = 0; i < n; i++) { TF.und_xy[2 * i] = kp[i].x; TF.und_xy[2 * i + 1] = kp[i].y; }
+}
 }  // namespace
 
 // host wall time of the calling thread's most recent orbt_* call (orbt_last_call_ms): what a latency figure should be made of when
@@ -1116,6 +1177,46 @@ int orbt_debug_prof(int* out, int reset) {
   return 0;
 }
 #endif
+
+// Frame::ComputeImageBounds (src/Frame.cc:357-385) on the host: the four corners through undistort_point, paired as :374-377 pair them
+int orbt_image_bounds(int w, int h, const float* K4, const float* dist5, float* bounds4) {
+  ORBHIP_REQUIRE(K4 && dist5 && bounds4, ORBHIP_EINVAL, "NULL argument");
+  ORBHIP_REQUIRE(w > 0 && h > 0, ORBHIP_EINVAL, "bad image dimensions");
+  for (int k = 0; k < 4; k++) ORBHIP_REQUIRE(std::isfinite(K4[k]), ORBHIP_EINVAL, "non-finite intrinsics");
+  for (int k = 0; k < 5; k++) ORBHIP_REQUIRE(std::isfinite(dist5[k]), ORBHIP_EINVAL, "non-finite distortion coefficient");
+  if (dist5[0] == 0.0f) { bounds4[0] = 0.0f; bounds4[1] = (float)w; bounds4[2] = 0.0f; bounds4[3] = (float)h; return 0; }      // k1 alone is tested (:358)
+  const float cx[4] = {0.0f, (float)w, 0.0f, (float)w}, cy[4] = {0.0f, 0.0f, (float)h, (float)h};
+  float ux[4], uy[4];
+  for (int c = 0; c < 4; c++)
+    orbhip::undistort_point(cx[c], cy[c], (double)K4[0], (double)K4[1], (double)K4[2], (double)K4[3], (double)dist5[0], (double)dist5[1], (double)dist5[2],
+                            (double)dist5[3], (double)dist5[4], ux[c], uy[c]);
+  bounds4[0] = std::min(ux[0], ux[2]); bounds4[1] = std::max(ux[1], ux[3]);
+  bounds4[2] = std::min(uy[0], uy[1]); bounds4[3] = std::max(uy[2], uy[3]);
+  return 0;
+}
+
+int orbt_set_distortion(orbx_ctx* ctx, const float* dist5) {
+  ORBHIP_REQUIRE(ctx, ORBHIP_EINVAL, "NULL context");
+  if (dist5) for (int k = 0; k < 5; k++) ORBHIP_REQUIRE(std::isfinite(dist5[k]), ORBHIP_EINVAL, "non-finite distortion coefficient");
+  std::vector<TrkDist>& V = g_trk_dist;
+  V.erase(std::remove_if(V.begin(), V.end(), [&](const TrkDist& e) { return e.ctx == ctx; }), V.end());
+  if (!dist5 || dist5[0] == 0.0f) return 0;                    // src/Frame.cc:330-333: k1 == 0 -> the keypoints are taken as they are
+  TrkDist e; e.ctx = ctx; e.gen = orbhip::orbx_ctx_generation(ctx);
+  for (int k = 0; k < 5; k++) e.d[k] = dist5[k];
+  V.push_back(e);
+  return 0;
+}
+
+int orbt_last_undistorted_keypoints(orbx_ctx* ctx, float* xy, int cap, int* n) {
+  ORBHIP_REQUIRE(ctx && n && cap >= 0 && (xy || cap == 0), ORBHIP_EINVAL, "NULL argument");
+  const TrkFrame& TF = g_trk_frame;
+  ORBHIP_REQUIRE(TF.valid && TF.made_by(ctx) && TF.und_xy.size() == 2 * (size_t)TF.n_kp, ORBHIP_EINVAL,
+                 "no frame of this extractor from an extracting orbt_* call of this thread");
+  *n = TF.n_kp;
+  ORBHIP_REQUIRE(cap >= TF.n_kp, ORBHIP_ECAP, "capacity below the frame's keypoint count");
+  if (TF.n_kp) std::memcpy(xy, TF.und_xy.data(), 8 * (size_t)TF.n_kp);
+  return 0;
+}
 
 int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h, int stride, const float* K4, const float* bounds,
                                  const double* Tcw_pred, const double* last_Xw, const uint8_t* last_desc, const int32_t* last_octave,
@@ -1155,6 +1256,8 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
     { double T[16]; for (int k = 0; k < 12; k++) T[k] = Tcw_pred[k]; T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1; if (int r2 = ba_matrix4d_to_pose7(T, I.pose7)) return r2; }
     for (int k = 0; k < 4; k++) { I.K4[k] = K4[k]; I.bounds[k] = bounds[k]; }
     I.th = th; I.nq = nq; I.check_ori = check_ori ? 1 : 0; I.nlevels = nlevels;
+    const float* dist5 = trk_distortion_of(ctx);
+    trk_fill_distortion(I, dist5);
     if (int r2 = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr)) return r2;
     // uploads: the image (straight from the caller's memory through pinned staging) and ONE packed block
     const size_t img_bytes = (size_t)stride * (h - 1) + w;
@@ -1170,6 +1273,7 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
     const size_t oOut = take(sizeof(TrkOut)), oPose = take(56), oSum = take(sizeof(ba_summary)), oCnt = take(4), oNin = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)),
                  oDesc = take((size_t)icap * 32), oMatch = take(4 * (size_t)std::max(nq, 1)), oOwner = take(4 * (size_t)icap), oFeat = take(4 * (size_t)icap),
                  oOutl = take((size_t)icap);
+    const size_t oUnd = dist5 ? take(8 * (size_t)icap) : 0;      // (behind everything else: without distortion the block is what it always was)
     if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap))) return rc;
     uint8_t* dblk = TF.blk.as<uint8_t>();
     float* d_quv = W.d<float>(2 * (size_t)std::max(nq, 1), &rc); float* d_qr = W.d<float>(std::max(nq, 1), &rc);
@@ -1187,8 +1291,9 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
     orbx_keypoint* d_kps = (orbx_keypoint*)(dblk + oKps); uint8_t* d_desc = dblk + oDesc; int32_t* d_count = (int32_t*)(dblk + oCnt);
     if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, d_kps, d_desc, icap, d_count, (void*)W.s))) return rc;
     const TrkIn* dI = in.dev<TrkIn>(pI);
-    hipLaunchKernelGGL(k_trk_prepare, dim3(1), dim3(1024), 0, W.s, dI, in.dev<double>(pX), in.dev<int32_t>(pO), in.dev<uint8_t>(pV), d_kps, d_count, icap, d_quv, d_qr,
-                       d_qlo, d_qhi, d_qv, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), nq, d_total);
+    trk_prepare_launch(dist5 != nullptr, W.s, dI, (const double*)in.dev<double>(pX), (const int32_t*)in.dev<int32_t>(pO), (const uint8_t*)in.dev<uint8_t>(pV), (const orbx_keypoint*)d_kps,
+                       (const int32_t*)d_count, icap, d_quv, d_qr, d_qlo, d_qhi, d_qv, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), nq, d_total,
+                       dist5 ? (float*)(dblk + oUnd) : (float*)nullptr);
     if (nq > 0) {
       hipLaunchKernelGGL(k_trk_windows, dim3((nq + 3) / 4), dim3(256), 0, W.s, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), grid.min_x, grid.min_y, grid.winv,
                          grid.hinv, d_quv, d_qr, d_qlo, d_qhi, d_qv, nq, in.dev<uint8_t>(pD), d_desc, d_total, d_off, d_pairs, cand_cap, d_acc, d_accn, TRK_TH_HIGH);
@@ -1223,6 +1328,7 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
     const int32_t* feat = (const int32_t*)(hb + oFeat);
     for (int k = 0; k < T->nobs; k++) outlier_out[feat[k]] = hb[oOutl + k];
     TF.oKps = oKps; TF.oDesc = oDesc; TF.oCnt = oCnt; TF.icap = icap; TF.n_kp = n; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16); TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx);
+    TF.oUnd = oUnd; trk_keep_undistorted(TF, dist5, hb + oKps, dist5 ? hb + oUnd : nullptr, n);
     res->n_keypoints = n; res->nmatches = T->nmatches; res->n_correspondences = T->nobs; res->greedy_rounds = T->rounds % 1000;
     std::memcpy(res->pose7, hb + oPose, 56);
     // PoseOptimization returns 0 and leaves the pose alone with fewer than 3 correspondences (src/CeresOptimizer.cc:330)
@@ -1266,6 +1372,7 @@ int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, co
     ORBHIP_REQUIRE(TF.valid && TF.device == W.device, ORBHIP_EINVAL, "no frame resident on this thread's device: call orbt_track_with_motion_model first (same host thread)");
     ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
     ORBHIP_REQUIRE(n_kp == TF.n_kp, ORBHIP_EINVAL, "n_kp differs from the resident frame's keypoint count");
+    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
     const int icap = TF.icap, nq = n_mp;
     TlmIn I; std::memset(&I, 0, sizeof(I));
     for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.C.R[3 * r + c] = Tcw[4 * r + c]; I.C.t[r] = Tcw[4 * r + 3]; }
@@ -1365,6 +1472,8 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
   TrkIn PI; std::memset(&PI, 0, sizeof(PI));                   // k_trk_prepare's constants (no queries: it builds the frame's records and grid)
   for (int k = 0; k < 4; k++) { PI.K4[k] = K4[k]; PI.bounds[k] = bounds[k]; }
   PI.nlevels = nlevels; std::memcpy(PI.scale, scale, sizeof(scale));
+  const float* dist5 = img ? trk_distortion_of(ctx) : nullptr;
+  trk_fill_distortion(PI, dist5);
   const int pI = in.add(&I, sizeof(I)), pP = in.add(&PI, sizeof(PI)), pD = in.add(kf_desc, 32 * (size_t)n_kf), pV = in.add(kf_valid, (size_t)n_kf), pA = in.add(kf_angle, 4 * (size_t)n_kf),
             pX = in.add(kf_Xw, 24 * (size_t)n_kf), pFn = in.add(kf_fv_node, 4 * (size_t)kf_fv_n), pFo = in.add(kf_fv_off, 4 * ((size_t)kf_fv_n + 1)), pFi = in.add(kf_fv_idx, 4 * (size_t)n_fv_idx);
   uint8_t* d_img = nullptr;
@@ -1374,25 +1483,26 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
   } else {
     ORBHIP_REQUIRE(TF.valid, ORBHIP_EINVAL, "img == NULL needs the frame of an earlier orbt_* call of this thread on the device");
     ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels && TF.icap == icap, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
+    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
   }
   if (rc || (rc = W.commit(in))) return rc;
   if (img) {
     // the same frame block orbt_track_with_motion_model leaves behind: [.. | count | keypoints | descriptors | ..]
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32);
+    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32), oUnd = dist5 ? take(8 * (size_t)icap) : 0;
     TF.valid = false;
     if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap)) || (rc = TF.grid.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = TF.grid.idx.ensure((size_t)icap * 4))) return rc;
-    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
+    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.oUnd = oUnd; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
     TF.grid.min_x = bounds[0]; TF.grid.min_y = bounds[2];
     TF.grid.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); TF.grid.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
     uint8_t* fb = TF.blk.as<uint8_t>();
     if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, (orbx_keypoint*)(fb + oKps), fb + oDesc, icap, (int32_t*)(fb + oCnt), (void*)W.s))) return rc;
     float* d_dummy = W.d<float>(4, &rc); int32_t* d_di = W.d<int32_t>(4, &rc); uint8_t* d_db = W.d<uint8_t>(4, &rc); uint32_t* d_tot = W.d<uint32_t>(1, &rc);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_trk_prepare, dim3(1), dim3(1024), 0, W.s, in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
+    trk_prepare_launch(dist5 != nullptr, W.s, (const TrkIn*)in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
                        (const orbx_keypoint*)(fb + oKps), (const int32_t*)(fb + oCnt), icap, d_dummy, d_dummy, d_di, d_di, d_db, TF.kps4.as<float>(),
-                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot);
+                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot, dist5 ? (float*)(fb + oUnd) : (float*)nullptr);
   }
   const uint8_t* fblk = TF.blk.as<uint8_t>();
   const float* d_kps4 = TF.kps4.as<float>();
@@ -1422,12 +1532,13 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
   ORBHIP_CHECK_HIP(hipGetLastError());
   if ((rc = ba_pose_optimization_batch_device(d_K4, (double*)(dblk + oPose), d_oX, d_ouv, d_ow, d_ooff, 1, dblk + oOutl, (int32_t*)(dblk + oNin), (ba_summary*)(dblk + oSum), (void*)W.s))) return rc;
   const uint8_t* hb = W.down(dblk, o, &rc);
-  const uint8_t* hf = img ? W.down(fblk, TF.oDesc + (size_t)fcap * 32, &rc) : nullptr;
+  const uint8_t* hf = img ? W.down(fblk, dist5 ? TF.oUnd + (size_t)fcap * 8 : TF.oDesc + (size_t)fcap * 32, &rc) : nullptr;
   if (rc || (rc = W.sync())) return rc;
   const TrkOut* T = (const TrkOut*)(hb + oOut);
   if (T->n_keypoints < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
   const int n = std::min(T->n_keypoints, fcap);
-  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32); }
+  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32);
+             trk_keep_undistorted(TF, dist5, hf + TF.oKps, dist5 ? hf + TF.oUnd : nullptr, n); }
   if (n != TF.n_kp) { set_error("resident frame changed"); return ORBHIP_EINVAL; }
   if (bow_word && bow_value && fv_node && fv_idx)
     orbhip::orbv_merge_host((const int32_t*)(hb + oWord), (const double*)(hb + oWt), (const uint32_t*)(hb + oNode), n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
@@ -1480,6 +1591,8 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
   TrkIn PI; std::memset(&PI, 0, sizeof(PI));
   for (int k = 0; k < 4; k++) { PI.K4[k] = K4[k]; PI.bounds[k] = bounds[k]; }
   PI.nlevels = nlevels; std::memcpy(PI.scale, scale, sizeof(scale));
+  const float* dist5 = img ? trk_distortion_of(ctx) : nullptr;
+  trk_fill_distortion(PI, dist5);
   const int pP = in.add(&PI, sizeof(PI));
   std::vector<TrfIn> h_in((size_t)std::max(n_cand, 1));
   struct Pieces { int d, v, a, fn, fo, fi; };
@@ -1501,25 +1614,26 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
   else {
     ORBHIP_REQUIRE(TF.valid, ORBHIP_EINVAL, "img == NULL needs the frame of an earlier orbt_* call of this thread on the device");
     ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels && TF.icap == icap, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
+    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
   }
   if (rc || (rc = W.commit(in))) return rc;
   if (img) {
     ORBHIP_REQUIRE(kps_out && desc_out, ORBHIP_EINVAL, "NULL output");
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32);
+    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32), oUnd = dist5 ? take(8 * (size_t)icap) : 0;
     TF.valid = false;
     if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap)) || (rc = TF.grid.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = TF.grid.idx.ensure((size_t)icap * 4))) return rc;
-    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
+    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.oUnd = oUnd; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
     TF.grid.min_x = bounds[0]; TF.grid.min_y = bounds[2];
     TF.grid.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); TF.grid.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
     uint8_t* fb = TF.blk.as<uint8_t>();
     if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, (orbx_keypoint*)(fb + oKps), fb + oDesc, icap, (int32_t*)(fb + oCnt), (void*)W.s))) return rc;
     float* d_dummy = W.d<float>(4, &rc); int32_t* d_di = W.d<int32_t>(4, &rc); uint8_t* d_db = W.d<uint8_t>(4, &rc); uint32_t* d_tot = W.d<uint32_t>(1, &rc);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_trk_prepare, dim3(1), dim3(1024), 0, W.s, in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
+    trk_prepare_launch(dist5 != nullptr, W.s, (const TrkIn*)in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
                        (const orbx_keypoint*)(fb + oKps), (const int32_t*)(fb + oCnt), icap, d_dummy, d_dummy, d_di, d_di, d_db, TF.kps4.as<float>(),
-                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot);
+                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot, dist5 ? (float*)(fb + oUnd) : (float*)nullptr);
   }
   const uint8_t* fblk = TF.blk.as<uint8_t>();
   const float* d_kps4 = TF.kps4.as<float>();
@@ -1556,12 +1670,13 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
   }
   ORBHIP_CHECK_HIP(hipGetLastError());
   const uint8_t* hb = W.down(dblk, o, &rc);
-  const uint8_t* hf = img ? W.down(fblk, TF.oDesc + (size_t)fcap * 32, &rc) : W.down(fblk, 256, &rc);
+  const uint8_t* hf = img ? W.down(fblk, dist5 ? TF.oUnd + (size_t)fcap * 8 : TF.oDesc + (size_t)fcap * 32, &rc) : W.down(fblk, 256, &rc);
   if (rc || (rc = W.sync())) return rc;
   const int n_dev = *(const int32_t*)(hf + TF.oCnt);
   if (n_dev < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
   const int n = std::min(n_dev, fcap);
-  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32); }
+  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32);
+             trk_keep_undistorted(TF, dist5, hf + TF.oKps, dist5 ? hf + TF.oUnd : nullptr, n); }
   if (n != TF.n_kp) { set_error("resident frame changed"); return ORBHIP_EINVAL; }
   *n_keypoints = n;
   if (bow_word && bow_value && fv_node && fv_idx)

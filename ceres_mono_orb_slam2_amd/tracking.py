@@ -26,10 +26,48 @@ def _addr(a):
     return a.__array_interface__["data"][0]
 
 
+def image_bounds(w, h, K4, dist5):
+    """Frame::ComputeImageBounds (include/orbslam_hip.h::orbt_image_bounds; reference src/Frame.cc:357-385): {min_x, max_x, min_y, max_y}
+    float32 of a w x h image under the distortion dist5 = (k1, k2, p1, p2, k3) - the `bounds` of every track_* call of that camera."""
+    L = _lib.load()
+    K4 = _c(K4, np.float32); d = _c(dist5, np.float32)
+    assert K4.size == 4 and d.size == 5
+    out = np.zeros(4, np.float32)
+    _lib.check(L.orbt_image_bounds(int(w), int(h), _addr(K4), _addr(d), _addr(out)), "orbt_image_bounds")
+    return out
+
+
+def set_distortion(extractor, dist5):
+    """orbt_set_distortion: every later track_* call of THIS thread that extracts a frame with `extractor` undistorts its keypoints with
+    dist5 = (k1, k2, p1, p2, k3) before the grid is built (Frame::UndistortKeyPoints).  None, or k1 == 0: no distortion (the default).
+    Set the coefficients of an extractor through THIS function, not through the library's orbt_set_distortion on extractor._h:
+    track_with_motion_model asks the library for kps_undistorted only for extractors that got coefficients here (for all others it
+    returns the raw coordinates as they lie in kps, without a call), so coefficients set behind its back would leave kps_undistorted raw.
+    A call that goes on with a resident frame (track_local_map, image=None) after the coefficients changed is refused."""
+    L = _lib.load()
+    if dist5 is None:
+        _lib.check(L.orbt_set_distortion(extractor._h, None), "orbt_set_distortion")
+        return
+    d = _c(dist5, np.float32)
+    assert d.size == 5
+    _lib.check(L.orbt_set_distortion(extractor._h, _addr(d)), "orbt_set_distortion")
+    # Never cleared: the coefficients are per THREAD in the library, so another thread may still hold some when this one drops its own.
+    # An extractor that never had any takes track_with_motion_model's shortcut (the raw coordinates as a view of kps, no call).
+    extractor._had_distortion = True
+
+
+def _last_undistorted(L, extractor, cap):
+    """undistort_keypoints_[i].pt of the frame the call before produced (orbt_last_undistorted_keypoints): (n, 2) float32"""
+    und = np.zeros((cap, 2), np.float32); n = C.c_int(0)
+    _lib.check(L.orbt_last_undistorted_keypoints(extractor._h, _addr(und), cap, C.byref(n)), "orbt_last_undistorted_keypoints")
+    return und[:n.value]
+
+
 def track_with_motion_model(extractor, image, K4, bounds, Tcw_pred, last_Xw, last_desc, last_octave, last_angle, last_valid, th=15.0,
                             check_ori=True, copy=True):
     """extractor: ORBextractor; image (H, W) uint8; Tcw_pred (3 or 4, 4); the last frame's per-feature arrays (see the header).
-    Returns dict(kps, desc, match, owner, outlier, pose7, nmatches, n_inliers, n_correspondences, greedy_rounds).  copy=True (the
+    Returns dict(kps, kps_undistorted, desc, match, owner, outlier, pose7, nmatches, n_inliers, n_correspondences, greedy_rounds); kps
+    are the raw keypoints, kps_undistorted (n, 2) float32 their undistorted coordinates (set_distortion; the raw ones without).  copy=True (the
     default) returns private arrays.  copy=False is for the latency-critical caller: the arrays are then READ-ONLY VIEWS of two
     alternating buffer sets kept with the extractor - frame N's arrays are overwritten by frame N + 2 - so anything kept longer
     (keyframe bookkeeping) must be copied by the caller.  Calls on one extractor are serialised by a lock kept with it."""
@@ -64,9 +102,10 @@ def _track_locked(L, extractor, img, w, h, K4, bounds, T, X, D, O, A, V, n, th, 
         nq = max(n, 1, S["nq"] if S else 0)
         def mk():
             b = dict(kps=np.zeros(cap, KP_DTYPE), desc=np.zeros((cap, 32), np.uint8), match=np.full(nq, -1, np.int32),
-                     owner=np.full(cap, -1, np.int32), outl=np.zeros(cap, np.uint8), res=TrackResult())
+                     owner=np.full(cap, -1, np.int32), outl=np.zeros(cap, np.uint8), res=TrackResult(), und=np.zeros((cap, 2), np.float32), nund=C.c_int(0))
             b["p"] = tuple(_addr(b[k]) for k in ("kps", "desc", "match", "owner", "outl"))
-            b["pres"] = C.byref(b["res"])
+            b["pres"] = C.byref(b["res"]); b["pund"] = _addr(b["und"]); b["pnund"] = C.byref(b["nund"])
+            b["raw_xy"] = np.ndarray((cap, 2), np.float32, b["kps"], 0, (b["kps"].itemsize, 4))      # {x, y} of the keypoint records in place
             return b
         S = dict(cap=cap, nq=nq, sets=(mk(), mk()), turn=0)
         extractor._track_bufs = S
@@ -77,11 +116,15 @@ def _track_locked(L, extractor, img, w, h, K4, bounds, T, X, D, O, A, V, n, th, 
     _lib.check(L.orbt_track_with_motion_model(extractor._h, _addr(img), w, h, img.strides[0], _addr(K4), _addr(bounds), _addr(T), _addr(X),
                                               _addr(D), _addr(O), _addr(A), _addr(V), n, float(th), int(bool(check_ori)), pk, pd, cap, pm, po, pl,
                                               B["pres"]), "orbt_track_with_motion_model")
+    und = B["raw_xy"]                                          # without distortion undistort_keypoints_ ARE keypoints_ (src/Frame.cc:330-333)
+    if getattr(extractor, "_had_distortion", False):
+        _lib.check(L.orbt_last_undistorted_keypoints(extractor._h, B["pund"], cap, B["pnund"]), "orbt_last_undistorted_keypoints")
+        und = B["und"]
     k = res.n_keypoints
-    out = dict(kps=B["kps"][:k], desc=B["desc"][:k], match=B["match"][:n], owner=B["owner"][:k], outlier=B["outl"][:k].view(np.bool_),
+    out = dict(kps=B["kps"][:k], kps_undistorted=und[:k], desc=B["desc"][:k], match=B["match"][:n], owner=B["owner"][:k], outlier=B["outl"][:k].view(np.bool_),
                pose7=np.array(res.pose7[:], np.float64), nmatches=res.nmatches, n_inliers=res.n_inliers,
                n_correspondences=res.n_correspondences, greedy_rounds=res.greedy_rounds)
-    for key in ("kps", "desc", "match", "owner", "outlier"):
+    for key in ("kps", "kps_undistorted", "desc", "match", "owner", "outlier"):
         if copy:
             out[key] = out[key].copy()
         else:
@@ -115,7 +158,7 @@ def track_local_map(extractor, K4, bounds, Tcw, log_scale_factor, mp_Xw, mp_norm
 def track_reference_keyframe(extractor, vocabulary, image, K4, bounds, Tcw_last, kf_desc, kf_valid, kf_angle, kf_Xw, kf_fv, nnratio=0.7, check_ori=True):
     """Tracking::TrackReferenceKeyFrame's data-parallel core (include/orbslam_hip.h::orbt_track_reference_keyframe; reference
     src/Tracking.cc:566-615).  image None: the frame of the last orbt_* call of this thread.  kf_fv = (node ids, offsets, indices).
-    Returns dict(kps, desc (None without image), bow=(words, values), fv=(nodes, offsets, indices), match, owner, outlier, pose7, ...)."""
+    Returns dict(kps, kps_undistorted, desc (None without image), bow=(words, values), fv=(nodes, offsets, indices), match, owner, outlier, pose7, ...)."""
     L = _lib.load()
     K4 = _c(K4, np.float32); bounds = _c(bounds, np.float32)
     T = np.ascontiguousarray(np.asarray(Tcw_last, np.float64).reshape(-1)[:12])
@@ -139,8 +182,9 @@ def track_reference_keyframe(extractor, vocabulary, image, K4, bounds, Tcw_last,
                                                    _addr(fn), _addr(fo), _addr(fi), len(fn), float(nnratio), int(bool(check_ori)), _addr(kps), _addr(desc), cap,
                                                    _addr(bw), _addr(bv), C.byref(nw), _addr(on), _addr(oo), _addr(oi), C.byref(nf), _addr(match), _addr(owner), _addr(outl),
                                                    C.byref(res)), "orbt_track_reference_keyframe")
+        und = _last_undistorted(L, extractor, cap) if img is not None else None
     k = res.n_keypoints
-    return dict(kps=kps[:k] if img is not None else None, desc=desc[:k] if img is not None else None, bow=(bw[:nw.value], bv[:nw.value]),
+    return dict(kps=kps[:k] if img is not None else None, kps_undistorted=und, desc=desc[:k] if img is not None else None, bow=(bw[:nw.value], bv[:nw.value]),
                 fv=(on[:nf.value], oo[:nf.value + 1], oi[:oo[nf.value]]), match=match[:n], owner=owner[:k], outlier=outl[:k].view(np.bool_),
                 pose7=np.array(res.pose7[:], np.float64), nmatches=res.nmatches, n_inliers=res.n_inliers, n_correspondences=res.n_correspondences, n_keypoints=k)
 
@@ -160,7 +204,7 @@ def relocalization_search_by_bow(extractor, vocabulary, image, K4, bounds, candi
     """Tracking::Relocalization, first stage (include/orbslam_hip.h::orbt_relocalization_search_by_bow; reference src/Tracking.cc:979-1029):
     ComputeBoW of the frame + SearchByBoW(keyframe, frame) for every candidate keyframe in one call.  candidates: dicts(desc[n,32],
     valid[n], angle[n], fv=(nodes, offsets, indices)).  image None: the frame of the last orbt_* call of this thread.
-    Returns dict(kps, desc (None without image), bow, fv, owner[n_cand, n_keypoints], nmatches[n_cand])."""
+    Returns dict(kps, kps_undistorted, desc (None without image), bow, fv, owner[n_cand, n_keypoints], nmatches[n_cand])."""
     import contextlib
     L = _lib.load()
     K4 = _c(K4, np.float32); bounds = _c(bounds, np.float32)
@@ -190,6 +234,7 @@ def relocalization_search_by_bow(extractor, vocabulary, image, K4, bounds, candi
         _lib.check(L.orbt_relocalization_search_by_bow(extractor._h, vocabulary._h, ip, w, h, st, _addr(K4), _addr(bounds), C.cast(cs, C.c_void_p), nc, float(nnratio),
                                                        int(bool(check_ori)), _addr(kps), _addr(desc), cap, _addr(bw), _addr(bv), C.byref(nw), _addr(on), _addr(oo), _addr(oi),
                                                        C.byref(nf), _addr(owner), _addr(nm), C.byref(nk)), "orbt_relocalization_search_by_bow")
+        und = _last_undistorted(L, extractor, cap) if img is not None else None
     k = nk.value
-    return dict(kps=kps[:k] if img is not None else None, desc=desc[:k] if img is not None else None, bow=(bw[:nw.value], bv[:nw.value]),
+    return dict(kps=kps[:k] if img is not None else None, kps_undistorted=und, desc=desc[:k] if img is not None else None, bow=(bw[:nw.value], bv[:nw.value]),
                 fv=(on[:nf.value], oo[:nf.value + 1], oi[:oo[nf.value]]), owner=owner[:nc, :k], nmatches=nm[:nc], n_keypoints=k)

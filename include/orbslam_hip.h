@@ -773,19 +773,21 @@ int orbt_sim3_iterate_batch_device(int n_candidates, const double* d_X1c, const 
 int orbt_sim3_iterate_workspace(int n_candidates, int n_total, int iterations, size_t* bytes);
 
 /* ---- the per-frame Tracking step with the motion model, device-resident (src/Tracking.cc:616-646): Frame construction
- * (ORBextractor::operator(), AssignFeaturesToGrid; zero distortion: the undistorted keypoints are the raw ones, as for the
- * KITTI configurations), ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) (src/ORBmatcher.cc:1161-1271,
+ * (ORBextractor::operator(), UndistortKeyPoints with the coefficients orbt_set_distortion attached to ctx - none by default, as for
+ * the KITTI configurations: the undistorted keypoints are then the raw ones -, AssignFeaturesToGrid), ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) (src/ORBmatcher.cc:1161-1271,
  * monocular) and CeresOptimizer::PoseOptimization (src/CeresOptimizer.cc:275-342) in ONE call: the image and one packed block
  * go up, the kernels of all three stages run back to back on one stream (the greedy, order-dependent pass of the search as a
  * parallel fixpoint on the device, csrc/orb_track.hip), one block comes down.
- *   in   img: CV_8UC1 w x h; K4 = {fx, fy, cx, cy}; bounds = {min_x, max_x, min_y, max_y}; Tcw_pred = current_frame_.Tcw_
+ *   in   img: CV_8UC1 w x h; K4 = {fx, fy, cx, cy}; bounds = {min_x, max_x, min_y, max_y} from orbt_image_bounds with the SAME
+ *        coefficients as orbt_set_distortion got (the grid and the projection test use them); Tcw_pred = current_frame_.Tcw_
  *        after SetPose(velocity_ * last_frame_.Tcw_), row-major 3x4 (or the first 12 of a 4x4); per last-frame feature i
  *        (n_last <= 4096): last_Xw = map point position, last_desc = its descriptor (MapPoint::GetDescriptor), last_octave =
  *        LastFrame.keypoints_[i].octave, last_angle = LastFrame.undistort_keypoints_[i].angle, last_valid = 0 (no map point,
  *        or is_outliers_[i]), 1 (map point with Observations() > 0) or 3 (without: it is matched but does not close the
  *        feature for later points, :1220-1221); th = 15 (the caller repeats the call with 2 * th when nmatches < 20,
  *        src/Tracking.cc:635-641); check_ori = mbCheckOrientation.
- *   out  kps / desc [cap >= orbx_max_keypoints(ctx)]: the frame's keypoints and descriptors; match[n_last]: index of the
+ *   out  kps / desc [cap >= orbx_max_keypoints(ctx)]: the frame's RAW keypoints (keypoints_) and descriptors - the undistorted
+ *        ones (undistort_keypoints_[i].pt) are orbt_last_undistorted_keypoints' -; match[n_last]: index of the
  *        current feature matched to last-frame feature i, -1 none, -2 - index removed by the rotation check; owner[n_kp]:
  *        which last-frame feature's map point CurrentFrame.map_points_[f] holds, or -1; outlier[n_kp] = is_outliers_ after
  *        PoseOptimization; res: counts, the optimised pose [tx, ty, tz, qx, qy, qz, qw] (the predicted one when fewer than
@@ -842,6 +844,28 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
                                   orbx_keypoint* kps, uint8_t* desc, int cap, uint32_t* bow_word, double* bow_value, int* n_words,
                                   uint32_t* fv_node, uint32_t* fv_off, uint32_t* fv_idx, int* n_fv_nodes, int32_t* match_kf,
                                   int32_t* slot_owner, uint8_t* outlier, orbt_result* res);
+
+/* ---- lens distortion in the device-resident Tracking calls (configs/EuRoC.yaml, TUM1.yaml, TUM2.yaml).  Once per calibration:
+ * orbt_image_bounds + orbt_set_distortion; per frame: the unchanged orbt_* call, then orbt_last_undistorted_keypoints for
+ * undistort_keypoints_.  The undistortion is cv::undistortPoints' five fixed-point iterations in double (OpenCV 2.4 / 3.2), the
+ * same arithmetic as orbm_undistort_keypoints, bit for bit.
+ *
+ * Frame::ComputeImageBounds (src/Frame.cc:357-385), host arithmetic: bounds4 = {min_x, max_x, min_y, max_y}.  dist5 = (k1, k2, p1, p2,
+ * k3); with dist5[0] == 0 (the reference tests k1 alone) {0, w, 0, h}, otherwise min / max of the four undistorted corners as
+ * :374-377 pair them.  ORBHIP_EINVAL for NULL, w <= 0, h <= 0 or non-finite values.                                            */
+int orbt_image_bounds(int w, int h, const float* K4, const float* dist5, float* bounds4);
+/* Frame::UndistortKeyPoints (src/Frame.cc:329-355) inside every later orbt_* call of the CALLING THREAD that extracts a frame with
+ * ctx: the resident frame's records, its grid, the window search, the rotation check and PoseOptimization's observations then use
+ * the undistorted coordinates; a keypoint that leaves the grid (PosInGrid false) is in no cell but keeps its slot.  NULL or
+ * dist5[0] == 0: none (the default; :330-333).  The state belongs to the thread, not to the context: every thread that extracts
+ * with ctx sets it, and a context created later at the same address starts without.  ORBHIP_EINVAL for a NULL context or
+ * non-finite coefficients (the state is unchanged then).  The resident frame remembers the coefficients that built it: a call that
+ * goes on with it (orbt_track_local_map, img == NULL) after they changed returns ORBHIP_EINVAL - extract a frame first.           */
+int orbt_set_distortion(orbx_ctx* ctx, const float* dist5);
+/* undistort_keypoints_[i].pt = xy[2 i], xy[2 i + 1] of the frame the calling thread's last extracting orbt_* call produced with ctx
+ * (a host copy of what that call downloaded: no device work); the raw coordinates without distortion.  *n = the frame's keypoint
+ * count.  ORBHIP_EINVAL without such a frame, ORBHIP_ECAP (only *n written) when cap < *n.                                     */
+int orbt_last_undistorted_keypoints(orbx_ctx* ctx, float* xy, int cap, int* n);
 
 /* Host wall time (ms) of the calling thread's most recent orbt_* call, measured inside the library (entry to return): the latency
  * of a Tracking step as the reference's C++ caller would see it, free of what a scripting host adds around the call.       */
