@@ -146,7 +146,7 @@ struct HostBA {
     ar_off = 0; ar_cap = bytes;
     return rc;
   }
-  static size_t arena_need(size_t count, size_t elem) { return (count * elem + 255) & ~(size_t)255; }
+  static size_t arena_need(size_t count, size_t elem) { return align256(count * elem); }
   template <typename T> T* arena_host(size_t count, int* rc) {
     const size_t need = arena_need(std::max<size_t>(count, 1), sizeof(T));
     if (ar_off + need > ar_cap) { if (!*rc) { set_error("internal: upload arena too small"); *rc = ORBHIP_EINVAL; } return nullptr; }
@@ -704,11 +704,10 @@ static int ba_solve_batch_impl(const BaInputs* in, int nprob, const ba_options* 
       } else B.g_npad_2l = std::max(B.g_npad_2l, D.npad);
     }
     // the batch's output block: one slice per problem
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     B.out_off.assign(nprob, 0); B.out_bytes = 0;
     for (int p = 0; p < nprob; p++) {
       B.out_off[p] = B.out_bytes;
-      B.out_bytes += al(sizeof(BaState)) + al(7 * (size_t)in[p].ncam * sizeof(double)) + al(3 * (size_t)in[p].npts * sizeof(double)) + al((size_t)std::max(in[p].nobs, 1));
+      B.out_bytes += align256(sizeof(BaState)) + align256(7 * (size_t)in[p].ncam * sizeof(double)) + align256(3 * (size_t)in[p].npts * sizeof(double)) + align256((size_t)std::max(in[p].nobs, 1));
     }
     B.out_d = H.alloc<unsigned char>(B.out_bytes, &rc); B.out_h = H.pinned<unsigned char>(B.out_bytes, &rc);
     if (rc) return rc;
@@ -966,13 +965,12 @@ static int ba_solve_batch_impl(const BaInputs* in, int nprob, const ba_options* 
   ORBHIP_CHECK_HIP(hipMemcpyAsync(B.out_h, B.out_d, B.out_bytes, hipMemcpyDeviceToHost, s));
   ORBHIP_CHECK_HIP(hipStreamSynchronize(s));
   {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     for (int p = 0; p < nprob; p++) {
       const unsigned char* o = B.out_h + B.out_off[p];
-      std::memcpy(&fin[p], o, sizeof(BaState)); o += al(sizeof(BaState));
-      std::memcpy(in[p].poses7, o, 7 * (size_t)in[p].ncam * sizeof(double)); o += al(7 * (size_t)in[p].ncam * sizeof(double));
+      std::memcpy(&fin[p], o, sizeof(BaState)); o += align256(sizeof(BaState));
+      std::memcpy(in[p].poses7, o, 7 * (size_t)in[p].ncam * sizeof(double)); o += align256(7 * (size_t)in[p].ncam * sizeof(double));
       if (in[p].npts) std::memcpy(in[p].pts3, o, 3 * (size_t)in[p].npts * sizeof(double));
-      o += al(3 * (size_t)in[p].npts * sizeof(double));
+      o += align256(3 * (size_t)in[p].npts * sizeof(double));
       if (classify && in[p].nobs) std::memcpy(P[p].h_rob, o, in[p].nobs);
     }
   }

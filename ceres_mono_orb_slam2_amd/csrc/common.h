@@ -53,6 +53,15 @@ inline int use_default_device() {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// One block carved into pieces that each start on a 256-byte boundary (what hipMalloc guarantees, enough for any vector access):
+// take() hands out the piece's offset, `total` is the size of the block so far.  Every packed upload, output block and workspace
+// size in the library is laid out by this rule, so that a size query and the call it sizes cannot drift apart.
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Carve {
+  size_t total = 0;
+  size_t take(size_t bytes) { const size_t at = total; total = align256(at + bytes); return at; }
+};
+
 // Copies between PINNED host staging and device memory are done BY A KERNEL on the call's stream (k_ws_copy, capi_common.hip: pinned
 // host memory is mapped into the device's address space), not by hipMemcpyAsync.  Measured (tools/scratch: rocprofv3 --hip-trace of
 // tests/test_gpu_concurrency.py): with two or three host threads issuing asynchronous copies, a hipMemcpyAsync of a few hundred
@@ -170,13 +179,11 @@ struct ThreadWs {
   }
   // several host arrays in ONE pinned block and ONE asynchronous copy (a copy costs microseconds of fixed overhead, the
   // per-frame calls move a few hundred kilobytes in ten pieces): add() the pieces, commit(), then dev<T>(piece)
-  struct Pack {
+  struct Pack : Carve {
     struct Piece { const void* src; size_t bytes, off; };
-    std::vector<Piece> pieces; size_t total = 0; uint8_t* dbase = nullptr;
+    std::vector<Piece> pieces; uint8_t* dbase = nullptr;
     int add(const void* src, size_t bytes) {
-      const size_t off = total;
-      pieces.push_back({src, bytes, off});
-      total = (off + bytes + 255) & ~(size_t)255;
+      pieces.push_back({src, bytes, take(bytes)});
       return (int)pieces.size() - 1;
     }
     template <typename T> T* dev(int piece) const { return piece < 0 ? nullptr : (T*)(dbase + pieces[piece].off); }

@@ -549,13 +549,12 @@ struct InitWs {
 };
 static InitWs init_ws_layout(int npairs, int n1_total, int n2_total, int iterations) {
   InitWs w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+  Carve blk;
   const size_t P = (size_t)npairs, N1 = (size_t)n1_total, N2 = (size_t)n2_total, I = (size_t)iterations;
-  w.pair = take(sizeof(InitPair) * P); w.mlist = take(8 * N1); w.pn1 = take(8 * N1); w.pn2 = take(8 * N2);
-  w.hyp = take(27 * 8 * P * I); w.score = take(2 * 4 * P * I); w.inl = take(2 * N1);
-  w.rt_p = take(8 * 24 * N1); w.rt_cos = take(8 * 4 * N1); w.rt_flag = take(8 * N1);
-  w.total = o;
+  w.pair = blk.take(sizeof(InitPair) * P); w.mlist = blk.take(8 * N1); w.pn1 = blk.take(8 * N1); w.pn2 = blk.take(8 * N2);
+  w.hyp = blk.take(27 * 8 * P * I); w.score = blk.take(2 * 4 * P * I); w.inl = blk.take(2 * N1);
+  w.rt_p = blk.take(8 * 24 * N1); w.rt_cos = blk.take(8 * 4 * N1); w.rt_flag = blk.take(8 * N1);
+  w.total = blk.total;
   return w;
 }
 
@@ -631,18 +630,17 @@ int orbt_initialize(const float* kps1, int n1, const float* kps2, int n2, const 
   const int pO1 = in.add(off1, 8), pO2 = in.add(off2, 8), pK = in.add(K4, 16), pS = in.add(ransac_sets, 32 * (size_t)iterations);
   const int pP = in.add(P3D, 24 * (size_t)n1);                // (the device copy starts as the caller's rows: untouched rows keep them)
   // outputs in one block: [R21 | t21 | triangulated | report]
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oR = take(72), oT = take(24), oG = take((size_t)n1), oRep = take(sizeof(orbt_init_report));
+  Carve blk;
+  const size_t oR = blk.take(72), oT = blk.take(24), oG = blk.take((size_t)n1), oRep = blk.take(sizeof(orbt_init_report));
   const InitWs lay = init_ws_layout(1, n1, n2, iterations);
-  uint8_t* dblk = W.d<uint8_t>(o, &rc);
+  uint8_t* dblk = W.d<uint8_t>(blk.total, &rc);
   uint8_t* dws = W.d<uint8_t>(lay.total, &rc);
   if (rc || (rc = W.commit(in))) return rc;
   double* dP = in.dev<double>(pP);
   if ((rc = orbt_initialize_batch_device(1, in.dev<float>(pK1), in.dev<int32_t>(pO1), n1, in.dev<float>(pK2), in.dev<int32_t>(pO2), n2, in.dev<int32_t>(pM),
                                          in.dev<float>(pK), sigma, iterations, in.dev<int32_t>(pS), (double*)(dblk + oR), (double*)(dblk + oT), dP,
                                          dblk + oG, (orbt_init_report*)(dblk + oRep), dws, W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, o, &rc);
+  const uint8_t* hb = W.down(dblk, blk.total, &rc);
   const double* hP = W.down(dP, 3 * (size_t)n1, &rc);
   const bool want_trace = trace && (trace->H21 || trace->H12 || trace->F21 || trace->score_h || trace->score_f || trace->motion_R || trace->motion_t ||
                                     trace->inliers_h || trace->inliers_f);

@@ -226,11 +226,11 @@ __global__ __launch_bounds__(KC_WG) void k_cull_export(CullArgs a) {
 // workspace sections, each rounded up to 256 bytes
 struct CullWs { size_t cnt, spt, sobs, snext, ohead, dead, bad, ncur, claim, total; };
 static CullWs cull_workspace(int nslots, int npts, int nobs) {
-  CullWs w; size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o = (o + 4 * n + 255) & ~(size_t)255; return at; };
-  w.cnt = take(nslots); w.spt = take(nslots); w.sobs = take(nslots); w.snext = take(nslots);
-  w.ohead = take(nobs); w.dead = take(nobs); w.bad = take(npts); w.ncur = take(npts); w.claim = take(npts);
-  w.total = o > 0 ? o : 256;
+  CullWs w; Carve ws;
+  const size_t slots = 4 * (size_t)nslots, obs = 4 * (size_t)nobs, pts = 4 * (size_t)npts;      // (every section holds 4-byte entries)
+  w.cnt = ws.take(slots); w.spt = ws.take(slots); w.sobs = ws.take(slots); w.snext = ws.take(slots);
+  w.ohead = ws.take(obs); w.dead = ws.take(obs); w.bad = ws.take(pts); w.ncur = ws.take(pts); w.claim = ws.take(pts);
+  w.total = ws.total > 0 ? ws.total : 256;
   return w;
 }
 
@@ -334,10 +334,10 @@ int orbl_keyframe_culling(int ncand, const int32_t* cand_kf, const uint8_t* cand
   const int pOK = nobs ? in.add(obs_kf, 4 * (size_t)nobs) : -1, pOL = nobs ? in.add(obs_level, 4 * (size_t)nobs) : -1;
   const int pB = npts && pt_bad ? in.add(pt_bad, (size_t)npts) : -1, pN = npts && pt_nobs ? in.add(pt_nobs, 4 * (size_t)npts) : -1;
   // outputs in one block: [culled | n_redundant | n_map_points | pt_bad_out | pt_nobs_out | obs_erased]
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oC = take((size_t)ncand), oR = take(4 * (size_t)ncand), oM = take(4 * (size_t)ncand), oB = take((size_t)npts), oN = take(4 * (size_t)npts),
-               oE = take((size_t)nobs);
+  Carve out;
+  const size_t oC = out.take((size_t)ncand), oR = out.take(4 * (size_t)ncand), oM = out.take(4 * (size_t)ncand), oB = out.take((size_t)npts), oN = out.take(4 * (size_t)npts),
+               oE = out.take((size_t)nobs);
+  const size_t o = out.total;
   uint8_t* dblk = W.d<uint8_t>(std::max<size_t>(o, 256), &rc);
   void* dws = W.d<uint8_t>(cull_workspace(nslots, npts, nobs).total, &rc);
   if (rc || (rc = W.commit(in))) return rc;

@@ -263,7 +263,7 @@ namespace orbhip {
 struct KfdbLayout {
   size_t count, minw, score, scored, ord_slot, ord_score, acc, best, flag, info, total;     // (info: the host entries' own orbv_db_query_info)
   KfdbLayout(int S, int Q) {
-    const size_t pair = ((size_t)S * Q * 4 + 255) & ~(size_t)255, one = ((size_t)S * 4 + 255) & ~(size_t)255;
+    const size_t pair = align256((size_t)S * Q * 4), one = align256((size_t)S * 4);
     size_t o = 0;
     count = o; o += pair; minw = o; o += pair; score = o; o += pair; scored = o; o += pair;
     ord_slot = o; o += one; ord_score = o; o += one; acc = o; o += one; best = o; o += one; flag = o; o += one;
@@ -408,15 +408,13 @@ static int kfdb_host_query(orbv_db* c, int kind, int stage, const uint32_t* word
   const KfdbLayout L(S, 1);
   int rc = 0;
   if ((rc = c->ws.ensure(L.total))) return rc;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  const size_t i_off = o; o = al(o + 8); const size_t i_w = o; o = al(o + (size_t)n * 4); const size_t i_v = o; o = al(o + (size_t)n * 8);
-  const size_t i_coff = o; o = al(o + 8); const size_t i_conn = o; o = al(o + (size_t)n_conn * 4); const size_t i_ms = o; o = al(o + 4);
-  const size_t i_rows = o; o = al(o + (size_t)n_rows * orbhip::KFDB_MAX_NEIGH * 4); const size_t i_rn = o; o = al(o + (size_t)n_rows * 4);
-  const size_t in_bytes = o;
+  Carve qb;                                                    // the query block: inputs, then the candidate list
+  const size_t i_off = qb.take(8), i_w = qb.take((size_t)n * 4), i_v = qb.take((size_t)n * 8), i_coff = qb.take(8), i_conn = qb.take((size_t)n_conn * 4), i_ms = qb.take(4);
+  const size_t i_rows = qb.take((size_t)n_rows * orbhip::KFDB_MAX_NEIGH * 4), i_rn = qb.take((size_t)n_rows * 4);
+  const size_t in_bytes = qb.total;
   const int ncand = std::max(std::min(cap, S), 0), nkept = want_kept ? S : 0;
-  st->o_cand = o; o = al(o + (size_t)std::max(ncand, 1) * 4);
-  const size_t dev_total = o;
+  st->o_cand = qb.take((size_t)std::max(ncand, 1) * 4);
+  const size_t dev_total = qb.total;
   if ((rc = c->qin.ensure(dev_total)) || (rc = c->hin.ensure(in_bytes))) return rc;
   uint8_t* h = (uint8_t*)c->hin.p; uint8_t* d = c->qin.as<uint8_t>();
   const int qo[2] = {0, n}, co[2] = {0, n_conn};
@@ -429,11 +427,10 @@ static int kfdb_host_query(orbv_db* c, int kind, int stage, const uint32_t* word
   if ((rc = kfdb_enqueue(c, kind, 1, stage, (int*)(d + i_off), (uint32_t*)(d + i_w), (double*)(d + i_v), (int*)(d + i_coff), (int*)(d + i_conn), (float*)(d + i_ms), qid, S,
                          n_rows || stage == 2 ? (int*)(d + i_rows) : nullptr, (int*)(d + i_rn), c->ws.as<uint8_t>(), st->info, st->cand, cap, c->s))) return rc;
   // outputs: info, candidates and (trace / begin) the kept list with its scores, one pinned block
-  size_t ho = 0;
-  const size_t h_info = ho; ho = al(ho + sizeof(orbv_db_query_info)); const size_t h_cand = ho; ho = al(ho + (size_t)ncand * 4);
-  const size_t h_slot = ho; ho = al(ho + (size_t)nkept * 4); const size_t h_score = ho; ho = al(ho + (size_t)nkept * 4);
-  const size_t h_acc = ho; ho = al(ho + (size_t)nkept * 4); const size_t h_best = ho; ho = al(ho + (size_t)nkept * 4);
-  if ((rc = c->hout.ensure(ho))) return rc;
+  Carve hc;
+  const size_t h_info = hc.take(sizeof(orbv_db_query_info)), h_cand = hc.take((size_t)ncand * 4), h_slot = hc.take((size_t)nkept * 4), h_score = hc.take((size_t)nkept * 4);
+  const size_t h_acc = hc.take((size_t)nkept * 4), h_best = hc.take((size_t)nkept * 4);
+  if ((rc = c->hout.ensure(hc.total))) return rc;
   uint8_t* hb = (uint8_t*)c->hout.p;
   hipError_t e = ws_copy(hb + h_info, st->info, sizeof(orbv_db_query_info), hipMemcpyDeviceToHost, c->s);
   if (e == hipSuccess && ncand && stage != 1) e = ws_copy(hb + h_cand, st->cand, (size_t)ncand * 4, hipMemcpyDeviceToHost, c->s);
@@ -603,8 +600,8 @@ int orbv_db_min_score(orbv_db* c, const uint32_t* words, const double* values, i
     ORBHIP_REQUIRE(slots[i] >= 0 && slots[i] < (int)c->slots.size() && c->slots[slots[i]].seq != 0, ORBHIP_EINVAL, "slot is not in the database");
   if (n_slots == 0) { *min_score = 1.0f; return 0; }
   if (int rc = kfdb_device(c)) return rc;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_w = 0, o_v = al((size_t)n * 4), o_l = al(o_v + (size_t)n * 8), in_bytes = al(o_l + (size_t)n_slots * 4), o_out = in_bytes;
+  Carve qb;
+  const size_t o_w = qb.take((size_t)n * 4), o_v = qb.take((size_t)n * 8), o_l = qb.take((size_t)n_slots * 4), in_bytes = qb.total, o_out = in_bytes;
   int rc = 0;
   if ((rc = c->qin.ensure(o_out + (size_t)n_slots * 4)) || (rc = c->hin.ensure(in_bytes)) || (rc = c->hout.ensure((size_t)n_slots * 4))) return rc;
   uint8_t* h = (uint8_t*)c->hin.p; uint8_t* d = c->qin.as<uint8_t>();

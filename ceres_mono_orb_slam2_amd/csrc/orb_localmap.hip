@@ -276,10 +276,9 @@ int orbl_create_new_map_points(const float* kps1, const uint8_t* desc1, const ui
   }
   const int pN = in.add(h_nb.data(), sizeof(LmNb) * (size_t)n_nb);
   // outputs in one block: [state (2 ints) | match12 | ok | x3D]
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oState = take(8), oM = take(4 * (size_t)n_nb * n1), oOk = take((size_t)n_nb * n1), oX = take(24 * (size_t)n_nb * n1);
-  uint8_t* dblk = W.d<uint8_t>(o, &rc);
+  Carve blk;
+  const size_t oState = blk.take(8), oM = blk.take(4 * (size_t)n_nb * n1), oOk = blk.take((size_t)n_nb * n1), oX = blk.take(24 * (size_t)n_nb * n1);
+  uint8_t* dblk = W.d<uint8_t>(blk.total, &rc);
   uint32_t* d_node_of = W.d<uint32_t>((size_t)n1, &rc);
   unsigned char* h_stop = W.h<unsigned char>(16, &rc);            // pinned, device-visible mirror of the caller's flag
   if (rc || (rc = W.commit(in))) return rc;
@@ -299,7 +298,7 @@ int orbl_create_new_map_points(const float* kps1, const uint8_t* desc1, const ui
     if (stop && *stop) *(volatile unsigned char*)h_stop = 1;     // (between the enqueues too: the gates of the neighbours behind see it)
   }
   if (hipGetLastError() != hipSuccess) { if (done) (void)hipEventDestroy(done); set_error("orbl_create_new_map_points: a launch failed"); return ORBHIP_ENODEV; }
-  const uint8_t* hb = W.down(dblk, o, &rc);
+  const uint8_t* hb = W.down(dblk, blk.total, &rc);
   if (rc) { if (done) (void)hipEventDestroy(done); return rc; }
   if (stop) {                                                    // forward the caller's flag while the chain runs (the kernels read the pinned mirror)
     (void)hipEventRecord(done, W.s);

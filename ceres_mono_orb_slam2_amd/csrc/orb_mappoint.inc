@@ -328,16 +328,15 @@ int orbl_update_map_points(int npts, const int32_t* obs_off, const double* X, co
   const int pX = nd ? in.add(X, 24 * (size_t)npts) : -1, pR = nd ? in.add(ref_kf, 4 * (size_t)npts) : -1, pL = nd ? in.add(ref_level, 4 * (size_t)npts) : -1;
   const int pF = nd ? in.add(obs_kf, 4 * (size_t)nobs) : -1, pC = nd ? in.add(kf_center, 24 * (size_t)nkf) : -1, pS = nd ? in.add(scale_factors, 4 * (size_t)n_levels) : -1;
   // outputs in one block: [best_obs | desc_out | normal | min_max | nd_written]
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oB = take(4 * (size_t)npts), oD = take(32 * (size_t)npts), oN = take(24 * (size_t)npts), oM = take(8 * (size_t)npts), oW = take((size_t)npts);
-  uint8_t* dblk = W.d<uint8_t>(o, &rc);
+  Carve out;
+  const size_t oB = out.take(4 * (size_t)npts), oD = out.take(32 * (size_t)npts), oN = out.take(24 * (size_t)npts), oM = out.take(8 * (size_t)npts), oW = out.take((size_t)npts);
+  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
   void* dws = W.d<uint8_t>(mp_workspace_bytes(npts), &rc);
   if (rc || (rc = W.commit(in))) return rc;
   if ((rc = orbl_update_map_points_device(npts, in.dev<int32_t>(pO), in.dev<double>(pX), in.dev<int32_t>(pR), in.dev<int32_t>(pL), in.dev<uint8_t>(pG), nobs,
                                           in.dev<int32_t>(pF), in.dev<uint8_t>(pD), in.dev<uint8_t>(pK), nkf, in.dev<double>(pC), in.dev<float>(pS), n_levels, what,
                                           (int32_t*)(dblk + oB), dblk + oD, (double*)(dblk + oN), (float*)(dblk + oM), dblk + oW, dws, W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, o, &rc);
+  const uint8_t* hb = W.down(dblk, out.total, &rc);
   if (rc || (rc = W.sync())) return rc;
   // only what the call wrote reaches the caller's buffers: unchanged points keep their bytes
   const int32_t* hbest = (const int32_t*)(hb + oB);

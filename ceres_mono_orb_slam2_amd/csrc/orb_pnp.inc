@@ -651,11 +651,10 @@ struct PnpWs {
 };
 static PnpWs pnp_ws_layout(int ncand, int n_total, int iterations) {
   PnpWs w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+  Carve blk;
   const size_t Cn = (size_t)ncand, N = (size_t)n_total, I = (size_t)iterations;
-  w.cand = take(sizeof(PnpCand) * Cn); w.hyp = take(16 * 8 * Cn * I); w.count = take(4 * Cn * I); w.ridx = take(4 * N); w.refit = take(14 * 8 * Cn * I);
-  w.total = o;
+  w.cand = blk.take(sizeof(PnpCand) * Cn); w.hyp = blk.take(16 * 8 * Cn * I); w.count = blk.take(4 * Cn * I); w.ridx = blk.take(4 * N); w.refit = blk.take(14 * 8 * Cn * I);
+  w.total = blk.total;
   return w;
 }
 

@@ -304,11 +304,10 @@ struct Sim3Ws {
 };
 static Sim3Ws sim3_ws_layout(int ncand, int n_total, int iterations) {
   Sim3Ws w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
+  Carve blk;
   const size_t Cn = (size_t)ncand, N = (size_t)n_total, I = (size_t)iterations;
-  w.cand = take(sizeof(Sim3Cand) * Cn); w.im1 = take(16 * N); w.im2 = take(16 * N); w.hyp = take(16 * 8 * Cn * I); w.count = take(4 * Cn * I);
-  w.total = o;
+  w.cand = blk.take(sizeof(Sim3Cand) * Cn); w.im1 = blk.take(16 * N); w.im2 = blk.take(16 * N); w.hyp = blk.take(16 * 8 * Cn * I); w.count = blk.take(4 * Cn * I);
+  w.total = blk.total;
   return w;
 }
 

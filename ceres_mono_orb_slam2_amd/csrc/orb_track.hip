@@ -1,5 +1,7 @@
 // ============================================================================
-// orb_track.hip -- the per-frame Tracking step with the motion model, device-resident from the image to the optimised pose
+// orb_track.hip -- the per-frame Tracking calls (motion model, local map, reference keyframe, relocalisation's SearchByBoW), device-
+// resident from the image to the optimised pose.  Their host halves are sequences of shared stages ("the stages ..." below: frame
+// build / publish, resident-frame check, window search, pose tail, BoW); the motion-model step is the one described here
 // (reference src/Tracking.cc:616-646: Frame construction - ORBextractor::operator(), AssignFeaturesToGrid -, then
 // ORBmatcher::SearchByProjection(current_frame_, last_frame_, th) src/ORBmatcher.cc:1161-1271 and
 // CeresOptimizer::PoseOptimization src/CeresOptimizer.cc:275-342).
@@ -1112,13 +1114,13 @@ namespace {
 // (FrameGridDev below) always did.
 struct TrkFrame {
   DevBuf blk, kps4; FrameGridDev grid;
-  size_t oKps = 0, oDesc = 0, oCnt = 0; int icap = 0, n_kp = 0, device = -1, nlevels = 0; float bounds[4] = {0, 0, 0, 0}; bool valid = false;
+  size_t oDesc = 0, oCnt = 0; int icap = 0, n_kp = 0, device = -1, nlevels = 0; bool valid = false;      // (oDesc, oCnt: the pieces inside blk later calls read)
   const orbx_ctx* producer = nullptr;      // the extractor that produced the resident frame: its level count / scale tables / capacity are the frame's
   unsigned long long producer_gen = 0;     // ... and its generation: a context destroyed and re-created at the same address is NOT that extractor
   bool made_by(const orbx_ctx* c) const { return producer == c && producer_gen == orbhip::orbx_ctx_generation(c); }
-  // lens distortion: the coefficients that built the frame (dist_on false: none), where k_trk_prepare<true> wrote the undistorted
-  // {x, y} inside blk, and the host's copy of undistort_keypoints_[i].pt from the producing call's download (orbt_last_undistorted_keypoints)
-  bool dist_on = false; float dist[5] = {0, 0, 0, 0, 0}; size_t oUnd = 0; std::vector<float> und_xy;
+  // lens distortion: the coefficients that built the frame (dist_on false: none) and the host's copy of undistort_keypoints_[i].pt from
+  // the producing call's download (orbt_last_undistorted_keypoints)
+  bool dist_on = false; float dist[5] = {0, 0, 0, 0, 0}; std::vector<float> und_xy;
 };
 thread_local TrkFrame g_trk_frame;
 
@@ -1136,18 +1138,11 @@ const float* trk_distortion_of(const orbx_ctx* c) {
   }
   return nullptr;
 }
-void trk_fill_distortion(TrkIn& I, const float* d) {
-  for (int k = 0; k < 5; k++) I.dist[k] = d ? (double)d[k] : 0.0;
-}
 // the coefficients `d` (nullptr: none) are the ones the resident frame was built with: a call that goes on with that frame (orbt_track_local_map,
 // img == NULL) after orbt_set_distortion changed them would mix two cameras - its bounds belong to the new coefficients, the grid to the old
 bool trk_same_distortion(const TrkFrame& TF, const float* d) {
   if (!d) return !TF.dist_on;
   return TF.dist_on && std::memcmp(TF.dist, d, sizeof(TF.dist)) == 0;
-}
-template <typename... A> void trk_prepare_launch(bool dist, hipStream_t s, A... a) {
-  if (dist) hipLaunchKernelGGL(k_trk_prepare<true>, dim3(1), dim3(1024), 0, s, a...);
-  else hipLaunchKernelGGL(k_trk_prepare<false>, dim3(1), dim3(1024), 0, s, a...);
 }
 // the producing call's downloaded block -> TF.und_xy (h_und NULL: no distortion, the raw coordinates)
 void trk_keep_undistorted(TrkFrame& TF, const float* d, const uint8_t* h_kps, const uint8_t* h_und, int n) {
@@ -1158,6 +1153,195 @@ void trk_keep_undistorted(TrkFrame& TF, const float* d, const uint8_t* h_kps, co
   const orbx_keypoint* kp = (const orbx_keypoint*)h_kps;
   for (int i = 0; i < n; i++) { TF.und_xy[2 * i] = kp[i].x; TF.und_xy[2 * i + 1] = kp[i].y; }
 }
+
+// ---- the stages the four Tracking calls are made of -------------------------------------------------------------------------------
+// Workspace slots (W.d<> / W.h<>) are served in request order and grow to the largest request they have seen, so the order in which
+// a call asks its stages for scratch is free; only the first calls after a switch between call types can see an extra hipMalloc.
+// the extractor's sizes (icap NULL: the resident frame's capacity counts; cap < 0: no keypoint output to check against it here)
+int trk_dims(orbx_ctx* ctx, int cap, int* icap, int* nlevels) {
+  if (icap) *icap = orbx_max_keypoints(ctx);
+  ORBHIP_REQUIRE(!icap || (*icap <= TRK_MAXKP && (cap < 0 || cap >= *icap)), ORBHIP_ECAP, "output capacity below orbx_max_keypoints(ctx) (or more than 4096 features per frame)");
+  *nlevels = orbx_get_levels(ctx);
+  ORBHIP_REQUIRE(*nlevels > 0 && *nlevels <= 16, ORBHIP_EINVAL, "bad level count");
+  return 0;
+}
+// a producing call starts here: the workspace, the stream and every kernel of the call live on the default device; an extractor created
+// on another one would launch across devices.  A device change drops the resident frame (and the caller's high-water mark).
+int trk_begin(ThreadWs& W, const orbx_ctx* ctx, TrkFrame& TF, uint32_t* cand_hw = nullptr) {
+  if (int rc = W.begin()) return rc;
+  ORBHIP_REQUIRE(orbhip::orbx_ctx_device(ctx) == W.device, ORBHIP_EINVAL, "the extractor context was created on another device than orbhip_set_default_device() selects");
+  if (TF.device != W.device) { TF = TrkFrame(); TF.device = W.device; if (cand_hw) *cand_hw = 0; }
+  return 0;
+}
+// a call that goes on with the frame an earlier call of this thread left on the device (icap < 0: the caller checks the keypoint count instead)
+int trk_require_resident(const TrkFrame& TF, int device, const orbx_ctx* ctx, int nlevels, int icap) {
+  ORBHIP_REQUIRE(TF.valid && TF.device == device, ORBHIP_EINVAL, "no frame resident on this thread's device: an extracting orbt_* call comes first (same host thread)");
+  ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels && (icap < 0 || TF.icap == icap), ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
+  ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
+  return 0;
+}
+// the first three rows of Tcw -> [t, q]
+int trk_pose7(const double* T34, double* pose7) {
+  double T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+  std::memcpy(T, T34, 12 * sizeof(double));
+  return ba_matrix4d_to_pose7(T, pose7);
+}
+// k_trk_prepare's constants that do not depend on the queries (I.scale comes from orbx_get_tables)
+void trk_prepare_consts(TrkIn& I, const float* K4, const float* bounds, int nlevels, const float* dist5) {
+  std::memset(&I, 0, sizeof(I));
+  for (int k = 0; k < 4; k++) { I.K4[k] = K4[k]; I.bounds[k] = bounds[k]; }
+  I.nlevels = nlevels;
+  for (int k = 0; k < 5; k++) I.dist[k] = dist5 ? (double)dist5[k] : 0.0;
+}
+
+// The window search (k_trk_windows): the queries' windows and their compacted candidate lists, at most cand_cap pairs (per_query * nq or the thread's
+// high-water mark).  When a frame has more, the kernel only counts them: regrown() raises the mark and the caller runs the call once more.
+struct TrkWindows {
+  int nq = 0; uint32_t cand_cap = 0;
+  float* quv; float* qr; int32_t* qlo; int32_t* qhi; uint8_t* qv; uint32_t* off; uint32_t* total; uint2* pairs; uint32_t* acc; int32_t* accn;
+  void alloc(ThreadWs& W, int nq_, uint32_t per_query, uint32_t cand_hw, int* rc) {
+    const size_t n1 = (size_t)std::max(nq = nq_, 1);
+    cand_cap = std::max<uint32_t>(cand_hw, (uint32_t)n1 * per_query);
+    quv = W.d<float>(2 * n1, rc); qr = W.d<float>(n1, rc); qlo = W.d<int32_t>(n1, rc); qhi = W.d<int32_t>(n1, rc); qv = W.d<uint8_t>(n1, rc);
+    off = W.d<uint32_t>(2 * (size_t)nq + 4, rc); total = off + 2 * (size_t)nq + 2;
+    pairs = W.d<uint2>(cand_cap, rc); acc = W.d<uint32_t>(n1 * TRK_LMAX, rc); accn = W.d<int32_t>(n1, rc);
+  }
+  void launch(hipStream_t s, const TrkFrame& TF, const uint8_t* q_desc, int dmax) const {      // (no queries: no launch)
+    const FrameGridDev& g = TF.grid;
+    if (nq > 0)
+      hipLaunchKernelGGL(k_trk_windows, dim3((nq + 3) / 4), dim3(256), 0, s, TF.kps4.as<float>(), g.off.as<uint32_t>(), g.idx.as<uint32_t>(), g.min_x, g.min_y, g.winv, g.hinv,
+                         quv, qr, qlo, qhi, qv, nq, q_desc, TF.blk.as<uint8_t>() + TF.oDesc, total, off, pairs, cand_cap, acc, accn, dmax);
+  }
+  static int no_fit() { set_error("window candidate lists did not fit after regrowing"); return ORBHIP_ENOMEM; }      // (after the second attempt)
+  bool regrown(uint32_t cand_total, uint32_t& cand_hw) const {
+    const bool again = cand_total > cand_cap;                    // (rare) once more, larger lists
+    cand_hw = again ? cand_total + cand_total / 4 : std::max<uint32_t>(cand_hw, cand_total + cand_total / 8);
+    return again;
+  }
+};
+
+// Building the resident frame: the extractor on the call's stream, then k_trk_prepare (the frame's float records and grid, the
+// projections of the caller's queries if it has any).  The frame's pieces are contiguous inside TF.blk - [count | keypoints |
+// descriptors | undistorted xy] - so that ONE range download covers them, alone (down) or as part of the caller's output block.
+struct TrkFrameBuild {
+  size_t oCnt = 0, oKps = 0, oDesc = 0, oUnd = 0, end = 0; int icap = 0; const float* dist5 = nullptr;
+  void carve(Carve& C, int icap_, const float* dist5_) {
+    icap = icap_; dist5 = dist5_;
+    oCnt = C.take(4); oKps = C.take((size_t)icap * sizeof(orbx_keypoint)); oDesc = C.take((size_t)icap * 32); end = oDesc + (size_t)icap * 32;
+    if (dist5) { oUnd = C.take(8 * (size_t)icap); end = oUnd + 8 * (size_t)icap; }
+  }
+  // (blk_bytes: the size of the block the pieces were carved from; no resident frame from here until publish())
+  int launch(TrkFrame& TF, ThreadWs& W, orbx_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, const float* bounds, int nlevels, size_t blk_bytes,
+             const TrkIn* dI, const TrkWindows* Q = nullptr, const double* q_Xw = nullptr, const int32_t* q_octave = nullptr, const uint8_t* q_valid = nullptr) const {
+    TF.valid = false;
+    int rc = 0;
+    FrameGridDev& g = TF.grid;
+    if ((rc = TF.blk.ensure(blk_bytes)) || (rc = TF.kps4.ensure(16 * (size_t)icap)) || (rc = g.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = g.idx.ensure((size_t)icap * 4))) return rc;
+    TF.oCnt = oCnt; TF.oDesc = oDesc; TF.icap = icap; TF.nlevels = nlevels;
+    g.min_x = bounds[0]; g.min_y = bounds[2];
+    g.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); g.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
+    uint8_t* fb = TF.blk.as<uint8_t>();
+    orbx_keypoint* d_kps = (orbx_keypoint*)(fb + oKps); int32_t* d_count = (int32_t*)(fb + oCnt);
+    if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, d_kps, fb + oDesc, icap, d_count, (void*)W.s))) return rc;
+    // without queries the kernel writes its list counter and nothing else of theirs: one scratch word stands in for every query array
+    uint32_t* d_none = Q ? nullptr : W.d<uint32_t>(4, &rc);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dist5 ? k_trk_prepare<true> : k_trk_prepare<false>, dim3(1), dim3(1024), 0, W.s, dI, q_Xw, q_octave, q_valid, d_kps, d_count, icap,
+                       Q ? Q->quv : (float*)d_none, Q ? Q->qr : (float*)d_none, Q ? Q->qlo : (int32_t*)d_none, Q ? Q->qhi : (int32_t*)d_none, Q ? Q->qv : (uint8_t*)d_none,
+                       TF.kps4.as<float>(), g.off.as<uint32_t>(), g.idx.as<uint32_t>(), Q ? Q->nq : 0, Q ? Q->total : d_none, dist5 ? (float*)(fb + oUnd) : (float*)nullptr);
+    return 0;
+  }
+  // (the returned pointer stands for the start of TF.blk, as publish() expects it)
+  const uint8_t* down(ThreadWs& W, const TrkFrame& TF, int* rc) const { return W.down(TF.blk.as<uint8_t>() + oCnt, end - oCnt, rc) - oCnt; }
+  // after the synchronise (n_dev: the count the kernels read; hb: host copy of TF.blk).  built: the frame becomes the resident one and goes to the caller
+  int publish(TrkFrame& TF, const orbx_ctx* ctx, bool built, int n_dev, const uint8_t* hb, orbx_keypoint* kps_out, uint8_t* desc_out, int* n_out) const {
+    if (n_dev < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
+    const int n = *n_out = std::min(n_dev, TF.icap);
+    if (built) {
+      TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx);
+      std::memcpy(kps_out, hb + oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hb + oDesc, (size_t)n * 32);
+      trk_keep_undistorted(TF, dist5, hb + oKps, dist5 ? hb + oUnd : nullptr, n);
+    }
+    if (n != TF.n_kp) { set_error("resident frame changed"); return ORBHIP_EINVAL; }
+    return 0;
+  }
+  // the frame of a call that takes either: built from the image, or (img NULL) the resident one; the call's packed inputs go up on the way
+  int from_image_or_resident(TrkFrame& TF, ThreadWs& W, orbx_ctx* ctx, const uint8_t* img, int w, int h, int stride, const float* bounds, int nlevels, int icap_,
+                             const float* dist5_, ThreadWs::Pack& in, int pPI) {
+    int rc = 0;
+    uint8_t* d_img = img ? W.up<uint8_t>(img, (size_t)stride * (h - 1) + w, &rc) : nullptr;
+    if (!img && (rc = trk_require_resident(TF, W.device, ctx, nlevels, icap_))) return rc;
+    if (rc || (rc = W.commit(in))) return rc;
+    Carve C; carve(C, icap_, dist5_);
+    return img ? launch(TF, W, ctx, d_img, w, h, stride, bounds, nlevels, C.total, in.dev<TrkIn>(pPI)) : 0;
+  }
+};
+
+// The tail three calls share: their matcher kernel leaves PoseOptimization's observation list (points, pixels, weights in feature order,
+// obs_feat: which feature each is) and the start pose on the device, k_pose_lm (ba_solver.hip) solves it there, and the outlier flags
+// come back per observation.  Pieces of the caller's output block: [TrkOut | pose7 | summary | n_inliers | obs_feat | outlier].
+struct TrkPoseTail {
+  size_t oOut = 0, oPose = 0, oSum = 0, oNin = 0, oFeat = 0, oOutl = 0;
+  double* oX; double* ouv; float* ow; int32_t* ooff; double* K4;
+  void carve(Carve& C, int icap) {
+    oOut = C.take(sizeof(TrkOut)); oPose = C.take(56); oSum = C.take(sizeof(ba_summary)); oNin = C.take(4); oFeat = C.take(4 * (size_t)icap); oOutl = C.take((size_t)icap);
+  }
+  void alloc(ThreadWs& W, int icap, int* rc) {      // (also the scratch k_trf_finish wants when nobody solves: relocalisation)
+    oX = W.d<double>(3 * (size_t)icap, rc); ouv = W.d<double>(2 * (size_t)icap, rc); ow = W.d<float>(icap, rc); ooff = W.d<int32_t>(2, rc); K4 = W.d<double>(4, rc);
+  }
+  int solve(uint8_t* dblk, hipStream_t s) const {      // (behind the matcher kernel's launch, whose error it reports)
+    ORBHIP_CHECK_HIP(hipGetLastError());
+    return ba_pose_optimization_batch_device(K4, (double*)(dblk + oPose), oX, ouv, ow, ooff, 1, dblk + oOutl, (int32_t*)(dblk + oNin), (ba_summary*)(dblk + oSum), (void*)s);
+  }
+  // (pose7_in: the pose the call started from; greedy_rounds / reserved are the caller's)
+  const TrkOut* unpack(const uint8_t* hb, const double* pose7_in, int n, uint8_t* outlier_out, orbt_result* res) const {
+    const TrkOut* T = (const TrkOut*)(hb + oOut);
+    std::memset(outlier_out, 0, (size_t)n);
+    const int32_t* feat = (const int32_t*)(hb + oFeat);
+    for (int k = 0; k < T->nobs; k++) outlier_out[feat[k]] = hb[oOutl + k];
+    res->n_keypoints = n; res->nmatches = T->nmatches; res->n_correspondences = T->nobs;
+    // PoseOptimization returns 0 and leaves the pose alone with fewer than 3 correspondences (src/CeresOptimizer.cc:330)
+    res->n_inliers = T->nobs < 3 ? 0 : *(const int32_t*)(hb + oNin);
+    std::memcpy(res->pose7, T->nobs < 3 ? (const void*)pose7_in : (const void*)(hb + oPose), 56);
+    return T;
+  }
+};
+
+// Frame::ComputeBoW (src/Frame.cc:322-327: levelsup 4) of the resident frame: the descent on the device (the rows behind the keypoint
+// count are descended too and ignored), the merge into the BoW / feature vectors on the host.  Pieces: [word | weight | node].
+struct TrkBow {
+  size_t oWord = 0, oWt = 0, oNode = 0;
+  void carve(Carve& C, int fcap) { oWord = C.take(4 * (size_t)fcap); oWt = C.take(8 * (size_t)fcap); oNode = C.take(4 * (size_t)fcap); }
+  int descend(orbv_ctx* voc, const TrkFrame& TF, uint8_t* dblk, hipStream_t s) const {
+    return orbv_descend_device(voc, TF.blk.as<uint8_t>() + TF.oDesc, TF.icap, 4, (int32_t*)(dblk + oWord), (double*)(dblk + oWt), (uint32_t*)(dblk + oNode), (void*)s);
+  }
+  void merge(const uint8_t* hb, int n, uint32_t* bow_word, double* bow_value, int* n_words, uint32_t* fv_node, uint32_t* fv_off, uint32_t* fv_idx, int* n_fv_nodes) const {
+    if (bow_word && bow_value && fv_node && fv_idx)
+      orbhip::orbv_merge_host((const int32_t*)(hb + oWord), (const double*)(hb + oWt), (const uint32_t*)(hb + oNode), n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
+    else { *n_words = 0; *n_fv_nodes = 0; fv_off[0] = 0; }
+  }
+};
+
+// ORBmatcher::SearchByBoW(keyframe, frame) against the resident frame: k_trf_init, k_trf_bow (one wave per vocabulary node of the
+// keyframe; none: no launch), k_trf_finish (rotation histogram, the observation list of PoseOptimization at P / d_feat / d_pose)
+struct TrfKeyframe {      // the keyframe's arrays as pieces of the call's packed upload
+  int n, fv_n, d, v, a, fn, fo, fi;
+  TrfKeyframe(ThreadWs::Pack& in, int n_, const uint8_t* desc, const uint8_t* valid, const float* angle, int fv_n_, const uint32_t* fv_node, const uint32_t* fv_off, const uint32_t* fv_idx)
+      : n(n_), fv_n(fv_n_), d(in.add(desc, 32 * (size_t)n)), v(in.add(valid, (size_t)n)), a(in.add(angle, 4 * (size_t)n)), fn(in.add(fv_node, 4 * (size_t)fv_n)),
+        fo(in.add(fv_off, 4 * ((size_t)fv_n + 1))), fi(in.add(fv_idx, 4 * (size_t)(fv_n ? fv_off[fv_n] : 0u))) {}
+};
+void trf_launch(hipStream_t s, const ThreadWs::Pack& in, const TrfIn* dI, const TrfKeyframe& kf, const double* kf_Xw, const TrkFrame& TF, const TrkBow& B, const uint8_t* dblk, int32_t* d_match, int32_t* d_owner, int32_t* d_bin,
+                int* d_hist, int32_t* d_feat, const TrkPoseTail& P, double* d_pose, TrkOut* d_out) {
+  const uint8_t* fblk = TF.blk.as<uint8_t>();
+  const float* d_kps4 = TF.kps4.as<float>();
+  const int32_t* d_count = (const int32_t*)(fblk + TF.oCnt);
+  const int fcap = TF.icap;
+  hipLaunchKernelGGL(k_trf_init, dim3((std::max(std::max(kf.n, fcap), 64) + 255) / 256), dim3(256), 0, s, d_match, kf.n, d_owner, d_bin, fcap, d_hist);
+  if (kf.fv_n > 0)
+    hipLaunchKernelGGL(k_trf_bow, dim3(kf.fv_n), dim3(64), 0, s, dI, in.dev<uint32_t>(kf.fn), in.dev<uint32_t>(kf.fo), in.dev<uint32_t>(kf.fi), in.dev<uint8_t>(kf.d), in.dev<uint8_t>(kf.v), in.dev<float>(kf.a), fblk + TF.oDesc, (const uint32_t*)(dblk + B.oNode),
+                       (const double*)(dblk + B.oWt), d_kps4, d_count, fcap, d_match, d_owner, d_bin, d_hist);
+  hipLaunchKernelGGL(k_trf_finish, dim3(1), dim3(1024), 0, s, dI, (const int*)d_hist, d_kps4, d_count, fcap, kf_Xw, d_match, d_owner, d_bin, d_feat, P.oX, P.ouv, P.ow, P.ooff, d_pose, P.K4, d_out);
+}
 }  // namespace
 
 // host wall time of the calling thread's most recent orbt_* call (orbt_last_call_ms): what a latency figure should be made of when
@@ -1166,6 +1350,26 @@ static thread_local double g_last_call_ms = 0.0;
 struct CallClock {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   ~CallClock() { g_last_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+// ORBHIP_TRACK_TIMING=1: host wall time of the motion-model call's phases (mean over every 100 calls of the thread, on stderr).
+// mark(0) at entry, (1) uploads enqueued, (2) kernels and download enqueued, (3) synchronised; report() closes the call.
+struct TrkTiming {
+  double t[5] = {0, 0, 0, 0, 0};
+  static bool on() { static const bool v = []() { const char* e = std::getenv("ORBHIP_TRACK_TIMING"); return e && e[0] == '1'; }(); return v; }
+  void mark(int k) { if (on()) t[k] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void report(const TrkOut* T) {
+    if (!on()) return;
+    static thread_local double acc[5] = {0, 0, 0, 0, 0}; static thread_local int n = 0;
+    mark(4);
+    const double d[5] = {t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[4] - t[0]};
+    for (int k = 0; k < 5; k++) acc[k] += d[k];
+    const char* fmt = "orbt_track_with_motion_model%s: staging + upload enqueue %.1f us, kernel launches %.1f us, wait %.1f us, unpack %.1f us, total %.1f us\n";
+    if (d[4] > 2000.0) fprintf(stderr, fmt, " SLOW CALL", d[0], d[1], d[2], d[3], d[4]);                 // an outlier: which phase waited?
+    if (++n < 100) return;
+    fprintf(stderr, "k_trk_greedy ticks (10 ns): setup %d rounds %d (%d rounds, %d sweeps; lists inverted at %d, first pass done at %d; setup: cleared at %d, counts scanned at %d) rotation+owners %d observations %d\n", T->ticks[0], T->ticks[1], T->rounds % 1000, T->rounds / 1000, T->ticks[4], T->ticks[5], T->ticks[6], T->ticks[7], T->ticks[2], T->ticks[3]);
+    fprintf(stderr, fmt, "", acc[0] / 100, acc[1] / 100, acc[2] / 100, acc[3] / 100, acc[4] / 100);
+    for (double& a : acc) a = 0; n = 0;
+  }
 };
 extern "C" {
 double orbt_last_call_ms(void) { return g_last_call_ms; }
@@ -1228,76 +1432,38 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
                  ORBHIP_EINVAL, "NULL argument");
   ORBHIP_REQUIRE(n_last >= 0 && n_last <= 4096 && (n_last == 0 || (last_Xw && last_desc && last_octave && last_angle && last_valid && match_out)), ORBHIP_EINVAL,
                  "bad last-frame arrays (at most 4096 features)");
-  const int icap = orbx_max_keypoints(ctx);
-  ORBHIP_REQUIRE(cap >= icap && icap <= TRK_MAXKP, ORBHIP_ECAP, "output capacity below orbx_max_keypoints(ctx) (or more than 4096 features per frame)");
-  const int nlevels = orbx_get_levels(ctx);
-  ORBHIP_REQUIRE(nlevels > 0 && nlevels <= 16, ORBHIP_EINVAL, "bad level count");
+  int icap = 0, nlevels = 0, rc = 0;
+  if ((rc = trk_dims(ctx, cap, &icap, &nlevels))) return rc;
   ThreadWs& W = thread_ws();
-  // ORBHIP_TRACK_TIMING=1: host wall time of the call's phases (mean over every 100 calls, on stderr)
-  static const bool timing = []() { const char* e = std::getenv("ORBHIP_TRACK_TIMING"); return e && e[0] == '1'; }();
-  static thread_local double t_acc[5] = {0, 0, 0, 0, 0}; static thread_local int t_n = 0;
-  auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = timing ? now_us() : 0.0;
-  static thread_local uint32_t cand_cap_tl = 0;
+  TrkTiming clock; clock.mark(0);
+  static thread_local uint32_t cand_hw = 0;                    // high-water mark of the candidate lists
   TrkFrame& TF = g_trk_frame;
-  FrameGridDev& grid = TF.grid;                                // (off / idx buffers filled by k_trk_prepare)
   TF.valid = false;
+  const int nq = n_last;
+  const float* dist5 = trk_distortion_of(ctx);
+  TrkIn I; trk_prepare_consts(I, K4, bounds, nlevels, dist5);
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.R[3 * r + c] = Tcw_pred[4 * r + c]; I.t[r] = Tcw_pred[4 * r + 3]; }
+  I.th = th; I.nq = nq; I.check_ori = check_ori ? 1 : 0;
   for (int attempt = 0; attempt < 2; attempt++) {
-    int rc = W.begin();
-    if (rc) return rc;
-    // the workspace, the stream and every kernel of this call live on the default device; an extractor created on another one
-    // would launch across devices
-    ORBHIP_REQUIRE(orbhip::orbx_ctx_device(ctx) == W.device, ORBHIP_EINVAL, "the extractor context was created on another device than orbhip_set_default_device() selects");
-    if (TF.device != W.device) { TF = TrkFrame(); TF.device = W.device; cand_cap_tl = 0; }
-    const int nq = n_last;
-    const uint32_t cand_cap = std::max<uint32_t>(cand_cap_tl, (uint32_t)std::max(nq, 1) * 64u);
-    TrkIn I; std::memset(&I, 0, sizeof(I));
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.R[3 * r + c] = Tcw_pred[4 * r + c]; I.t[r] = Tcw_pred[4 * r + 3]; }
-    { double T[16]; for (int k = 0; k < 12; k++) T[k] = Tcw_pred[k]; T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1; if (int r2 = ba_matrix4d_to_pose7(T, I.pose7)) return r2; }
-    for (int k = 0; k < 4; k++) { I.K4[k] = K4[k]; I.bounds[k] = bounds[k]; }
-    I.th = th; I.nq = nq; I.check_ori = check_ori ? 1 : 0; I.nlevels = nlevels;
-    const float* dist5 = trk_distortion_of(ctx);
-    trk_fill_distortion(I, dist5);
-    if (int r2 = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr)) return r2;
+    if ((rc = trk_begin(W, ctx, TF, &cand_hw))) return rc;
+    if ((rc = trk_pose7(Tcw_pred, I.pose7)) || (rc = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr))) return rc;
     // uploads: the image (straight from the caller's memory through pinned staging) and ONE packed block
-    const size_t img_bytes = (size_t)stride * (h - 1) + w;
-    uint8_t* d_img = W.up<uint8_t>(img, img_bytes, &rc);
+    uint8_t* d_img = W.up<uint8_t>(img, (size_t)stride * (h - 1) + w, &rc);
     ThreadWs::Pack in;
     const int pI = in.add(&I, sizeof(I)), pX = in.add(last_Xw, 24 * (size_t)nq), pD = in.add(last_desc, 32 * (size_t)nq), pO = in.add(last_octave, 4 * (size_t)nq),
               pA = in.add(last_angle, 4 * (size_t)nq), pV = in.add(last_valid, (size_t)nq);
     if (rc || (rc = W.commit(in))) return rc;
-    const double t1 = timing ? now_us() : 0.0;
-    // ONE output block: [TrkOut | pose7 | summary | count | kps | desc | match | owner | obs_feat | outlier]
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oOut = take(sizeof(TrkOut)), oPose = take(56), oSum = take(sizeof(ba_summary)), oCnt = take(4), oNin = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)),
-                 oDesc = take((size_t)icap * 32), oMatch = take(4 * (size_t)std::max(nq, 1)), oOwner = take(4 * (size_t)icap), oFeat = take(4 * (size_t)icap),
-                 oOutl = take((size_t)icap);
-    const size_t oUnd = dist5 ? take(8 * (size_t)icap) : 0;      // (behind everything else: without distortion the block is what it always was)
-    if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap))) return rc;
-    uint8_t* dblk = TF.blk.as<uint8_t>();
-    float* d_quv = W.d<float>(2 * (size_t)std::max(nq, 1), &rc); float* d_qr = W.d<float>(std::max(nq, 1), &rc);
-    int32_t* d_qlo = W.d<int32_t>(std::max(nq, 1), &rc); int32_t* d_qhi = W.d<int32_t>(std::max(nq, 1), &rc); uint8_t* d_qv = W.d<uint8_t>(std::max(nq, 1), &rc);
-    float* d_kps4 = TF.kps4.as<float>();
-    uint32_t* d_off = W.d<uint32_t>(2 * (size_t)nq + 4, &rc); uint2* d_pairs = W.d<uint2>(cand_cap, &rc);
-    uint32_t* d_total = d_off + 2 * (size_t)nq + 2;
-    double* d_oX = W.d<double>(3 * (size_t)icap, &rc); double* d_ouv = W.d<double>(2 * (size_t)icap, &rc); float* d_ow = W.d<float>(icap, &rc);
-    int32_t* d_ooff = W.d<int32_t>(2, &rc); double* d_K4 = W.d<double>(4, &rc);
-    uint32_t* d_acc = W.d<uint32_t>((size_t)std::max(nq, 1) * TRK_LMAX, &rc); int32_t* d_accn = W.d<int32_t>(std::max(nq, 1), &rc);
+    clock.mark(1);
+    // ONE output block, which is the resident frame's block too: [frame pieces | pose tail | match | owner]
+    Carve C; TrkFrameBuild F; TrkPoseTail P; TrkWindows Q;
+    F.carve(C, icap, dist5); P.carve(C, icap);
+    const size_t oMatch = C.take(4 * (size_t)std::max(nq, 1)), oOwner = C.take(4 * (size_t)icap);
+    Q.alloc(W, nq, 64u, cand_hw, &rc); P.alloc(W, icap, &rc);
     if (rc) return rc;
-    if ((rc = grid.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = grid.idx.ensure((size_t)icap * 4))) return rc;
-    grid.min_x = bounds[0]; grid.min_y = bounds[2];
-    grid.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); grid.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
-    orbx_keypoint* d_kps = (orbx_keypoint*)(dblk + oKps); uint8_t* d_desc = dblk + oDesc; int32_t* d_count = (int32_t*)(dblk + oCnt);
-    if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, d_kps, d_desc, icap, d_count, (void*)W.s))) return rc;
     const TrkIn* dI = in.dev<TrkIn>(pI);
-    trk_prepare_launch(dist5 != nullptr, W.s, dI, (const double*)in.dev<double>(pX), (const int32_t*)in.dev<int32_t>(pO), (const uint8_t*)in.dev<uint8_t>(pV), (const orbx_keypoint*)d_kps,
-                       (const int32_t*)d_count, icap, d_quv, d_qr, d_qlo, d_qhi, d_qv, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), nq, d_total,
-                       dist5 ? (float*)(dblk + oUnd) : (float*)nullptr);
-    if (nq > 0) {
-      hipLaunchKernelGGL(k_trk_windows, dim3((nq + 3) / 4), dim3(256), 0, W.s, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), grid.min_x, grid.min_y, grid.winv,
-                         grid.hinv, d_quv, d_qr, d_qlo, d_qhi, d_qv, nq, in.dev<uint8_t>(pD), d_desc, d_total, d_off, d_pairs, cand_cap, d_acc, d_accn, TRK_TH_HIGH);
-    }
+    if ((rc = F.launch(TF, W, ctx, d_img, w, h, stride, bounds, nlevels, C.total, dI, &Q, in.dev<double>(pX), in.dev<int32_t>(pO), in.dev<uint8_t>(pV)))) return rc;
+    uint8_t* dblk = TF.blk.as<uint8_t>();
+    Q.launch(W.s, TF, in.dev<uint8_t>(pD), TRK_TH_HIGH);
     // dynamic LDS of the greedy kernel: offsets, states, proposals (ints per query), two work lists, the candidate entries
     // (+ the inverted lists of the dataflow path: two bytes per entry behind the four of the entries themselves)
     const size_t lds_fixed = (size_t)(3 * nq + 1) * 4 + 2 * (size_t)((nq + 1) & ~1) * 2;
@@ -1306,51 +1472,25 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
     const size_t lds_greedy = lds_fixed + (size_t)ecap * 6 + 16;
     static const int force_rounds = []() { const char* e = ORBHIP_EXP_ENV("ORBHIP_TRACK_ROUNDS"); return (e && e[0] == '1') ? 1 : 0; }();
     if ((rc = raise_dynamic_lds((const void*)k_trk_greedy, W.device, 100 * 1024 + 64))) return rc;
-    hipLaunchKernelGGL(k_trk_greedy, dim3(1), dim3(TRK_GT), lds_greedy, W.s, dI, d_qv, in.dev<float>(pA), d_acc, d_accn, in.dev<double>(pX), d_off, d_total, d_pairs, cand_cap, d_kps4, d_count, icap,
-                       (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), (int32_t*)(dblk + oFeat), d_oX, d_ouv, d_ow, d_ooff, (double*)(dblk + oPose), d_K4,
-                       (TrkOut*)(dblk + oOut), ecap, tcap, force_rounds, nq, I.check_ori);
-    ORBHIP_CHECK_HIP(hipGetLastError());
-    if ((rc = ba_pose_optimization_batch_device(d_K4, (double*)(dblk + oPose), d_oX, d_ouv, d_ow, d_ooff, 1, dblk + oOutl, (int32_t*)(dblk + oNin),
-                                                (ba_summary*)(dblk + oSum), (void*)W.s))) return rc;
-    const uint8_t* hb = W.down(dblk, o, &rc);
-    const double t2 = timing ? now_us() : 0.0;
+    hipLaunchKernelGGL(k_trk_greedy, dim3(1), dim3(TRK_GT), lds_greedy, W.s, dI, Q.qv, in.dev<float>(pA), Q.acc, Q.accn, in.dev<double>(pX), Q.off, Q.total, Q.pairs, Q.cand_cap,
+                       TF.kps4.as<float>(), (int32_t*)(dblk + F.oCnt), icap, (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), (int32_t*)(dblk + P.oFeat), P.oX, P.ouv, P.ow, P.ooff,
+                       (double*)(dblk + P.oPose), P.K4, (TrkOut*)(dblk + P.oOut), ecap, tcap, force_rounds, nq, I.check_ori);
+    if ((rc = P.solve(dblk, W.s))) return rc;
+    const uint8_t* hb = W.down(dblk, C.total, &rc);
+    clock.mark(2);
     if (rc || (rc = W.sync())) return rc;
-    const double t3 = timing ? now_us() : 0.0;
-    const TrkOut* T = (const TrkOut*)(hb + oOut);
-    if (T->n_keypoints < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
-    if ((uint32_t)T->cand_total > cand_cap) { cand_cap_tl = (uint32_t)T->cand_total + (uint32_t)T->cand_total / 4; continue; }   // (rare) once more, larger lists
-    cand_cap_tl = std::max<uint32_t>(cand_cap_tl, (uint32_t)T->cand_total + (uint32_t)T->cand_total / 8);
-    const int n = std::min(T->n_keypoints, icap);
-    std::memcpy(kps_out, hb + oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hb + oDesc, (size_t)n * 32);
+    clock.mark(3);
+    if (Q.regrown((uint32_t)((const TrkOut*)(hb + P.oOut))->cand_total, cand_hw)) continue;
+    int n = 0;
+    if ((rc = F.publish(TF, ctx, true, *(const int32_t*)(hb + F.oCnt), hb, kps_out, desc_out, &n))) return rc;
     if (nq) std::memcpy(match_out, hb + oMatch, 4 * (size_t)nq);
     std::memcpy(owner_out, hb + oOwner, 4 * (size_t)n);
-    std::memset(outlier_out, 0, (size_t)n);
-    const int32_t* feat = (const int32_t*)(hb + oFeat);
-    for (int k = 0; k < T->nobs; k++) outlier_out[feat[k]] = hb[oOutl + k];
-    TF.oKps = oKps; TF.oDesc = oDesc; TF.oCnt = oCnt; TF.icap = icap; TF.n_kp = n; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16); TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx);
-    TF.oUnd = oUnd; trk_keep_undistorted(TF, dist5, hb + oKps, dist5 ? hb + oUnd : nullptr, n);
-    res->n_keypoints = n; res->nmatches = T->nmatches; res->n_correspondences = T->nobs; res->greedy_rounds = T->rounds % 1000;
-    std::memcpy(res->pose7, hb + oPose, 56);
-    // PoseOptimization returns 0 and leaves the pose alone with fewer than 3 correspondences (src/CeresOptimizer.cc:330)
-    res->n_inliers = T->nobs < 3 ? 0 : *(const int32_t*)(hb + oNin);
-    if (T->nobs < 3) std::memcpy(res->pose7, I.pose7, 56);
-    if (timing) {
-      const double t4 = now_us();
-      t_acc[0] += t1 - t0; t_acc[1] += t2 - t1; t_acc[2] += t3 - t2; t_acc[3] += t4 - t3; t_acc[4] += t4 - t0;
-      if (t4 - t0 > 2000.0)                 // an outlier: which phase waited?
-        fprintf(stderr, "orbt_track_with_motion_model SLOW CALL: staging + upload enqueue %.1f us, kernel launches %.1f us, wait %.1f us, unpack %.1f us, total %.1f us\n",
-                t1 - t0, t2 - t1, t3 - t2, t4 - t3, t4 - t0);
-      if (++t_n == 100) {
-        fprintf(stderr, "k_trk_greedy ticks (10 ns): setup %d rounds %d (%d rounds, %d sweeps; lists inverted at %d, first pass done at %d; setup: cleared at %d, counts scanned at %d) rotation+owners %d observations %d\n", T->ticks[0], T->ticks[1], T->rounds % 1000, T->rounds / 1000, T->ticks[4], T->ticks[5], T->ticks[6], T->ticks[7], T->ticks[2], T->ticks[3]);
-        fprintf(stderr, "orbt_track_with_motion_model: staging + upload enqueue %.1f us, kernel launches %.1f us, wait %.1f us, unpack %.1f us, total %.1f us\n",
-                t_acc[0] / 100, t_acc[1] / 100, t_acc[2] / 100, t_acc[3] / 100, t_acc[4] / 100);
-        for (double& a : t_acc) a = 0; t_n = 0;
-      }
-    }
+    const TrkOut* T = P.unpack(hb, I.pose7, n, outlier_out, res);
+    res->greedy_rounds = T->rounds % 1000;
+    clock.report(T);
     return 0;
   }
-  set_error("window candidate lists did not fit after regrowing");
-  return ORBHIP_ENOMEM;
+  return TrkWindows::no_fit();
 }
 
 int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, const double* Tcw, float log_scale_factor,
@@ -1361,85 +1501,59 @@ int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, co
   ORBHIP_REQUIRE(ctx && K4 && bounds && Tcw && res && mp_in_view && mp_match && slot_owner && outlier_out && slot_Xw && slot_state, ORBHIP_EINVAL, "NULL argument");
   ORBHIP_REQUIRE(n_mp >= 0 && n_mp <= TLM_MAXMP, ORBHIP_ECAP, "more than 16384 local map points per call");
   ORBHIP_REQUIRE(n_mp == 0 || (mp_Xw && mp_normal && mp_min_dist && mp_max_dist && mp_desc && mp_state), ORBHIP_EINVAL, "NULL map-point argument");
-  TrkFrame& TF = g_trk_frame;
+  const TrkFrame& TF = g_trk_frame;
   ThreadWs& W = thread_ws();
-  static thread_local uint32_t cand_cap_tl = 0;
-  const int nlevels = orbx_get_levels(ctx);
-  ORBHIP_REQUIRE(nlevels > 0 && nlevels <= 16, ORBHIP_EINVAL, "bad level count");
+  static thread_local uint32_t cand_hw = 0;
+  int nlevels = 0, rc = 0;
+  if ((rc = trk_dims(ctx, -1, nullptr, &nlevels))) return rc;
+  const int nq = n_mp;
+  TlmIn I; std::memset(&I, 0, sizeof(I));
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.C.R[3 * r + c] = Tcw[4 * r + c]; I.C.t[r] = Tcw[4 * r + 3]; }
+  for (int k = 0; k < 3; k++) I.C.Ow[k] = -(I.C.R[k] * I.C.t[0] + I.C.R[3 + k] * I.C.t[1] + I.C.R[6 + k] * I.C.t[2]);      // Ow = -Rcw^T tcw (src/Frame.cc:188)
+  I.C.fx = K4[0]; I.C.fy = K4[1]; I.C.cx = K4[2]; I.C.cy = K4[3];
+  I.C.min_x = bounds[0]; I.C.max_x = bounds[1]; I.C.min_y = bounds[2]; I.C.max_y = bounds[3];
+  I.C.cos_limit = 0.5f; I.C.log_scale = log_scale_factor; I.C.nlevels = nlevels;          // isInFrustum(map_point, 0.5) (src/Tracking.cc:822)
+  for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
+  I.th = th; I.ratio = nnratio; I.n_mp = n_mp; I.n_kp_host = n_kp;
+  // a distance can win only if it is <= TH_HIGH and can veto through the ratio test only if ratio * d < TH_HIGH
+  { int dm = TRK_TH_HIGH; while (dm < 255 && nnratio * (float)(dm + 1) < (float)TRK_TH_HIGH) dm++; I.dmax = dm; }
   for (int attempt = 0; attempt < 2; attempt++) {
-    int rc = W.begin();
-    if (rc) return rc;
-    ORBHIP_REQUIRE(TF.valid && TF.device == W.device, ORBHIP_EINVAL, "no frame resident on this thread's device: call orbt_track_with_motion_model first (same host thread)");
-    ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
+    if ((rc = W.begin()) || (rc = trk_require_resident(TF, W.device, ctx, nlevels, -1))) return rc;
     ORBHIP_REQUIRE(n_kp == TF.n_kp, ORBHIP_EINVAL, "n_kp differs from the resident frame's keypoint count");
-    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
-    const int icap = TF.icap, nq = n_mp;
-    TlmIn I; std::memset(&I, 0, sizeof(I));
-    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.C.R[3 * r + c] = Tcw[4 * r + c]; I.C.t[r] = Tcw[4 * r + 3]; }
-    for (int k = 0; k < 3; k++) I.C.Ow[k] = -(I.C.R[k] * I.C.t[0] + I.C.R[3 + k] * I.C.t[1] + I.C.R[6 + k] * I.C.t[2]);      // Ow = -Rcw^T tcw (src/Frame.cc:188)
-    I.C.fx = K4[0]; I.C.fy = K4[1]; I.C.cx = K4[2]; I.C.cy = K4[3];
-    I.C.min_x = bounds[0]; I.C.max_x = bounds[1]; I.C.min_y = bounds[2]; I.C.max_y = bounds[3];
-    I.C.cos_limit = 0.5f; I.C.log_scale = log_scale_factor; I.C.nlevels = nlevels;          // isInFrustum(map_point, 0.5) (src/Tracking.cc:822)
-    { double T[16]; for (int k = 0; k < 12; k++) T[k] = Tcw[k]; T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1; if (int r2 = ba_matrix4d_to_pose7(T, I.pose7)) return r2; }
-    for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
-    if (int r2 = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr)) return r2;
-    I.th = th; I.ratio = nnratio; I.n_mp = n_mp; I.n_kp_host = n_kp;
-    // a distance can win only if it is <= TH_HIGH and can veto through the ratio test only if ratio * d < TH_HIGH
-    { int dm = TRK_TH_HIGH; while (dm < 255 && nnratio * (float)(dm + 1) < (float)TRK_TH_HIGH) dm++; I.dmax = dm; }
-    const uint32_t cand_cap = std::max<uint32_t>(cand_cap_tl, (uint32_t)std::max(nq, 1) * 32u);
+    if ((rc = trk_pose7(Tcw, I.pose7)) || (rc = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr))) return rc;
+    const int icap = TF.icap;
     ThreadWs::Pack in;
     const int pI = in.add(&I, sizeof(I)), pX = in.add(mp_Xw, 24 * (size_t)nq), pN = in.add(mp_normal, 24 * (size_t)nq), pMi = in.add(mp_min_dist, 4 * (size_t)nq),
               pMa = in.add(mp_max_dist, 4 * (size_t)nq), pD = in.add(mp_desc, 32 * (size_t)nq), pS = in.add(mp_state, (size_t)nq), pSX = in.add(slot_Xw, 24 * (size_t)n_kp),
               pSS = in.add(slot_state, (size_t)n_kp);
     if ((rc = W.commit(in))) return rc;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oOut = take(sizeof(TrkOut)), oPose = take(56), oSum = take(sizeof(ba_summary)), oNin = take(4), oView = take((size_t)std::max(nq, 1)),
-                 oMatch = take(4 * (size_t)std::max(nq, 1)), oOwner = take(4 * (size_t)icap), oFeat = take(4 * (size_t)icap), oOutl = take((size_t)icap);
-    uint8_t* dblk = W.d<uint8_t>(o, &rc);
-    float* d_quv = W.d<float>(2 * (size_t)std::max(nq, 1), &rc); float* d_qr = W.d<float>(std::max(nq, 1), &rc);
-    int32_t* d_qlo = W.d<int32_t>(std::max(nq, 1), &rc); int32_t* d_qhi = W.d<int32_t>(std::max(nq, 1), &rc); uint8_t* d_qv = W.d<uint8_t>(std::max(nq, 1), &rc);
-    uint32_t* d_off = W.d<uint32_t>(2 * (size_t)nq + 4, &rc); uint2* d_pairs = W.d<uint2>(cand_cap, &rc);
-    uint32_t* d_total = d_off + 2 * (size_t)nq + 2;
-    double* d_oX = W.d<double>(3 * (size_t)icap, &rc); double* d_ouv = W.d<double>(2 * (size_t)icap, &rc); float* d_ow = W.d<float>(icap, &rc);
-    int32_t* d_ooff = W.d<int32_t>(2, &rc); double* d_K4 = W.d<double>(4, &rc);
-    uint32_t* d_acc = W.d<uint32_t>((size_t)std::max(nq, 1) * TRK_LMAX, &rc); int32_t* d_accn = W.d<int32_t>(std::max(nq, 1), &rc);
+    // output block: [pose tail | in_view | match | owner]
+    Carve C; TrkPoseTail P; TrkWindows Q;
+    P.carve(C, icap);
+    const size_t oView = C.take((size_t)std::max(nq, 1)), oMatch = C.take(4 * (size_t)std::max(nq, 1)), oOwner = C.take(4 * (size_t)icap);
+    uint8_t* dblk = W.d<uint8_t>(C.total, &rc);
+    Q.alloc(W, nq, 32u, cand_hw, &rc); P.alloc(W, icap, &rc);
     if (rc) return rc;
     const TlmIn* dI = in.dev<TlmIn>(pI);
-    const uint8_t* fblk = TF.blk.as<uint8_t>();
-    const float* d_kps4 = TF.kps4.as<float>();
-    const FrameGridDev& grid = TF.grid;
     hipLaunchKernelGGL(k_tlm_frustum, dim3((std::max(nq, 1) + 255) / 256), dim3(256), 0, W.s, dI, in.dev<double>(pX), in.dev<double>(pN), in.dev<float>(pMi), in.dev<float>(pMa),
-                       in.dev<uint8_t>(pS), dblk + oView, d_quv, d_qr, d_qlo, d_qhi, d_qv, d_total);
-    if (nq > 0)
-      hipLaunchKernelGGL(k_trk_windows, dim3((nq + 3) / 4), dim3(256), 0, W.s, d_kps4, grid.off.as<uint32_t>(), grid.idx.as<uint32_t>(), grid.min_x, grid.min_y, grid.winv,
-                         grid.hinv, d_quv, d_qr, d_qlo, d_qhi, d_qv, nq, in.dev<uint8_t>(pD), fblk + TF.oDesc, d_total, d_off, d_pairs, cand_cap, d_acc, d_accn, I.dmax);
+                       in.dev<uint8_t>(pS), dblk + oView, Q.quv, Q.qr, Q.qlo, Q.qhi, Q.qv, Q.total);
+    Q.launch(W.s, TF, in.dev<uint8_t>(pD), I.dmax);
     if ((rc = raise_dynamic_lds((const void*)k_tlm_greedy, W.device, 4 * TLM_MAXMP))) return rc;
-    hipLaunchKernelGGL(k_tlm_greedy, dim3(1), dim3(1024), 4 * TLM_MAXMP, W.s, dI, d_qv, d_acc, d_accn, d_off, d_total, d_pairs, cand_cap, d_kps4, (const int32_t*)(fblk + TF.oCnt), icap,
-                       in.dev<double>(pX), in.dev<double>(pSX), in.dev<uint8_t>(pSS), (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), (int32_t*)(dblk + oFeat), d_oX, d_ouv, d_ow,
-                       d_ooff, (double*)(dblk + oPose), d_K4, (TrkOut*)(dblk + oOut), nq);
-    ORBHIP_CHECK_HIP(hipGetLastError());
-    if ((rc = ba_pose_optimization_batch_device(d_K4, (double*)(dblk + oPose), d_oX, d_ouv, d_ow, d_ooff, 1, dblk + oOutl, (int32_t*)(dblk + oNin),
-                                                (ba_summary*)(dblk + oSum), (void*)W.s))) return rc;
-    const uint8_t* hb = W.down(dblk, o, &rc);
+    hipLaunchKernelGGL(k_tlm_greedy, dim3(1), dim3(1024), 4 * TLM_MAXMP, W.s, dI, Q.qv, Q.acc, Q.accn, Q.off, Q.total, Q.pairs, Q.cand_cap, TF.kps4.as<float>(),
+                       (const int32_t*)(TF.blk.as<uint8_t>() + TF.oCnt), icap, in.dev<double>(pX), in.dev<double>(pSX), in.dev<uint8_t>(pSS), (int32_t*)(dblk + oMatch),
+                       (int32_t*)(dblk + oOwner), (int32_t*)(dblk + P.oFeat), P.oX, P.ouv, P.ow, P.ooff, (double*)(dblk + P.oPose), P.K4, (TrkOut*)(dblk + P.oOut), nq);
+    if ((rc = P.solve(dblk, W.s))) return rc;
+    const uint8_t* hb = W.down(dblk, C.total, &rc);
     if (rc || (rc = W.sync())) return rc;
-    const TrkOut* T = (const TrkOut*)(hb + oOut);
-    if ((uint32_t)T->cand_total > cand_cap) { cand_cap_tl = (uint32_t)T->cand_total + (uint32_t)T->cand_total / 4; continue; }   // (rare) once more, larger lists
-    cand_cap_tl = std::max<uint32_t>(cand_cap_tl, (uint32_t)T->cand_total + (uint32_t)T->cand_total / 8);
+    if (Q.regrown((uint32_t)((const TrkOut*)(hb + P.oOut))->cand_total, cand_hw)) continue;
     if (nq) { std::memcpy(mp_in_view, hb + oView, (size_t)nq); std::memcpy(mp_match, hb + oMatch, 4 * (size_t)nq); }
     std::memcpy(slot_owner, hb + oOwner, 4 * (size_t)n_kp);
-    std::memset(outlier_out, 0, (size_t)n_kp);
-    const int32_t* feat = (const int32_t*)(hb + oFeat);
-    for (int k = 0; k < T->nobs; k++) outlier_out[feat[k]] = hb[oOutl + k];
+    const TrkOut* T = P.unpack(hb, I.pose7, n_kp, outlier_out, res);
     int nview = 0; for (int i = 0; i < nq; i++) nview += mp_in_view[i];
-    res->n_keypoints = n_kp; res->nmatches = T->nmatches; res->n_correspondences = T->nobs; res->greedy_rounds = T->rounds; res->reserved = nview;
-    std::memcpy(res->pose7, hb + oPose, 56);
-    res->n_inliers = T->nobs < 3 ? 0 : *(const int32_t*)(hb + oNin);
-    if (T->nobs < 3) std::memcpy(res->pose7, I.pose7, 56);
+    res->greedy_rounds = T->rounds; res->reserved = nview;
     return 0;
   }
-  set_error("window candidate lists did not fit after regrowing");
-  return ORBHIP_ENOMEM;
+  return TrkWindows::no_fit();
 }
 
 int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* img, int w, int h, int stride, const float* K4, const float* bounds, const double* Tcw_last,
@@ -1451,107 +1565,45 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
   ORBHIP_REQUIRE(ctx && voc && K4 && bounds && Tcw_last && res && match_kf && slot_owner && outlier_out && n_words && n_fv_nodes && fv_off, ORBHIP_EINVAL, "NULL argument");
   ORBHIP_REQUIRE(!img || (w > 0 && h > 0 && stride >= w), ORBHIP_EINVAL, "bad image dimensions");
   ORBHIP_REQUIRE(n_kf >= 0 && kf_fv_n >= 0 && (n_kf == 0 || (kf_desc && kf_valid && kf_angle && kf_Xw)) && (kf_fv_n == 0 || (kf_fv_node && kf_fv_off && kf_fv_idx)), ORBHIP_EINVAL, "NULL keyframe argument");
-  const int icap = orbx_max_keypoints(ctx);
-  ORBHIP_REQUIRE(icap <= TRK_MAXKP, ORBHIP_ECAP, "more than 4096 features per frame");
-  const int nlevels = orbx_get_levels(ctx);
-  ORBHIP_REQUIRE(nlevels > 0 && nlevels <= 16, ORBHIP_EINVAL, "bad level count");
+  int icap = 0, nlevels = 0, rc = 0;
+  if ((rc = trk_dims(ctx, -1, &icap, &nlevels))) return rc;
   TrkFrame& TF = g_trk_frame;
   ThreadWs& W = thread_ws();
-  int rc = W.begin();
-  if (rc) return rc;
-  ORBHIP_REQUIRE(orbhip::orbx_ctx_device(ctx) == W.device, ORBHIP_EINVAL, "the extractor context was created on another device than orbhip_set_default_device() selects");
-  if (TF.device != W.device) { TF = TrkFrame(); TF.device = W.device; }
-  TrfIn I; std::memset(&I, 0, sizeof(I));
-  { double T[16]; for (int k = 0; k < 12; k++) T[k] = Tcw_last[k]; T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1; if (int r2 = ba_matrix4d_to_pose7(T, I.pose7)) return r2; }
-  float scale[16];
-  for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
-  if (int r2 = orbx_get_tables(ctx, scale, nullptr, nullptr, I.inv_sigma2, nullptr)) return r2;
-  I.ratio = nnratio; I.check_ori = check_ori ? 1 : 0; I.nn = kf_fv_n; I.n_kf = n_kf;
-  const uint32_t n_fv_idx = kf_fv_n ? kf_fv_off[kf_fv_n] : 0u;
-  ThreadWs::Pack in;
-  TrkIn PI; std::memset(&PI, 0, sizeof(PI));                   // k_trk_prepare's constants (no queries: it builds the frame's records and grid)
-  for (int k = 0; k < 4; k++) { PI.K4[k] = K4[k]; PI.bounds[k] = bounds[k]; }
-  PI.nlevels = nlevels; std::memcpy(PI.scale, scale, sizeof(scale));
+  if ((rc = trk_begin(W, ctx, TF))) return rc;
   const float* dist5 = img ? trk_distortion_of(ctx) : nullptr;
-  trk_fill_distortion(PI, dist5);
-  const int pI = in.add(&I, sizeof(I)), pP = in.add(&PI, sizeof(PI)), pD = in.add(kf_desc, 32 * (size_t)n_kf), pV = in.add(kf_valid, (size_t)n_kf), pA = in.add(kf_angle, 4 * (size_t)n_kf),
-            pX = in.add(kf_Xw, 24 * (size_t)n_kf), pFn = in.add(kf_fv_node, 4 * (size_t)kf_fv_n), pFo = in.add(kf_fv_off, 4 * ((size_t)kf_fv_n + 1)), pFi = in.add(kf_fv_idx, 4 * (size_t)n_fv_idx);
-  uint8_t* d_img = nullptr;
-  if (img) {
-    ORBHIP_REQUIRE(kps_out && desc_out && cap >= icap, ORBHIP_ECAP, "output capacity below orbx_max_keypoints(ctx)");
-    d_img = W.up<uint8_t>(img, (size_t)stride * (h - 1) + w, &rc);
-  } else {
-    ORBHIP_REQUIRE(TF.valid, ORBHIP_EINVAL, "img == NULL needs the frame of an earlier orbt_* call of this thread on the device");
-    ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels && TF.icap == icap, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
-    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
-  }
-  if (rc || (rc = W.commit(in))) return rc;
-  if (img) {
-    // the same frame block orbt_track_with_motion_model leaves behind: [.. | count | keypoints | descriptors | ..]
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32), oUnd = dist5 ? take(8 * (size_t)icap) : 0;
-    TF.valid = false;
-    if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap)) || (rc = TF.grid.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = TF.grid.idx.ensure((size_t)icap * 4))) return rc;
-    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.oUnd = oUnd; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
-    TF.grid.min_x = bounds[0]; TF.grid.min_y = bounds[2];
-    TF.grid.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); TF.grid.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
-    uint8_t* fb = TF.blk.as<uint8_t>();
-    if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, (orbx_keypoint*)(fb + oKps), fb + oDesc, icap, (int32_t*)(fb + oCnt), (void*)W.s))) return rc;
-    float* d_dummy = W.d<float>(4, &rc); int32_t* d_di = W.d<int32_t>(4, &rc); uint8_t* d_db = W.d<uint8_t>(4, &rc); uint32_t* d_tot = W.d<uint32_t>(1, &rc);
-    if (rc) return rc;
-    trk_prepare_launch(dist5 != nullptr, W.s, (const TrkIn*)in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
-                       (const orbx_keypoint*)(fb + oKps), (const int32_t*)(fb + oCnt), icap, d_dummy, d_dummy, d_di, d_di, d_db, TF.kps4.as<float>(),
-                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot, dist5 ? (float*)(fb + oUnd) : (float*)nullptr);
-  }
-  const uint8_t* fblk = TF.blk.as<uint8_t>();
-  const float* d_kps4 = TF.kps4.as<float>();
-  const int32_t* d_count = (const int32_t*)(fblk + TF.oCnt);
-  const uint8_t* d_fdesc = fblk + TF.oDesc;
+  TrfIn I; std::memset(&I, 0, sizeof(I));
+  TrkIn PI; trk_prepare_consts(PI, K4, bounds, nlevels, dist5);      // (no queries: k_trk_prepare builds the frame's records and grid)
+  if ((rc = trk_pose7(Tcw_last, I.pose7)) || (rc = orbx_get_tables(ctx, PI.scale, nullptr, nullptr, I.inv_sigma2, nullptr))) return rc;
+  for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
+  I.ratio = nnratio; I.check_ori = check_ori ? 1 : 0; I.nn = kf_fv_n; I.n_kf = n_kf;
+  ThreadWs::Pack in;
+  const int pI = in.add(&I, sizeof(I)), pP = in.add(&PI, sizeof(PI)), pX = in.add(kf_Xw, 24 * (size_t)n_kf);
+  const TrfKeyframe kf(in, n_kf, kf_desc, kf_valid, kf_angle, kf_fv_n, kf_fv_node, kf_fv_off, kf_fv_idx);
+  ORBHIP_REQUIRE(!img || (kps_out && desc_out && cap >= icap), ORBHIP_ECAP, "output capacity below orbx_max_keypoints(ctx)");
+  TrkFrameBuild F;
+  if ((rc = F.from_image_or_resident(TF, W, ctx, img, w, h, stride, bounds, nlevels, icap, dist5, in, pP))) return rc;
   const int fcap = TF.icap;
-  // output block: [TrkOut | pose7 | summary | n_inliers | word | weight | node | match_kf | owner | obs_feat | outlier]
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oOut = take(sizeof(TrkOut)), oPose = take(56), oSum = take(sizeof(ba_summary)), oNin = take(4), oWord = take(4 * (size_t)fcap), oWt = take(8 * (size_t)fcap),
-               oNode = take(4 * (size_t)fcap), oMatch = take(4 * (size_t)std::max(n_kf, 1)), oOwner = take(4 * (size_t)fcap), oFeat = take(4 * (size_t)fcap), oOutl = take((size_t)fcap);
-  uint8_t* dblk = W.d<uint8_t>(o, &rc);
+  // output block: [pose tail | word | weight | node | match_kf | owner]
+  Carve C; TrkPoseTail P; TrkBow B;
+  P.carve(C, fcap); B.carve(C, fcap);
+  const size_t oMatch = C.take(4 * (size_t)std::max(n_kf, 1)), oOwner = C.take(4 * (size_t)fcap);
+  uint8_t* dblk = W.d<uint8_t>(C.total, &rc);
   int32_t* d_bin = W.d<int32_t>(fcap, &rc); int* d_hist = W.d<int>(TRK_HISTO + 2, &rc);
-  double* d_oX = W.d<double>(3 * (size_t)fcap, &rc); double* d_ouv = W.d<double>(2 * (size_t)fcap, &rc); float* d_ow = W.d<float>(fcap, &rc);
-  int32_t* d_ooff = W.d<int32_t>(2, &rc); double* d_K4 = W.d<double>(4, &rc);
-  if (rc) return rc;
-  // Frame::ComputeBoW (src/Frame.cc:322-327: levelsup 4); the rows behind the keypoint count are descended too and ignored
-  if ((rc = orbv_descend_device(voc, d_fdesc, fcap, 4, (int32_t*)(dblk + oWord), (double*)(dblk + oWt), (uint32_t*)(dblk + oNode), (void*)W.s))) return rc;
-  const TrfIn* dI = in.dev<TrfIn>(pI);
-  hipLaunchKernelGGL(k_trf_init, dim3((std::max(std::max(n_kf, fcap), 64) + 255) / 256), dim3(256), 0, W.s, (int32_t*)(dblk + oMatch), n_kf, (int32_t*)(dblk + oOwner), d_bin, fcap, d_hist);
-  if (kf_fv_n > 0)
-    hipLaunchKernelGGL(k_trf_bow, dim3(std::max(kf_fv_n, 1)), dim3(64), 0, W.s, dI, in.dev<uint32_t>(pFn), in.dev<uint32_t>(pFo), in.dev<uint32_t>(pFi), in.dev<uint8_t>(pD),
-                       in.dev<uint8_t>(pV), in.dev<float>(pA), d_fdesc, (const uint32_t*)(dblk + oNode), (const double*)(dblk + oWt), d_kps4, d_count, fcap,
-                       (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), d_bin, d_hist);
-  hipLaunchKernelGGL(k_trf_finish, dim3(1), dim3(1024), 0, W.s, dI, d_hist, d_kps4, d_count, fcap, in.dev<double>(pX), (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), d_bin,
-                     (int32_t*)(dblk + oFeat), d_oX, d_ouv, d_ow, d_ooff, (double*)(dblk + oPose), d_K4, (TrkOut*)(dblk + oOut));
-  ORBHIP_CHECK_HIP(hipGetLastError());
-  if ((rc = ba_pose_optimization_batch_device(d_K4, (double*)(dblk + oPose), d_oX, d_ouv, d_ow, d_ooff, 1, dblk + oOutl, (int32_t*)(dblk + oNin), (ba_summary*)(dblk + oSum), (void*)W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, o, &rc);
-  const uint8_t* hf = img ? W.down(fblk, dist5 ? TF.oUnd + (size_t)fcap * 8 : TF.oDesc + (size_t)fcap * 32, &rc) : nullptr;
+  P.alloc(W, fcap, &rc);
+  if (rc || (rc = B.descend(voc, TF, dblk, W.s))) return rc;
+  trf_launch(W.s, in, in.dev<TrfIn>(pI), kf, in.dev<double>(pX), TF, B, dblk, (int32_t*)(dblk + oMatch), (int32_t*)(dblk + oOwner), d_bin, d_hist, (int32_t*)(dblk + P.oFeat), P, (double*)(dblk + P.oPose),
+             (TrkOut*)(dblk + P.oOut));
+  if ((rc = P.solve(dblk, W.s))) return rc;
+  const uint8_t* hb = W.down(dblk, C.total, &rc);
+  const uint8_t* hf = img ? F.down(W, TF, &rc) : nullptr;
   if (rc || (rc = W.sync())) return rc;
-  const TrkOut* T = (const TrkOut*)(hb + oOut);
-  if (T->n_keypoints < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
-  const int n = std::min(T->n_keypoints, fcap);
-  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32);
-             trk_keep_undistorted(TF, dist5, hf + TF.oKps, dist5 ? hf + TF.oUnd : nullptr, n); }
-  if (n != TF.n_kp) { set_error("resident frame changed"); return ORBHIP_EINVAL; }
-  if (bow_word && bow_value && fv_node && fv_idx)
-    orbhip::orbv_merge_host((const int32_t*)(hb + oWord), (const double*)(hb + oWt), (const uint32_t*)(hb + oNode), n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
-  else { *n_words = 0; *n_fv_nodes = 0; fv_off[0] = 0; }
+  int n = 0;
+  if ((rc = F.publish(TF, ctx, img != nullptr, ((const TrkOut*)(hb + P.oOut))->n_keypoints, hf, kps_out, desc_out, &n))) return rc;
+  B.merge(hb, n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
   if (n_kf) std::memcpy(match_kf, hb + oMatch, 4 * (size_t)n_kf);
   std::memcpy(slot_owner, hb + oOwner, 4 * (size_t)n);
-  std::memset(outlier_out, 0, (size_t)n);
-  const int32_t* feat = (const int32_t*)(hb + oFeat);
-  for (int k = 0; k < T->nobs; k++) outlier_out[feat[k]] = hb[oOutl + k];
-  res->n_keypoints = n; res->nmatches = T->nmatches; res->n_correspondences = T->nobs; res->greedy_rounds = 0; res->reserved = 0;
-  std::memcpy(res->pose7, hb + oPose, 56);
-  res->n_inliers = T->nobs < 3 ? 0 : *(const int32_t*)(hb + oNin);
-  if (T->nobs < 3) std::memcpy(res->pose7, I.pose7, 56);
+  P.unpack(hb, I.pose7, n, outlier_out, res);
+  res->greedy_rounds = 0; res->reserved = 0;
   return 0;
 }
 
@@ -1571,32 +1623,23 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
   CallClock call_clock;
   ORBHIP_REQUIRE(ctx && voc && K4 && bounds && n_words && n_fv_nodes && fv_off && n_keypoints && n_cand >= 0 && (n_cand == 0 || (cand && slot_owner && nmatches)), ORBHIP_EINVAL, "NULL argument");
   ORBHIP_REQUIRE(!img || (w > 0 && h > 0 && stride >= w), ORBHIP_EINVAL, "bad image dimensions");
-  const int icap = orbx_max_keypoints(ctx);
-  ORBHIP_REQUIRE(icap <= TRK_MAXKP, ORBHIP_ECAP, "more than 4096 features per frame");
-  ORBHIP_REQUIRE(cap >= icap, ORBHIP_ECAP, "output capacity below orbx_max_keypoints(ctx)");
-  const int nlevels = orbx_get_levels(ctx);
-  ORBHIP_REQUIRE(nlevels > 0 && nlevels <= 16, ORBHIP_EINVAL, "bad level count");
+  int icap = 0, nlevels = 0, rc = 0;
+  if ((rc = trk_dims(ctx, cap, &icap, &nlevels))) return rc;
   for (int i = 0; i < n_cand; i++)
     ORBHIP_REQUIRE(cand[i].n >= 0 && cand[i].fv_n >= 0 && (cand[i].n == 0 || (cand[i].desc && cand[i].valid && cand[i].angle)) &&
                    (cand[i].fv_n == 0 || (cand[i].fv_node && cand[i].fv_off && cand[i].fv_idx)), ORBHIP_EINVAL, "NULL candidate argument");
   TrkFrame& TF = g_trk_frame;
   ThreadWs& W = thread_ws();
-  int rc = W.begin();
-  if (rc) return rc;
-  ORBHIP_REQUIRE(orbhip::orbx_ctx_device(ctx) == W.device, ORBHIP_EINVAL, "the extractor context was created on another device than orbhip_set_default_device() selects");
-  if (TF.device != W.device) { TF = TrkFrame(); TF.device = W.device; }
-  float scale[16], inv_sigma2[16];
-  if (int r2 = orbx_get_tables(ctx, scale, nullptr, nullptr, inv_sigma2, nullptr)) return r2;
-  ThreadWs::Pack in;
-  TrkIn PI; std::memset(&PI, 0, sizeof(PI));
-  for (int k = 0; k < 4; k++) { PI.K4[k] = K4[k]; PI.bounds[k] = bounds[k]; }
-  PI.nlevels = nlevels; std::memcpy(PI.scale, scale, sizeof(scale));
+  if ((rc = trk_begin(W, ctx, TF))) return rc;
   const float* dist5 = img ? trk_distortion_of(ctx) : nullptr;
-  trk_fill_distortion(PI, dist5);
+  float inv_sigma2[16];
+  TrkIn PI; trk_prepare_consts(PI, K4, bounds, nlevels, dist5);
+  if ((rc = orbx_get_tables(ctx, PI.scale, nullptr, nullptr, inv_sigma2, nullptr))) return rc;
+  ThreadWs::Pack in;
   const int pP = in.add(&PI, sizeof(PI));
   std::vector<TrfIn> h_in((size_t)std::max(n_cand, 1));
-  struct Pieces { int d, v, a, fn, fo, fi; };
-  std::vector<Pieces> pc((size_t)std::max(n_cand, 1));
+  std::vector<TrfKeyframe> kf;
+  int max_kf = 1;
   for (int i = 0; i < n_cand; i++) {
     const orbt_reloc_keyframe& q = cand[i];
     TrfIn& I = h_in[i]; std::memset(&I, 0, sizeof(I));
@@ -1604,87 +1647,38 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
     for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
     std::memcpy(I.inv_sigma2, inv_sigma2, sizeof(inv_sigma2));
     I.ratio = nnratio; I.check_ori = check_ori ? 1 : 0; I.nn = q.fv_n; I.n_kf = q.n;
-    const uint32_t nidx = q.fv_n ? q.fv_off[q.fv_n] : 0u;
-    pc[i].d = in.add(q.desc, 32 * (size_t)q.n); pc[i].v = in.add(q.valid, (size_t)q.n); pc[i].a = in.add(q.angle, 4 * (size_t)q.n);
-    pc[i].fn = in.add(q.fv_node, 4 * (size_t)q.fv_n); pc[i].fo = in.add(q.fv_off, 4 * ((size_t)q.fv_n + 1)); pc[i].fi = in.add(q.fv_idx, 4 * (size_t)nidx);
+    kf.push_back(TrfKeyframe(in, q.n, q.desc, q.valid, q.angle, q.fv_n, q.fv_node, q.fv_off, q.fv_idx));
+    max_kf = std::max(max_kf, q.n);
   }
   const int pI = in.add(h_in.data(), sizeof(TrfIn) * (size_t)std::max(n_cand, 1));
-  uint8_t* d_img = nullptr;
-  if (img) d_img = W.up<uint8_t>(img, (size_t)stride * (h - 1) + w, &rc);
-  else {
-    ORBHIP_REQUIRE(TF.valid, ORBHIP_EINVAL, "img == NULL needs the frame of an earlier orbt_* call of this thread on the device");
-    ORBHIP_REQUIRE(TF.made_by(ctx) && TF.nlevels == nlevels && TF.icap == icap, ORBHIP_EINVAL, "ctx is not the extractor that produced the resident frame");
-    ORBHIP_REQUIRE(trk_same_distortion(TF, trk_distortion_of(ctx)), ORBHIP_EINVAL, "orbt_set_distortion changed the coefficients since the resident frame was built");
-  }
-  if (rc || (rc = W.commit(in))) return rc;
-  if (img) {
-    ORBHIP_REQUIRE(kps_out && desc_out, ORBHIP_EINVAL, "NULL output");
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t oCnt = take(4), oKps = take((size_t)icap * sizeof(orbx_keypoint)), oDesc = take((size_t)icap * 32), oUnd = dist5 ? take(8 * (size_t)icap) : 0;
-    TF.valid = false;
-    if ((rc = TF.blk.ensure(o)) || (rc = TF.kps4.ensure(16 * (size_t)icap)) || (rc = TF.grid.off.ensure((size_t)(TRK_NCELL + 1) * 4)) || (rc = TF.grid.idx.ensure((size_t)icap * 4))) return rc;
-    TF.oCnt = oCnt; TF.oKps = oKps; TF.oDesc = oDesc; TF.oUnd = oUnd; TF.icap = icap; TF.nlevels = nlevels; std::memcpy(TF.bounds, bounds, 16);
-    TF.grid.min_x = bounds[0]; TF.grid.min_y = bounds[2];
-    TF.grid.winv = static_cast<float>(FRAME_GRID_COLS) / (bounds[1] - bounds[0]); TF.grid.hinv = static_cast<float>(FRAME_GRID_ROWS) / (bounds[3] - bounds[2]);
-    uint8_t* fb = TF.blk.as<uint8_t>();
-    if ((rc = orbhip::orbx_extract_chained(ctx, d_img, w, h, stride, (orbx_keypoint*)(fb + oKps), fb + oDesc, icap, (int32_t*)(fb + oCnt), (void*)W.s))) return rc;
-    float* d_dummy = W.d<float>(4, &rc); int32_t* d_di = W.d<int32_t>(4, &rc); uint8_t* d_db = W.d<uint8_t>(4, &rc); uint32_t* d_tot = W.d<uint32_t>(1, &rc);
-    if (rc) return rc;
-    trk_prepare_launch(dist5 != nullptr, W.s, (const TrkIn*)in.dev<TrkIn>(pP), (const double*)nullptr, (const int32_t*)nullptr, (const uint8_t*)nullptr,
-                       (const orbx_keypoint*)(fb + oKps), (const int32_t*)(fb + oCnt), icap, d_dummy, d_dummy, d_di, d_di, d_db, TF.kps4.as<float>(),
-                       TF.grid.off.as<uint32_t>(), TF.grid.idx.as<uint32_t>(), 0, d_tot, dist5 ? (float*)(fb + oUnd) : (float*)nullptr);
-  }
-  const uint8_t* fblk = TF.blk.as<uint8_t>();
-  const float* d_kps4 = TF.kps4.as<float>();
-  const int32_t* d_count = (const int32_t*)(fblk + TF.oCnt);
-  const uint8_t* d_fdesc = fblk + TF.oDesc;
+  ORBHIP_REQUIRE(!img || (kps_out && desc_out), ORBHIP_EINVAL, "NULL output");
+  TrkFrameBuild F;
+  if ((rc = F.from_image_or_resident(TF, W, ctx, img, w, h, stride, bounds, nlevels, icap, dist5, in, pP))) return rc;
   const int fcap = TF.icap;
-  int max_kf = 1;
-  for (int i = 0; i < n_cand; i++) max_kf = std::max(max_kf, cand[i].n);
   // output block: [word | weight | node | per candidate {TrkOut, owner[fcap]}]; scratch shared by the candidates (they run one after the other)
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-  const size_t oWord = take(4 * (size_t)fcap), oWt = take(8 * (size_t)fcap), oNode = take(4 * (size_t)fcap);
-  const size_t oOut = take(sizeof(TrkOut) * (size_t)std::max(n_cand, 1)), oOwner = take(4 * (size_t)fcap * std::max(n_cand, 1));
-  uint8_t* dblk = W.d<uint8_t>(o, &rc);
+  Carve C; TrkBow B; TrkPoseTail P;
+  B.carve(C, fcap);
+  const size_t oOut = C.take(sizeof(TrkOut) * (size_t)std::max(n_cand, 1)), oOwner = C.take(4 * (size_t)fcap * std::max(n_cand, 1));
+  uint8_t* dblk = W.d<uint8_t>(C.total, &rc);
   int32_t* d_match = W.d<int32_t>((size_t)max_kf, &rc); int32_t* d_bin = W.d<int32_t>(fcap, &rc); int* d_hist = W.d<int>(TRK_HISTO + 2, &rc);
-  int32_t* d_feat = W.d<int32_t>(fcap, &rc); double* d_oX = W.d<double>(3 * (size_t)fcap, &rc); double* d_ouv = W.d<double>(2 * (size_t)fcap, &rc); float* d_ow = W.d<float>(fcap, &rc);
-  int32_t* d_ooff = W.d<int32_t>(2, &rc); double* d_K4 = W.d<double>(4, &rc); double* d_pose = W.d<double>(7, &rc);
+  int32_t* d_feat = W.d<int32_t>(fcap, &rc); double* d_pose = W.d<double>(7, &rc);
+  P.alloc(W, fcap, &rc);
   double* d_kfX = W.d<double>(3 * (size_t)max_kf, &rc);        // (k_trf_finish gathers PoseOptimization's points: not used here, any readable memory)
   if (rc) return rc;
   ORBHIP_CHECK_HIP(hipMemsetAsync(d_kfX, 0, 24 * (size_t)max_kf, W.s));
-  // Frame::ComputeBoW (src/Frame.cc:322-327: levelsup 4)
-  if ((rc = orbv_descend_device(voc, d_fdesc, fcap, 4, (int32_t*)(dblk + oWord), (double*)(dblk + oWt), (uint32_t*)(dblk + oNode), (void*)W.s))) return rc;
-  for (int i = 0; i < n_cand; i++) {
-    const orbt_reloc_keyframe& q = cand[i];
-    const TrfIn* dI = in.dev<TrfIn>(pI) + i;
-    int32_t* d_owner = (int32_t*)(dblk + oOwner) + (size_t)i * fcap;
-    hipLaunchKernelGGL(k_trf_init, dim3((std::max(std::max(q.n, fcap), 64) + 255) / 256), dim3(256), 0, W.s, d_match, q.n, d_owner, d_bin, fcap, d_hist);
-    if (q.fv_n > 0)
-      hipLaunchKernelGGL(k_trf_bow, dim3(q.fv_n), dim3(64), 0, W.s, dI, in.dev<uint32_t>(pc[i].fn), in.dev<uint32_t>(pc[i].fo), in.dev<uint32_t>(pc[i].fi), in.dev<uint8_t>(pc[i].d),
-                         in.dev<uint8_t>(pc[i].v), in.dev<float>(pc[i].a), d_fdesc, (const uint32_t*)(dblk + oNode), (const double*)(dblk + oWt), d_kps4, d_count, fcap,
-                         d_match, d_owner, d_bin, d_hist);
-    hipLaunchKernelGGL(k_trf_finish, dim3(1), dim3(1024), 0, W.s, dI, d_hist, d_kps4, d_count, fcap, (const double*)d_kfX, d_match, d_owner, d_bin, d_feat, d_oX, d_ouv, d_ow, d_ooff,
-                       d_pose, d_K4, (TrkOut*)(dblk + oOut) + i);
-  }
+  if ((rc = B.descend(voc, TF, dblk, W.s))) return rc;
+  for (int i = 0; i < n_cand; i++)
+    trf_launch(W.s, in, in.dev<TrfIn>(pI) + i, kf[i], d_kfX, TF, B, dblk, d_match, (int32_t*)(dblk + oOwner) + (size_t)i * fcap, d_bin, d_hist, d_feat, P, d_pose, (TrkOut*)(dblk + oOut) + i);
   ORBHIP_CHECK_HIP(hipGetLastError());
-  const uint8_t* hb = W.down(dblk, o, &rc);
-  const uint8_t* hf = img ? W.down(fblk, dist5 ? TF.oUnd + (size_t)fcap * 8 : TF.oDesc + (size_t)fcap * 32, &rc) : W.down(fblk, 256, &rc);
+  const uint8_t* hb = W.down(dblk, C.total, &rc);
+  const uint8_t* hf = img ? F.down(W, TF, &rc) : W.down(TF.blk.as<uint8_t>() + TF.oCnt, 256, &rc) - TF.oCnt;      // (resident frame: its count piece alone)
   if (rc || (rc = W.sync())) return rc;
-  const int n_dev = *(const int32_t*)(hf + TF.oCnt);
-  if (n_dev < 0) { set_error("extractor capacity exceeded"); return ORBHIP_EOVERFLOW; }
-  const int n = std::min(n_dev, fcap);
-  if (img) { TF.n_kp = n; TF.valid = true; TF.producer = ctx; TF.producer_gen = orbhip::orbx_ctx_generation(ctx); std::memcpy(kps_out, hf + TF.oKps, (size_t)n * sizeof(orbx_keypoint)); std::memcpy(desc_out, hf + TF.oDesc, (size_t)n * 32);
-             trk_keep_undistorted(TF, dist5, hf + TF.oKps, dist5 ? hf + TF.oUnd : nullptr, n); }
-  if (n != TF.n_kp) { set_error("resident frame changed"); return ORBHIP_EINVAL; }
+  int n = 0;
+  if ((rc = F.publish(TF, ctx, img != nullptr, *(const int32_t*)(hf + TF.oCnt), hf, kps_out, desc_out, &n))) return rc;
   *n_keypoints = n;
-  if (bow_word && bow_value && fv_node && fv_idx)
-    orbhip::orbv_merge_host((const int32_t*)(hb + oWord), (const double*)(hb + oWt), (const uint32_t*)(hb + oNode), n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
-  else { *n_words = 0; *n_fv_nodes = 0; fv_off[0] = 0; }
+  B.merge(hb, n, bow_word, bow_value, n_words, fv_node, fv_off, fv_idx, n_fv_nodes);
   for (int i = 0; i < n_cand; i++) {
-    const TrkOut* T = (const TrkOut*)(hb + oOut) + i;
-    nmatches[i] = T->nmatches;
+    nmatches[i] = ((const TrkOut*)(hb + oOut) + i)->nmatches;
     std::memcpy(slot_owner + (size_t)i * cap, hb + oOwner + 4 * (size_t)i * fcap, 4 * (size_t)n);
     for (int k = n; k < cap; k++) slot_owner[(size_t)i * cap + k] = -1;
   }

@@ -106,11 +106,8 @@ def test_tracking_step_vs_oracle_composition(oracle, seed, th, kw):
         assert got["nmatches"] > 200 and got["n_inliers"] > 150
 
 
-def test_tracking_step_periodic_texture_many_lookalikes(oracle):
-    """A frame tiled with ONE 20 x 20 patch: every corner has dozens of bit-identical look-alikes inside a th = 40 window, so
-    queries hold more than 16 acceptable candidates (the full-list path of k_trk_windows / k_trk_greedy, the first-minimum rule
-    among equal distances and long chains of contested targets).  Same frame as last and current one, identity motion."""
-    from ceres_mono_orb_slam2_amd import ORBextractor, tracking
+def _periodic_scenario(oracle):
+    """A frame tiled with ONE 20 x 20 patch, the same frame as last and current one, identity motion, every point at 18 m."""
     rng = np.random.default_rng(42)
     patch = (rng.random((20, 20)) < 0.5).astype(np.uint8) * 170 + 40
     patch = np.kron(patch[::4, ::4], np.ones((4, 4), np.uint8))                 # 4-pixel blocks: strong corners
@@ -122,7 +119,16 @@ def test_tracking_step_periodic_texture_many_lookalikes(oracle):
     z = np.full(n, 18.0)
     X = np.stack([(k_last["x"] - K4[2]) / K4[0] * z, (k_last["y"] - K4[3]) / K4[1] * z, z], 1).astype(np.float64)
     valid = np.ones(n, np.uint8); valid[rng.random(n) < 0.2] = 3
-    S = dict(img=img, E=E, X=X, desc=d_last, octave=k_last["octave"].astype(np.int32), angle=k_last["angle"].astype(np.float32), valid=valid, T=np.eye(4))
+    return dict(img=img, E=E, kps=k_last, X=X, desc=d_last, octave=k_last["octave"].astype(np.int32), angle=k_last["angle"].astype(np.float32), valid=valid, T=np.eye(4))
+
+
+def test_tracking_step_periodic_texture_many_lookalikes(oracle):
+    """A frame tiled with ONE 20 x 20 patch: every corner has dozens of bit-identical look-alikes inside a th = 40 window, so
+    queries hold more than 16 acceptable candidates (the full-list path of k_trk_windows / k_trk_greedy, the first-minimum rule
+    among equal distances and long chains of contested targets).  Same frame as last and current one, identity motion."""
+    from ceres_mono_orb_slam2_amd import ORBextractor, tracking
+    S = _periodic_scenario(oracle)
+    img, X, d_last, valid, n = S["img"], S["X"], S["desc"], S["valid"], len(S["X"])
     ex = ORBextractor(2000, 1.2, 8, 20, 7)
     for th in (40.0, 12.0):
         got = tracking.track_with_motion_model(ex, img, K4, BOUNDS, S["T"], X, d_last, S["octave"], S["angle"], valid, th, True)
@@ -133,6 +139,83 @@ def test_tracking_step_periodic_texture_many_lookalikes(oracle):
         assert got["n_inliers"] == exp["n_inliers"] and np.array_equal(got["outlier"], exp["outlier"])
         print("periodic texture th %.0f: %d keypoints, %d matches, %d greedy rounds" % (th, n, got["nmatches"], got["greedy_rounds"]))
     assert n > 500
+
+
+def _full_list_entries(kps, desc, uv, rad, q_valid, q_lo, q_hi, q_desc, dmax):
+    """What k_trk_windows adds up in its list counter: over the valid queries with more than 16 in-window, in-level candidates at a
+    Hamming distance <= dmax, the number of their in-window, in-level candidates (window: |dx| < r and |dy| < r, in float32)."""
+    x, y, oc = kps["x"].astype(F32), kps["y"].astype(F32), kps["octave"].astype(np.int32)
+    popcount = np.array([bin(b).count("1") for b in range(256)], np.int32)
+    total = 0
+    for q in np.nonzero(q_valid)[0]:
+        j = np.nonzero((oc >= q_lo[q]) & (oc <= q_hi[q]) & (np.abs(x - uv[q, 0]) < rad[q]) & (np.abs(y - uv[q, 1]) < rad[q]))[0]
+        if (popcount[desc[j] ^ q_desc[q]].sum(1) <= dmax).sum() > 16:
+            total += len(j)
+    return total
+
+
+def test_window_candidate_lists_regrow_on_a_fresh_thread(oracle):
+    """The second attempt of orbt_track_with_motion_model / orbt_track_local_map: a call whose full candidate lists hold more than
+    64 * n_last (32 * n_mp) entries finds its list buffer too small while the calling thread's high-water mark is still low, raises
+    the mark and runs once more.  A new host thread has new thread-locals, so the first call there starts from the floor; the periodic
+    frame at th = 100 (local map: th = 24, windows of 2.5 * 24 * scale) is far above it - counted here from the oracle's keypoints
+    before anything runs, so the test cannot pass without entering the retry (th = 40 gives 8894 entries against a floor of 128384,
+    th = 80 112730; the local map 28770 / 67709 at th = 16 / 22 against 64192).  Both calls must equal the oracle's composition, and the
+    same call once more on that thread - now with room, no retry - must return the same."""
+    import threading
+    from ceres_mono_orb_slam2_amd import ORBextractor, tracking
+    from tests.test_gpu_track_local_map import _expected as _expected_local_map
+    S = _periodic_scenario(oracle)
+    E, kps, X, desc, octave, valid, T = S["E"], S["kps"], S["X"], S["desc"], S["octave"], S["valid"], S["T"]
+    n = len(X)
+    th, th_lm, ratio = 100.0, 24.0, 0.8
+    uv, rad, v = _project(T, X, valid, octave, E.scale, th)
+    entries = _full_list_entries(kps, desc, uv, rad, v, octave - 1, octave + 1, desc, 100)
+    print("motion model th %.0f: %d full-list entries, floor %d" % (th, entries, 64 * n))
+    assert entries > 64 * n
+    # the local map: the same points, seen head-on from the camera centre (radius factor 2.5), every slot of the frame still empty
+    dist = np.linalg.norm(X, axis=1)
+    maxd = (dist * E.scale[octave]).astype(F32)
+    M = dict(X=X, Pn=X / dist[:, None], mind=(maxd / E.scale[7]).astype(F32), maxd=maxd, D=desc, state=valid, slot_state=np.zeros(n, np.uint8), slot_X=np.zeros((n, 3)))
+    log_scale = F32(np.log(F32(1.2)))
+    iv, uv_lm, lv, vc = oracle.is_in_frustum(T[:3, :3], T[:3, 3], K4, BOUNDS, X, M["Pn"], M["mind"], M["maxd"], 0.5, log_scale, 8)
+    rad_lm = ((np.where(vc > F32(0.998), F32(2.5), F32(4.0)).astype(F32) * F32(th_lm)).astype(F32) * E.scale[lv]).astype(F32)
+    dmax = 100
+    while dmax < 255 and F32(ratio) * F32(dmax + 1) < F32(100): dmax += 1       # (a distance counts while ratio * d < TH_HIGH: it can veto)
+    entries_lm = _full_list_entries(kps, desc, uv_lm.astype(F32), rad_lm, np.where(iv.astype(bool), valid, 0), lv - 1, lv, desc, dmax)
+    print("local map th %.0f: %d full-list entries, floor %d" % (th_lm, entries_lm, 32 * n))
+    assert entries_lm > 32 * n
+    exp = _expected(oracle, S, th)
+    ex = ORBextractor(2000, 1.2, 8, 20, 7)
+    got = []
+    def fresh_thread():
+        try:
+            for _ in range(2):
+                got.append(tracking.track_with_motion_model(ex, S["img"], K4, BOUNDS, T, X, desc, octave, S["angle"], valid, th, True))
+            for _ in range(2):
+                got.append(tracking.track_local_map(ex, K4, BOUNDS, T, log_scale, X, M["Pn"], M["mind"], M["maxd"], desc, valid, M["slot_X"], M["slot_state"], th_lm, ratio))
+        except BaseException as e:
+            got.append(e)
+    t = threading.Thread(target=fresh_thread); t.start(); t.join()
+    for g in got:
+        if isinstance(g, BaseException): raise g
+    first, again, lm_first, lm_again = got
+    assert np.array_equal(first["kps"], exp["kps"])
+    assert first["nmatches"] == exp["nmatches"] and np.array_equal(first["match"], exp["match"])
+    assert np.array_equal(first["owner"], exp["owner"]) and first["n_correspondences"] == exp["ncorr"]
+    assert first["n_inliers"] == exp["n_inliers"] and np.array_equal(first["outlier"], exp["outlier"])
+    for key in ("kps", "desc", "match", "owner", "outlier", "pose7"):
+        assert np.array_equal(first[key], again[key]), key
+    assert (first["nmatches"], first["n_correspondences"], first["n_inliers"]) == (again["nmatches"], again["n_correspondences"], again["n_inliers"])
+    want = _expected_local_map(oracle, S, first, M, T, th_lm, ratio)
+    assert np.array_equal(lm_first["in_view"], want["in_view"]) and np.array_equal(lm_first["match"], want["match"]) and lm_first["nmatches"] == want["nmatches"]
+    assert np.array_equal(lm_first["owner"], want["owner"]) and lm_first["n_correspondences"] == want["ncorr"]
+    assert np.array_equal(lm_first["outlier"], want["outlier"]) and lm_first["n_inliers"] == want["n_inliers"]
+    assert np.allclose(lm_first["pose7"], want["pose7"], rtol=0, atol=1e-7)
+    for key in ("in_view", "match", "owner", "outlier", "pose7"):
+        assert np.array_equal(lm_first[key], lm_again[key]), key
+    assert (lm_first["nmatches"], lm_first["n_correspondences"], lm_first["n_inliers"]) == (lm_again["nmatches"], lm_again["n_correspondences"], lm_again["n_inliers"])
+    print("regrow: motion model %d matches / %d inliers, local map %d matches / %d inliers" % (first["nmatches"], first["n_inliers"], lm_first["nmatches"], lm_first["n_inliers"]))
 
 
 def test_tracking_step_degenerate_inputs(oracle):
