@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "../../include/orbslam_hip.h"
+#include "align.h"
 
 namespace orbhip {
 
@@ -51,12 +52,9 @@ inline int use_default_device() {
 #define ORBHIP_EXP_ENV(name) ((const char*)nullptr)
 #endif
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // One block carved into pieces that each start on a 256-byte boundary (what hipMalloc guarantees, enough for any vector access):
 // take() hands out the piece's offset, `total` is the size of the block so far.  Every packed upload, output block and workspace
-// size in the library is laid out by this rule, so that a size query and the call it sizes cannot drift apart.
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// size in the library is laid out by this rule (align256: align.h), so that a size query and the call it sizes cannot drift apart.
 struct Carve {
   size_t total = 0;
   size_t take(size_t bytes) { const size_t at = total; total = align256(at + bytes); return at; }

@@ -28,48 +28,13 @@
 #include <algorithm>
 #include <new>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
+#include "orb_geometry.h"
 #include "orb_pattern_data.h"
 
 namespace orbhip {
-
-static const int PATCH_SIZE = 31, HALF_PATCH = 15, EDGE_THRESHOLD = 19;
-static const int MAX_LEVELS = 16;
-static const int MAX_INI = 64;            // initial octree nodes per level (round(W/H))
-static const int KEYCAP_MAX = 1 << 23;     // the dense candidate array of a (frame, level) is sized for its theoretical worst case (cells x
-                                           // in-cell NMS density 1/4); this bound only keeps the 24-bit candidate index of the octree's
-                                           // best-key word valid (a 4095 x 4095 level has at most 4.2 M).  ORBHIP_KEYCAP lowers it (test hook)
-
-struct LevelDev {
-  int w, h;
-  int pitch;            // bytes per row of the un-blurred level (level 0: the caller's stride)
-  int bpitch;           // bytes per row of the blurred level
-  long long pyr_off;    // byte offset inside one frame's pyramid block (levels >= 1)
-  long long blur_off;   // byte offset inside one frame's blurred block
-  int minBX, minBY, winW, winH;   // detection window origin and size (maxBorder - minBorder)
-  int cell_begin, ncells;
-  int quota;
-  int nIni; float hX;
-  int ini_x[MAX_INI + 1];
-  float scale; float patch;
-  int kcap; int key_off;          // dense key capacity / offset (in keys) inside one frame's key block
-  int dblk_begin, dblk_count;     // k_describe: first workgroup of this level / number of workgroups (level capacity / DESC_WPB)
-};
-
-struct GeomDev {
-  int nlevels, ncells_total, cell_cap, sel_cap, keys_per_frame, desc_blocks;
-  int tile_w, tile_h, tile_pitch;       // FAST LDS tile (max cell incl. apron)
-  int node_cap, max_cells_level;
-#ifdef ORBHIP_OCT_LEVEL_EXPERIMENT
-  int oct_level_mask;
-#endif
-  long long pyr_frame_bytes, blur_frame_bytes;
-  LevelDev lv[MAX_LEVELS];
-};
-
-struct alignas(16) CellDesc { short level, x0, y0, x1, y1, offx, offy, pad; };   // 16-byte aligned: read with one scalar load
-struct alignas(8) BlurTile { short level, tx, ty, pad; };
 
 // ---------------------------------------------------------------------------- device helpers
 __device__ __forceinline__ const uint8_t* level_ptr(const GeomDev& G, int l, int f, const uint8_t* img0,
@@ -216,16 +181,13 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
 // needs, the workgroup's share of the level itself), from the level below held in LDS; it writes every pixel of its boxes, so
 // neighbouring workgroups write their overlap twice - the same bytes (a pixel is one fixed function of four source pixels,
 // k_resize's arithmetic).  1.7x the arithmetic of the level launches, 1/7 of the launches.  The boxes come from the host
-// (prepare(): they depend on the geometry only).
+// (plan_cone, orb_geometry.h: they depend on the geometry only).
 #ifdef ORBHIP_CONE_PROF
 __device__ unsigned long long g_cone_ticks[24];
 #define CONE_MARK(i) do { if (blockIdx.x == 77 && threadIdx.x == 0) g_cone_ticks[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define CONE_MARK(i) do { } while (0)
 #endif
-#define CONE_TPB 1024     /* a lone wave per SIMD issues one instruction per ~4.5 cycles: four waves per SIMD share the work of a cone */
-#define CONE_MAXL 8        /* pyramid levels the cone kernel handles (its table registers are unrolled over the levels) */
-#define CONE_SRC_PT 12      /* bytes of the level 0 box a thread loads (all requested at once) */
 struct ConeLevel { int sw, dw, dpitch, pad; long long doff; const uint2* xtab; const int* yofs; const short* ibeta; int sh, dh; };
 struct ConeArgs { ConeLevel lv[MAX_LEVELS]; int nl, spitch0, buf0, bufk; };      // buf0 / bufk: bytes of the LDS image buffers (level 0 box / larger of the others)
 __global__ __launch_bounds__(CONE_TPB) void k_pyr_cone(ConeArgs A, const short* __restrict__ boxes, const uint8_t* __restrict__ img, uint8_t* __restrict__ pyr, int* __restrict__ status) {
@@ -246,12 +208,12 @@ __global__ __launch_bounds__(CONE_TPB) void k_pyr_cone(ConeArgs A, const short* 
       tc[l] = make_uint2(0u, 0u); ty[l] = 0; tb[l] = 0;
       if (l < nl) {
         const ConeLevel& L = A.lv[l];
-        const int x0 = B[4 * l], y0 = B[4 * l + 1], rw = B[4 * l + 2] - x0, rh = B[4 * l + 3] - y0;      // (<= 256 each: prepare())
+        const int x0 = B[4 * l], y0 = B[4 * l + 1], rw = B[4 * l + 2] - x0, rh = B[4 * l + 3] - y0;      // (<= 256 each: cone_box_fits)
         if (tid < rw) tc[l] = L.xtab[x0 + tid];
         if (tid < rh) { ty[l] = L.yofs[y0 + tid]; tb[l] = *(const int*)(L.ibeta + 2 * (y0 + tid)); }
       }
     }
-    const int x0 = B[0], y0 = B[1], rw = B[2] - x0, n0 = rw * (B[3] - y0);      // (<= CONE_TPB * CONE_SRC_PT bytes: prepare())
+    const int x0 = B[0], y0 = B[1], rw = B[2] - x0, n0 = rw * (B[3] - y0);      // (<= CONE_TPB * CONE_SRC_PT bytes: cone_box_fits)
     uint8_t v[CONE_SRC_PT];
 #pragma unroll
     for (int u = 0; u < CONE_SRC_PT; u++) {
@@ -668,18 +630,7 @@ template <> struct OctT<true> {
   static __device__ __forceinline__ void add(cc_t* cc, int p, int q) { atomicAdd(&cc[p].x + q, 1u); }
   static __device__ __forceinline__ void get(const cc_t& v, int c4[4]) { c4[0] = (int)v.x; c4[1] = (int)v.y; c4[2] = (int)v.z; c4[3] = (int)v.w; }
 };
-// Node arrays of one (frame, level) workgroup.  LDS instantiation with 16-bit counters: 44 bytes per node, so that the 442 nodes of
-// nfeatures = 2000 take 19.3 kB and EIGHT workgroups share a CU's 160 kB - all 2048 workgroups of a 256-frame batch are resident at
-// once (at 50 bytes per node plus a separate cell-prefix array only six fitted and the kernel ran in two rounds).  The scan
-// arrays are 16-bit there (values <= 4 node_cap), the cell-prefix array of the gather phase lies over everything behind rect[0]
-// (nothing else is live yet), the final-phase sort keys and the processing order share the childpos rows (dead until phase G),
-// the best-key array the child-count rows (dead after the last sweep).
-static size_t octree_lds_bytes(int node_cap, int max_cells_level, bool wide, bool gmem) {
-  const size_t scan_b = (wide || gmem) ? 4 : 2;
-  const size_t per_node = 8 * 2 + (wide ? 16 : 8) + 8 + 2 * scan_b + (wide ? 4 : 2) * 2 + 2 + 2;
-  const size_t nodes = (size_t)node_cap * per_node, pref = (size_t)node_cap * 8 + (size_t)(max_cells_level + 8) * 4;
-  return std::max(nodes, pref) + 16;
-}
+// (octree_lds_bytes, orb_geometry.h, sizes the node arrays carved below.)
 // GMEM: the node arrays live in a global scratch row of the (frame, level) workgroup instead of LDS - the fallback for per-level
 // quotas whose node arrays exceed the 160 kB of LDS (about 3200 keypoints in one level, i.e. nfeatures beyond ~15000; the
 // reference has no such limit).  Same code, same order of operations, slower memory.
@@ -1016,8 +967,6 @@ __global__ __launch_bounds__(OCT_TPB) void k_octree_pair(GeomDev G, const int* _
 }
 
 // ---------------------------------------------------------------------------- k_blur7
-#define BLUR_TW 128
-#define BLUR_TH 64
 #if !defined(BLUR_COL_SLIDE) || !defined(ORBHIP_EXPERIMENTS)
 #undef BLUR_COL_SLIDE
 #define BLUR_COL_SLIDE 0      // 1: a thread owns eight CONSECUTIVE output rows (14 LDS reads + 56 unpacks per thread instead of 56 + 224, bit-exact) - 0.407 ms against 0.392
@@ -1127,11 +1076,6 @@ __global__ __launch_bounds__(256) void k_blur7(GeomDev G, const BlurTile* __rest
 // The index k inside an instruction pairs byte j of lane group g of A with byte j of lane group g of B (csrc/orb_matcher.hip), so
 // "k = 16 g + j" below is a convention the Toeplitz tables (host-built, g_blur_toep) share with the source operand.
 // VALU per wave: ~16 per source operand, 6 per four row sums (pack + sign), 11 per four outputs: ~7 lane-instructions per pixel.
-#define BM_TW 192                   /* output columns per workgroup (4 waves x 48) */
-#define BM_TH 58                    /* output rows per chunk */
-#define BM_RC 4                     /* chunks (of 58 rows) a wave walks down its 48 columns: the Toeplitz operands are loaded once, the next
-                                       chunk's source is in flight during the products (one-chunk waves were dispatch- and latency-bound:
-                                       0.425 ms per 256 frames at 26 % VALU-busy) */
 typedef int bm_v4i __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(1))) bm_u128 { uint32_t x, y, z, w; };     // a 16-byte load with no alignment promise
 typedef uint32_t bm_u32x3 __attribute__((ext_vector_type(3), aligned(4)));        // 12 bytes, 4-byte aligned: one global_store_dwordx3
@@ -1395,7 +1339,6 @@ __device__ __forceinline__ void desc_patch_load(const uint8_t* base_al, uint32_t
   }
 }
 
-#define DESC_WPB 4      // keypoints (= waves) per workgroup (1 / 2 / 4 / 8 / 16: 0.575 / 0.548 / 0.530 / 0.551 / 0.587 ms)
 __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(GeomDev G, const uint32_t* __restrict__ sel,
                                                   const int* __restrict__ sel_cnt, const int* __restrict__ status,
                                                   const uint8_t* __restrict__ img0, long long img_frame_bytes,
@@ -1566,8 +1509,6 @@ __global__ __launch_bounds__(64 * DESC_WPB) void k_describe(GeomDev G, const uin
 }
 
 // ============================================================================ host side
-inline int cv_round(double v) { return (int)std::nearbyint(v); }
-
 }  // namespace orbhip
 
 using namespace orbhip;
@@ -1577,34 +1518,21 @@ struct orbx_ctx {
   const unsigned long long generation = ++g_ctx_generation;      // a resident frame remembers (pointer, generation): a context re-created at the same address is another producer
   int nfeatures, nlevels, iniTh, minTh, device;
   double scaleFactor;
-  std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
-  std::vector<int> quota, umax;
-  float atan_p[4], factorPI;
+  ScaleTables S;                      // scale / sigma tables, quotas, umax, the atan polynomial: functions of the parameters alone
   // shape-dependent state
   int w = 0, h = 0, stride = 0, nframes = 0;
-  GeomDev G;
-  std::vector<CellDesc> cells;
-  std::vector<BlurTile> btiles, mtiles, mtiles1;      // k_blur7's 128 x 64 tiles, k_blur7_mfma's strips of BM_RC chunks (batches) / of one chunk (a lone frame: latency)
+  ExtractorPlan P;                    // geometry, cell and tile lists, table offsets, launch and LDS sizes of (w, h, stride): plan_extractor
   DevBuf d_cells, d_btiles, d_mtiles, d_mtiles1, d_tab;      // tables
   int blur_mfma = 1;                  // k_blur7_mfma (default) / k_blur7 (ORBHIP_BLUR_MFMA=0: the VALU kernel, for A/B runs)
-  std::vector<size_t> tab_xofs, tab_ialpha, tab_yofs, tab_ibeta;   // byte offsets into d_tab per level
-  struct RmHost { size_t oW = 0, oC = 0, oC0 = 0, oRow = 0; int nchunks = 0, nblocks = 0; bool ok = false; };
-  std::vector<RmHost> rm;              // k_resize_mfma's tables per level (ok = false: the level takes k_resize)
-  int resize_mfma = 1;                 // ORBHIP_RESIZE_MFMA=0: every level on the VALU kernel k_resize (A/B runs)
-  size_t tab_cone = 0; int cone_wgs = 0, cone_buf0 = 0, cone_bufk = 0; size_t cone_lds = 0;      // k_pyr_cone: boxes in d_tab, grid, LDS layout (cone_wgs == 0: not available)
+  int resize_mfma = 1;                // ORBHIP_RESIZE_MFMA=0: every level on the VALU kernel k_resize (A/B runs)
   DevBuf d_pyr, d_blur, d_cellcnt, d_cellkps, d_keys, d_knode, d_sel, d_selcnt, d_nkeys, d_status, d_octnodes;
   DevBuf d_img, d_out;                     // host-API staging: image; {counts | keypoints | descriptors} in one block
   void* h_pin = nullptr; size_t h_bytes = 0;   // pinned host mirror of both
-  size_t fast_lds = 0, octree_lds = 0, octree_lds_wide = 0;
-  bool octree_wide = false;           // some level can hold > 65535 candidates: 32-bit node counters (k_octree<true, .>)
   int fast_xcd = 1;                   // k_fast_cells with frame f on XCD f % 8 (batches of a multiple of 8 frames).  Round 5: default - with the kernel
                                       // VALU-bound the mapping costs nothing any more (176.3 k against 175.2 k frames/s) and its 36-byte tile rows
                                       // meet their 128-byte lines in ONE L2: FETCH_SIZE 860 -> 164 MB per 256-frame launch (ORBHIP_FAST_XCD=0 in
                                       // an experiments build restores the plain order; rounds 1-2 measured it 40 % slower, latency-bound then)
-  bool fast_narrow = false;           // k_fast_cells<true>: all cell interiors <= 32 px wide
   int desc_xcd = 1;                   // k_describe: frame f on XCD f % 8 (ORBHIP_DESC_XCD=0 restores the plain order)
-  bool octree_gmem = false;           // node arrays larger than the LDS: global scratch rows (k_octree<., true>)
-  size_t octree_row = 0;
   // last call (for introspection)
   const uint8_t* last_img0 = nullptr; long long last_img_frame_bytes = 0; int last_nframes = 0;
   bool const_uploaded = false;
@@ -1620,35 +1548,60 @@ struct orbx_ctx {
   int overlap_blur = -1;       // -1: by batch size (see run_batch); 0: one stream; 1: k_blur7 on the side stream beside FAST + octree; 2: beside the octree only
 };
 
-static int build_tables(orbx_ctx* c) {
-  const int nl = c->nlevels;
-  c->scale.resize(nl); c->sigma2.resize(nl); c->inv_scale.resize(nl); c->inv_sigma2.resize(nl);
-  c->scale[0] = 1.0f; c->sigma2[0] = 1.0f;
-  for (int i = 1; i < nl; i++) {
-    c->scale[i] = (float)(c->scale[i - 1] * c->scaleFactor);        // src/ORBextractor.cc:421
-    c->sigma2[i] = c->scale[i] * c->scale[i];
+// grow a device buffer to hold a host vector (at least min_bytes) and copy it
+template <typename T>
+static int upload(DevBuf& d, const std::vector<T>& v, size_t min_bytes = 0) {
+  if (int rc = d.ensure(std::max(v.size() * sizeof(T), min_bytes))) return rc;
+  if (!v.empty()) ORBHIP_CHECK_HIP(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// a new image shape: plan it (orb_geometry.h), upload the plan's tables, raise the octree's LDS limits
+static int replan(orbx_ctx* c, int w, int h, int stride) {
+  int keycap_max = KEYCAP_MAX;
+  if (const char* e = std::getenv("ORBHIP_KEYCAP")) keycap_max = std::max(64, std::min(KEYCAP_MAX, atoi(e)));   // test hook for the overflow path
+  const ExtractorParams prm = {c->nlevels, c->S.inv_scale.data(), c->S.scale.data(), c->S.quota.data()};
+  ExtractorPlan fresh;
+  const char* why = "";
+  if (int rc = plan_extractor(prm, w, h, stride, keycap_max, &fresh, &why)) { set_error("%s", why); return rc; }   // (the context keeps its shape)
+  ExtractorPlan& P = c->P = std::move(fresh);
+  c->w = c->h = c->stride = c->nframes = 0;                  // (no shape until the tables are in place too)
+#ifdef ORBHIP_OCT_LEVEL_EXPERIMENT
+  P.G.oct_level_mask = ORBHIP_EXP_ENV("ORBHIP_OCT_LEVELS") ? (int)strtol(ORBHIP_EXP_ENV("ORBHIP_OCT_LEVELS"), nullptr, 0) : 0xFFFF;
+#endif
+  if (int rc = upload(c->d_cells, P.cells, sizeof(CellDesc))) return rc;
+  if (int rc = upload(c->d_btiles, P.btiles)) return rc;
+  if (int rc = upload(c->d_mtiles, P.mtiles)) return rc;
+  if (int rc = upload(c->d_mtiles1, P.mtiles1)) return rc;
+  if (int rc = upload(c->d_tab, P.tab, 16)) return rc;
+  std::vector<uint8_t>().swap(P.tab);                        // (the device copy is the one in use)
+  if (!P.octree_gmem && P.octree_lds > 64 * 1024)
+    if (int rc = raise_dynamic_lds((const void*)k_octree<false, false>, c->device, P.octree_lds)) return rc;
+  if (!P.octree_gmem && P.octree_wide && P.octree_lds_wide > 64 * 1024)
+    if (int rc = raise_dynamic_lds((const void*)k_octree<true, false>, c->device, P.octree_lds_wide)) return rc;
+  c->w = w; c->h = h; c->stride = stride;
+  return 0;
+}
+
+// once per context: the BRIEF pattern, umax and k_blur7_mfma's Toeplitz operands
+static int upload_constants(orbx_ctx* c) {
+  ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), ORB_BIT_PATTERN_31, 1024));
+  ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_umax), c->S.umax.data(), 16 * sizeof(int)));
+  // k_blur7_mfma's Toeplitz operands (see the kernel): lane (n, g), byte j <-> k = 16 g + j
+  std::vector<int8_t> T((size_t)2 * 7 * 64 * 16, 0);
+  for (int var = 0; var < 2; var++) {
+    const int taps[7] = {18, 34, var ? 48 : 49, var ? 56 : 55, var ? 48 : 49, 34, 18};
+    for (int q = 0; q < 7; q++)
+      for (int lane = 0; lane < 64; lane++)
+        for (int j = 0; j < 16; j++) {
+          const int n = lane & 15, kk = 16 * (lane >> 4) + j;
+          const int ti = q < 3 ? kk - (12 * (n >> 2) + 4 * q + (n & 3)) - 1      // row pass, block q: output column c + 12 (n >> 2) + 4 q + (n & 3), source column c - 4 + kk
+                               : kk - (16 * (q - 3) + n);                         // column pass, block s = q - 3: output row R0 + 3 + 16 s + n, source row R0 + kk
+          T[(((size_t)var * 7 + q) * 64 + lane) * 16 + j] = (int8_t)((ti >= 0 && ti <= 6) ? taps[ti] : 0);
+        }
   }
-  for (int i = 0; i < nl; i++) { c->inv_scale[i] = 1.0f / c->scale[i]; c->inv_sigma2[i] = 1.0f / c->sigma2[i]; }
-  c->quota.resize(nl);
-  float factor = (float)(1.0f / c->scaleFactor);
-  float nDesired = c->nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nl));
-  int sum = 0;
-  for (int l = 0; l < nl - 1; l++) { c->quota[l] = cv_round(nDesired); sum += c->quota[l]; nDesired *= factor; }
-  c->quota[nl - 1] = std::max(c->nfeatures - sum, 0);
-  c->umax.assign(HALF_PATCH + 1, 0);
-  int v, v0, vmax = (int)std::floor(HALF_PATCH * std::sqrt(2.f) / 2 + 1);
-  int vmin = (int)std::ceil(HALF_PATCH * std::sqrt(2.f) / 2);
-  const double hp2 = HALF_PATCH * HALF_PATCH;
-  for (v = 0; v <= vmax; ++v) c->umax[v] = cv_round(std::sqrt(hp2 - v * v));
-  for (v = HALF_PATCH, v0 = 0; v >= vmin; --v) {
-    while (c->umax[v0] == c->umax[v0 + 1]) ++v0;
-    c->umax[v] = v0;
-    ++v0;
-  }
-  const float k = (float)(180.0 / 3.14159265358979323846);
-  c->atan_p[0] = 0.9997878412794807f * k; c->atan_p[1] = -0.3258083974640975f * k;
-  c->atan_p[2] = 0.1555786518463281f * k; c->atan_p[3] = -0.04432655554792128f * k;
-  c->factorPI = (float)(3.14159265358979323846 / 180.f);
+  ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blur_toep), T.data(), T.size()));
+  c->const_uploaded = true;
   return 0;
 }
 
@@ -1656,288 +1609,10 @@ static int build_tables(orbx_ctx* c) {
 static int prepare(orbx_ctx* c, int w, int h, int stride, int nframes) {
   const bool same_shape = (c->w == w && c->h == h && c->stride == stride);
   if (same_shape && nframes <= c->nframes) return 0;
-  ORBHIP_REQUIRE(w >= 2 * EDGE_THRESHOLD + 8 && h >= 2 * EDGE_THRESHOLD + 8, ORBHIP_EINVAL, "image too small");
-  ORBHIP_REQUIRE(w <= 4095 && h <= 4095, ORBHIP_EINVAL, "image larger than 4095 px per side");
-  const int nl = c->nlevels;
-  GeomDev& G = c->G;
-  if (!same_shape) {
-    std::memset(&G, 0, sizeof(G));
-    G.nlevels = nl;
-    c->cells.clear(); c->btiles.clear(); c->mtiles.clear(); c->mtiles1.clear();
-    long long pyr_off = 0, blur_off = 0;
-    int key_off = 0, tile_w = 8, tile_h = 8, cell_cap = 1, max_cells = 1, node_cap = MAX_INI + 8, sel_cap = 8, desc_blocks = 0;
-    std::vector<uint8_t> tab;
-    std::vector<std::vector<int>> h_xofs, h_yofs;                 // (host copies for the cone boxes below)
-    c->tab_xofs.assign(nl, 0); c->tab_ialpha.assign(nl, 0); c->tab_yofs.assign(nl, 0); c->tab_ibeta.assign(nl, 0);
-    for (int l = 0; l < nl; l++) {
-      LevelDev& L = G.lv[l];
-      float s = c->inv_scale[l];
-      L.w = cv_round((float)w * s); L.h = cv_round((float)h * s);      // src/ORBextractor.cc:1112
-      ORBHIP_REQUIRE(L.w >= 1 && L.h >= 1, ORBHIP_EINVAL, "image too small for the requested number of pyramid levels");
-      L.pitch = (l == 0) ? stride : round_up(L.w, 64);
-      L.bpitch = round_up(L.w, 64);
-      L.pyr_off = pyr_off; if (l > 0) pyr_off += (long long)L.pitch * L.h;
-      L.blur_off = blur_off; blur_off += (long long)L.bpitch * L.h;
-      L.scale = c->scale[l];
-      L.patch = (float)(int)(PATCH_SIZE * c->scale[l]);                 // :837
-      L.quota = c->quota[l];
-      // detection window and cell grid (:773-787)
-      const int minBX = EDGE_THRESHOLD - 3, minBY = minBX;
-      const int maxBX = L.w - EDGE_THRESHOLD + 3, maxBY = L.h - EDGE_THRESHOLD + 3;
-      L.minBX = minBX; L.minBY = minBY; L.winW = maxBX - minBX; L.winH = maxBY - minBY;
-      const float W = 30;
-      const float width = (float)(maxBX - minBX), height = (float)(maxBY - minBY);
-      const int nCols = (int)(width / W), nRows = (int)(height / W);
-      L.cell_begin = (int)c->cells.size();
-      if (nCols >= 1 && nRows >= 1) {
-        const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
-        for (int i = 0; i < nRows; i++) {
-          const float iniY = (float)(minBY + i * hCell);
-          float maxY = iniY + hCell + 6;
-          if (iniY >= maxBY - 3) continue;
-          if (maxY > maxBY) maxY = (float)maxBY;
-          for (int j = 0; j < nCols; j++) {
-            const float iniX = (float)(minBX + j * wCell);
-            float maxX = iniX + wCell + 6;
-            if (iniX >= maxBX - 6) continue;
-            if (maxX > maxBX) maxX = (float)maxBX;
-            CellDesc cd;
-            cd.level = (short)l; cd.x0 = (short)iniX; cd.y0 = (short)iniY; cd.x1 = (short)maxX; cd.y1 = (short)maxY;
-            cd.offx = (short)(j * wCell); cd.offy = (short)(i * hCell); cd.pad = 0;
-            c->cells.push_back(cd);
-            int tw = cd.x1 - cd.x0, th = cd.y1 - cd.y0;
-            tile_w = std::max(tile_w, tw); tile_h = std::max(tile_h, th);
-            int iw = std::max(tw - 6, 0), ih = std::max(th - 6, 0);
-            cell_cap = std::max(cell_cap, ((iw + 1) / 2) * ((ih + 1) / 2));
-          }
-        }
-      }
-      L.ncells = (int)c->cells.size() - L.cell_begin;
-      max_cells = std::max(max_cells, L.ncells);
-      // octree initial nodes (:543-563)
-      // (levels too small to hold a cell produce no candidates; the reference divides by zero there)
-      int nIni = (L.ncells > 0) ? (int)std::round(static_cast<float>(L.winW) / L.winH) : 1;
-      if (nIni < 1) nIni = 1;
-      ORBHIP_REQUIRE(nIni <= MAX_INI, ORBHIP_EINVAL, "aspect ratio too extreme (more than 64 initial octree nodes)");
-      L.nIni = nIni;
-      L.hX = (L.ncells > 0) ? static_cast<float>(L.winW) / nIni : 1.0f;
-      for (int i = 0; i <= nIni; i++) L.ini_x[i] = (int)(L.hX * static_cast<float>(i));
-      node_cap = std::max(node_cap, std::max(L.quota + 8, 4 * nIni + 8));
-      sel_cap = std::max(sel_cap, std::max(L.quota + 4, 4 * nIni + 4));   // the first octree sweep can return 4 * nIni > N nodes
-      L.dblk_begin = desc_blocks; L.dblk_count = (std::max(L.quota + 4, 4 * nIni + 4) + 2 * DESC_WPB - 1) / (2 * DESC_WPB); desc_blocks += L.dblk_count;
-      long long theo = (long long)L.ncells * cell_cap;
-      int keycap_max = KEYCAP_MAX;
-      if (const char* e = std::getenv("ORBHIP_KEYCAP")) keycap_max = std::max(64, std::min(KEYCAP_MAX, atoi(e)));   // test hook for the overflow path
-      L.kcap = (int)std::min<long long>(std::max<long long>(theo, 64), keycap_max);
-      L.key_off = key_off; key_off += round_up(L.kcap, 4);
-      // resize tables: level l from level l-1
-      if (l > 0) {
-        const int sw = G.lv[l - 1].w, sh = G.lv[l - 1].h, dw = L.w, dh = L.h;
-        double inv_scale_x = (double)dw / sw, inv_scale_y = (double)dh / sh;
-        double scale_x = 1. / inv_scale_x, scale_y = 1. / inv_scale_y;
-        std::vector<int> xofs(dw), yofs(dh);
-        std::vector<short> ia(2 * dw), ib(2 * dh);
-        h_xofs.resize(nl); h_yofs.resize(nl);
-        auto sat = [](int v) { return (short)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); };
-        for (int dx = 0; dx < dw; dx++) {
-          float fx = (float)((dx + 0.5) * scale_x - 0.5);
-          int sx = (int)std::floor(fx);
-          fx -= sx;
-          if (sx < 0) { fx = 0; sx = 0; }
-          if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-          xofs[dx] = sx;
-          ia[2 * dx] = sat(cv_round((1.f - fx) * 2048)); ia[2 * dx + 1] = sat(cv_round(fx * 2048));
-        }
-        for (int dy = 0; dy < dh; dy++) {
-          float fy = (float)((dy + 0.5) * scale_y - 0.5);
-          int sy = (int)std::floor(fy);
-          fy -= sy;
-          yofs[dy] = sy;
-          ib[2 * dy] = sat(cv_round((1.f - fy) * 2048)); ib[2 * dy + 1] = sat(cv_round(fy * 2048));
-        }
-        auto push = [&](const void* p, size_t bytes) {
-          size_t off = (tab.size() + 15) / 16 * 16;
-          tab.resize(off + bytes);
-          std::memcpy(tab.data() + off, p, bytes);
-          return off;
-        };
-        const int dw4 = round_up(dw, 4);                      // padded with copies of the last column: a thread reads its 4 entries as two 16-byte loads
-        std::vector<uint32_t> xt(2 * (size_t)dw4);
-        for (int dx4 = 0; dx4 < dw4; dx4++) {
-          const int dx = std::min(dx4, dw - 1);
-          xt[2 * dx4] = (uint32_t)(xofs[dx] & 0xFFFF) | ((uint32_t)(uint16_t)ia[2 * dx] << 16);
-          xt[2 * dx4 + 1] = (uint32_t)(uint16_t)ia[2 * dx] | ((uint32_t)(uint16_t)ia[2 * dx + 1] << 16);   // both weights, v_dot2 operand order
-        }
-        c->tab_xofs[l] = push(xt.data(), xt.size() * 4);
-        c->tab_ialpha[l] = 0;
-        c->tab_yofs[l] = push(yofs.data(), yofs.size() * 4);
-        c->tab_ibeta[l] = push(ib.data(), ib.size() * 2);
-        h_xofs[l] = xofs; h_yofs[l] = yofs;
-        // ---- k_resize_mfma's tables (see the kernel): per 48-column chunk the weight digits as MFMA A operands + the accumulator
-        // start values, per source row the output row it is sy0 of.  Conditions, checked here: a chunk's source span fits 64 columns
-        // (true for scale factors up to ~1.3), yofs strictly increasing and non-negative (true for every downscale).
-        {
-          if (c->rm.size() != (size_t)nl) c->rm.assign(nl, orbx_ctx::RmHost());
-          orbx_ctx::RmHost& M = c->rm[l];
-          M = orbx_ctx::RmHost();
-          const int nchunks = (dw + 47) / 48;
-          bool ok = true;
-          std::vector<int> c0(nchunks);
-          for (int t = 0; t < nchunks && ok; t++) {
-            const int lo = xofs[48 * t], hi = std::min(xofs[std::min(48 * t + 47, dw - 1)] + 1, sw - 1);
-            c0[t] = lo & ~3;
-            if (hi - c0[t] > 63) ok = false;
-          }
-          for (int dy = 0; dy < dh && ok; dy++) if (yofs[dy] < 0 || (dy > 0 && yofs[dy] <= yofs[dy - 1])) ok = false;
-          for (int dx = 0; dx < 2 * dw && ok; dx++) if (ia[dx] < 0 || ia[dx] > 2048) ok = false;
-          for (int dy = 0; dy < 2 * dh && ok; dy++) if (ib[dy] < 0 || ib[dy] > 2048) ok = false;
-          if (ok) {
-            std::vector<int8_t> W((size_t)nchunks * 6 * 64 * 16, 0);
-            std::vector<int32_t> Cc((size_t)nchunks * 3 * 16, 0);
-            for (int t = 0; t < nchunks; t++)
-              for (int cb = 0; cb < 3; cb++)
-                for (int m = 0; m < 16; m++) {
-                  const int dx = 48 * t + 12 * (m >> 2) + 4 * cb + (m & 3);
-                  if (dx >= dw) continue;
-                  const int s0 = xofs[dx], s1 = std::min(xofs[dx] + 1, sw - 1);
-                  const int wgt[2] = {ia[2 * dx], ia[2 * dx + 1]}, col[2] = {s0, s1};
-                  Cc[((size_t)t * 3 + cb) * 16 + m] = 128 * (wgt[0] + wgt[1]);
-                  for (int e = 0; e < 2; e++) {
-                    const int k = col[e] - c0[t];                       // (0 .. 63: checked above)
-                    const size_t lane = (size_t)m + 16 * (k >> 4), byte = (size_t)(k & 15);
-                    int8_t* wh = &W[(((size_t)t * 6 + 2 * cb) * 64 + lane) * 16 + byte];
-                    int8_t* wl = &W[(((size_t)t * 6 + 2 * cb + 1) * 64 + lane) * 16 + byte];
-                    // (s1 == s0 at the right border: the two weights meet in one column and add up - a1 is 0 there)
-                    const int tot = 32 * (int)*wh + (int)*wl + wgt[e];
-                    *wh = (int8_t)(tot >> 5); *wl = (int8_t)(tot & 31);
-                  }
-                }
-            const int smax = yofs[dh - 1], nblocks = (smax + 1 + 14) / 15;
-            std::vector<uint32_t> rowtab(2 * ((size_t)15 * nblocks + 1), 0);
-            for (size_t s2 = 0; s2 < rowtab.size() / 2; s2++) rowtab[2 * s2] = 0xFFFFFFFFu;        // dy = -1
-            for (int dy = 0; dy < dh; dy++) { rowtab[2 * (size_t)yofs[dy]] = (uint32_t)dy; rowtab[2 * (size_t)yofs[dy] + 1] = (uint32_t)(uint16_t)ib[2 * dy] | ((uint32_t)(uint16_t)ib[2 * dy + 1] << 16); }
-            M.oW = push(W.data(), W.size()); M.oC = push(Cc.data(), Cc.size() * 4); M.oC0 = push(c0.data(), c0.size() * 4); M.oRow = push(rowtab.data(), rowtab.size() * 4);
-            M.nchunks = nchunks; M.nblocks = nblocks; M.ok = true;
-          }
-        }
-      }
-      // blur tiles
-      for (int ty = 0; ty < (L.h + BLUR_TH - 1) / BLUR_TH; ty++)
-        for (int tx = 0; tx < (L.w + BLUR_TW - 1) / BLUR_TW; tx++) {
-          BlurTile bt; bt.level = (short)l; bt.tx = (short)tx; bt.ty = (short)ty; bt.pad = 0;
-          c->btiles.push_back(bt);
-        }
-      for (int ty = 0, nty = (L.h + BM_TH - 1) / BM_TH; ty < nty; ty += BM_RC)       // k_blur7_mfma: ty = first 58-row chunk, pad = chunks of the workgroup
-        for (int tx = 0; tx < (L.w + BM_TW - 1) / BM_TW; tx++) {
-          BlurTile bt; bt.level = (short)l; bt.tx = (short)tx; bt.ty = (short)ty; bt.pad = (short)std::min(BM_RC, nty - ty);
-          c->mtiles.push_back(bt);
-          for (int q = 0; q < bt.pad; q++) { BlurTile b1 = bt; b1.ty = (short)(ty + q); b1.pad = 1; c->mtiles1.push_back(b1); }
-        }
-    }
-    G.ncells_total = (int)c->cells.size();
-    G.cell_cap = cell_cap; G.sel_cap = sel_cap; G.keys_per_frame = key_off; G.desc_blocks = desc_blocks;
-    ORBHIP_REQUIRE(tile_w <= 64 && tile_h <= 64, ORBHIP_EINVAL, "FAST cell larger than 64 px (unsupported image geometry)");
-    G.tile_w = tile_w; G.tile_h = tile_h; G.tile_pitch = round_up(tile_w, 4) + 4;
-    G.node_cap = round_up(node_cap, 8); G.max_cells_level = round_up(max_cells, 8);
-#ifdef ORBHIP_OCT_LEVEL_EXPERIMENT
-    G.oct_level_mask = ORBHIP_EXP_ENV("ORBHIP_OCT_LEVELS") ? (int)strtol(ORBHIP_EXP_ENV("ORBHIP_OCT_LEVELS"), nullptr, 0) : 0xFFFF;
-#endif
-    // ---- k_pyr_cone: per 32 x 8 tile of the top level, the box it computes on every level (see the kernel)
-    c->cone_wgs = 0;
-    if (nl >= 3 && nl <= CONE_MAXL) {
-      const int top = nl - 1, TW = 32, TH = 8;
-      const int ntx = (G.lv[top].w + TW - 1) / TW, nty = (G.lv[top].h + TH - 1) / TH;
-      std::vector<short> boxes((size_t)ntx * nty * nl * 4);
-      int buf0 = 0, bufk = 0; size_t tabmax = 0; bool ok = G.lv[0].w < 32000 && G.lv[0].h < 32000;
-      for (int j = 0; j < nty && ok; j++)
-        for (int i = 0; i < ntx && ok; i++) {
-          short* Bx = &boxes[((size_t)j * ntx + i) * nl * 4];
-          int bx0 = i * TW, by0 = j * TH, bx1 = std::min((i + 1) * TW, G.lv[top].w), by1 = std::min((j + 1) * TH, G.lv[top].h);
-          size_t tb = 0;
-          for (int k = top; k >= 0; k--) {
-            const int Wk = G.lv[k].w, Hk = G.lv[k].h;
-            if (k < top) {
-              // what the box of level k + 1 reads from level k ...
-              const std::vector<int>& xo = h_xofs[k + 1]; const std::vector<int>& yo = h_yofs[k + 1];
-              const int ux0 = Bx[4 * (k + 1)], ux1 = std::min<int>(Bx[4 * (k + 1) + 2], G.lv[k + 1].w), uy0 = Bx[4 * (k + 1) + 1], uy1 = Bx[4 * (k + 1) + 3];
-              auto cy = [&](int v) { return std::min(std::max(v, 0), Hk - 1); };
-              int nx0 = xo[ux0], nx1 = std::min(xo[ux1 - 1] + 1, Wk - 1) + 1, ny0 = cy(yo[uy0]), ny1 = cy(yo[uy1 - 1] + 1) + 1;
-              for (int y = uy0; y < uy1; y++) { ny0 = std::min(ny0, cy(yo[y])); ny1 = std::max(ny1, cy(yo[y] + 1) + 1); }
-              for (int x = ux0; x < ux1; x++) { nx0 = std::min(nx0, xo[x]); nx1 = std::max(nx1, std::min(xo[x] + 1, Wk - 1) + 1); }
-              bx0 = nx0; bx1 = nx1; by0 = ny0; by1 = ny1;
-              if (k >= 1) {                                       // ... and this workgroup's share of level k itself
-                bx0 = std::min(bx0, (int)((long long)i * Wk / ntx)); bx1 = std::max(bx1, (int)((long long)(i + 1) * Wk / ntx));
-                by0 = std::min(by0, (int)((long long)j * Hk / nty)); by1 = std::max(by1, (int)((long long)(j + 1) * Hk / nty));
-              }
-            }
-            if (k >= 1) { bx0 &= ~3; bx1 = std::min(round_up(bx1, 4), round_up(Wk, 4)); }      // whole dwords, as k_resize stores them
-            Bx[4 * k] = (short)bx0; Bx[4 * k + 1] = (short)by0; Bx[4 * k + 2] = (short)bx1; Bx[4 * k + 3] = (short)by1;
-            const int bytes = (bx1 - bx0) * (by1 - by0);
-            if (k >= 1 && (bx1 - bx0 > 256 || by1 - by0 > 256)) ok = false;      // (a thread loads one table entry per level)
-            if (k == 0 && bytes > CONE_TPB * CONE_SRC_PT) ok = false;
-            if (k == 0) buf0 = std::max(buf0, bytes); else { bufk = std::max(bufk, bytes); tb += 8 * (size_t)(bx1 - bx0) + 16 * (size_t)(by1 - by0); }
-          }
-          tabmax = std::max(tabmax, tb);
-        }
-      buf0 = round_up(buf0, 16); bufk = round_up(bufk, 16);
-      const size_t lds = (size_t)buf0 + 2 * (size_t)bufk + tabmax + 64;
-      if (ok && lds <= 96 * 1024) {
-        size_t off = (tab.size() + 15) / 16 * 16;
-        tab.resize(off + boxes.size() * 2);
-        std::memcpy(tab.data() + off, boxes.data(), boxes.size() * 2);
-        c->tab_cone = off; c->cone_wgs = ntx * nty; c->cone_buf0 = buf0; c->cone_bufk = bufk; c->cone_lds = lds;
-      }
-    }
-    G.pyr_frame_bytes = (pyr_off + 255) / 256 * 256;
-    G.blur_frame_bytes = (blur_off + 255) / 256 * 256;
-    c->fast_narrow = tile_w - 6 <= 32;                      // every cell interior <= 32 px wide: k_fast_cells<true> (32-bit row masks)
-    c->fast_lds = (size_t)round_up((int)((size_t)2 * round_up(G.tile_h * G.tile_pitch, 16) + 2 * 64 * (c->fast_narrow ? 4 : 8) + 16 + (size_t)2 * std::max(tile_w - 6, 1) * std::max(tile_h - 6, 1) + 16), 16);   // tile + score (u8) + row masks + queue counter + queue (u16)
-    c->octree_wide = false;
-    for (int l = 0; l < c->nlevels; l++) c->octree_wide = c->octree_wide || G.lv[l].kcap > 65535;
-    c->octree_lds = octree_lds_bytes(G.node_cap, G.max_cells_level, false, false);
-    c->octree_lds_wide = octree_lds_bytes(G.node_cap, G.max_cells_level, true, false);
-    // node arrays beyond the LDS: both instantiations keep them in a global scratch row per (frame, level) instead (k_octree<.., true>)
-    c->octree_gmem = (c->octree_wide ? c->octree_lds_wide : c->octree_lds) > 160 * 1024;
-    c->octree_row = (size_t)round_up((int)octree_lds_bytes(G.node_cap, G.max_cells_level, true, true), 256);
-    ORBHIP_REQUIRE(G.node_cap <= 32760, ORBHIP_EINVAL, "nfeatures too large: more than 32752 keypoints in one level (16-bit node indices)");
-    if (int rc = c->d_cells.ensure(std::max<size_t>(c->cells.size(), 1) * sizeof(CellDesc))) return rc;
-    if (int rc = c->d_btiles.ensure(c->btiles.size() * sizeof(BlurTile))) return rc;
-    if (int rc = c->d_mtiles.ensure(c->mtiles.size() * sizeof(BlurTile))) return rc;
-    if (int rc = c->d_mtiles1.ensure(c->mtiles1.size() * sizeof(BlurTile))) return rc;
-    if (int rc = c->d_tab.ensure(std::max<size_t>(tab.size(), 16))) return rc;
-    if (!c->cells.empty()) ORBHIP_CHECK_HIP(hipMemcpy(c->d_cells.p, c->cells.data(), c->cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
-    ORBHIP_CHECK_HIP(hipMemcpy(c->d_btiles.p, c->btiles.data(), c->btiles.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
-    ORBHIP_CHECK_HIP(hipMemcpy(c->d_mtiles.p, c->mtiles.data(), c->mtiles.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
-    ORBHIP_CHECK_HIP(hipMemcpy(c->d_mtiles1.p, c->mtiles1.data(), c->mtiles1.size() * sizeof(BlurTile), hipMemcpyHostToDevice));
-    if (!tab.empty()) ORBHIP_CHECK_HIP(hipMemcpy(c->d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-    if (!c->octree_gmem && c->octree_lds > 64 * 1024)
-      if (int rc = raise_dynamic_lds((const void*)k_octree<false, false>, c->device, c->octree_lds)) return rc;
-    if (!c->octree_gmem && c->octree_wide && c->octree_lds_wide > 64 * 1024)
-      if (int rc = raise_dynamic_lds((const void*)k_octree<true, false>, c->device, c->octree_lds_wide)) return rc;
-    c->w = w; c->h = h; c->stride = stride; c->nframes = 0;
-  }
-  if (!c->const_uploaded) {
-    ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), ORB_BIT_PATTERN_31, 1024));
-    ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_umax), c->umax.data(), 16 * sizeof(int)));
-    {
-      // k_blur7_mfma's Toeplitz operands (see the kernel): lane (n, g), byte j <-> k = 16 g + j
-      std::vector<int8_t> T((size_t)2 * 7 * 64 * 16, 0);
-      for (int var = 0; var < 2; var++) {
-        const int taps[7] = {18, 34, var ? 48 : 49, var ? 56 : 55, var ? 48 : 49, 34, 18};
-        for (int q = 0; q < 7; q++)
-          for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 16; j++) {
-              const int n = lane & 15, kk = 16 * (lane >> 4) + j;
-              const int ti = q < 3 ? kk - (12 * (n >> 2) + 4 * q + (n & 3)) - 1      // row pass, block q: output column c + 12 (n >> 2) + 4 q + (n & 3), source column c - 4 + kk
-                                   : kk - (16 * (q - 3) + n);                         // column pass, block s = q - 3: output row R0 + 3 + 16 s + n, source row R0 + kk
-              T[(((size_t)var * 7 + q) * 64 + lane) * 16 + j] = (int8_t)((ti >= 0 && ti <= 6) ? taps[ti] : 0);
-            }
-      }
-      ORBHIP_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_blur_toep), T.data(), T.size()));
-    }
-    c->const_uploaded = true;
-  }
-  const size_t B = (size_t)nframes;
+  if (!same_shape) { if (int rc = replan(c, w, h, stride)) return rc; }
+  if (!c->const_uploaded) { if (int rc = upload_constants(c)) return rc; }
+  const GeomDev& G = c->P.G;
+  const size_t B = (size_t)nframes, nl = (size_t)c->nlevels;
   if (int rc = c->d_pyr.ensure(std::max<size_t>(B * G.pyr_frame_bytes, 256))) return rc;
   if (int rc = c->d_blur.ensure(B * G.blur_frame_bytes)) return rc;
   if (int rc = c->d_cellcnt.ensure(std::max<size_t>(B * G.ncells_total * 4, 16))) return rc;
@@ -1945,7 +1620,7 @@ static int prepare(orbx_ctx* c, int w, int h, int stride, int nframes) {
   if (int rc = c->d_keys.ensure(B * G.keys_per_frame * 4)) return rc;
   if (int rc = c->d_knode.ensure(B * G.keys_per_frame * 2)) return rc;
   if (int rc = c->d_sel.ensure(B * nl * G.sel_cap * 4)) return rc;
-  if (c->octree_gmem) { if (int rc = c->d_octnodes.ensure(B * nl * c->octree_row)) return rc; }
+  if (c->P.octree_gmem) { if (int rc = c->d_octnodes.ensure(B * nl * c->P.octree_row)) return rc; }
   if (int rc = c->d_selcnt.ensure(B * nl * 4)) return rc;
   if (int rc = c->d_nkeys.ensure(B * nl * 4)) return rc;
   if (int rc = c->d_status.ensure(B * 4)) return rc;
@@ -1953,65 +1628,59 @@ static int prepare(orbx_ctx* c, int w, int h, int stride, int nframes) {
   return 0;
 }
 
-static int run_batch(orbx_ctx* c, const uint8_t* d_imgs, int w, int h, int stride, size_t frame_stride,
-                     int nframes, orbx_keypoint* d_kps, uint8_t* d_desc, int cap, int32_t* d_counts,
-                     hipStream_t st) {
-  void (*blur_k)(GeomDev, const BlurTile*, const uint8_t*, long long, const uint8_t*, uint8_t*) =
-      c->blur_mfma ? (c->blur_variant ? k_blur7_mfma<1> : k_blur7_mfma<0>) : (c->blur_variant ? k_blur7<1> : k_blur7<0>);
+// what one run_batch call hands to its launches
+struct BatchCall { orbx_ctx* c; const uint8_t* d_imgs; size_t frame_stride; int nframes; hipStream_t st; };
 
-  ORBHIP_CHECK_HIP(hipSetDevice(c->device));
-  if (int rc = prepare(c, w, h, stride, nframes)) return rc;
-  const GeomDev& G = c->G;
-  const int nl = c->nlevels;
-  uint8_t* pyr = c->d_pyr.as<uint8_t>();
-  // (a lone frame: one 58-row chunk per wave - four times the workgroups, a quarter of the chain per wave)
-  const bool blur_short = c->blur_mfma && nframes < 4;
-  const unsigned n_btiles = (unsigned)(c->blur_mfma ? (blur_short ? c->mtiles1.size() : c->mtiles.size()) : c->btiles.size());
-  const BlurTile* d_btl = c->blur_mfma ? (blur_short ? c->d_mtiles1.as<BlurTile>() : c->d_mtiles.as<BlurTile>()) : c->d_btiles.as<BlurTile>();
-  auto mark = [&]() { if (c->profiling) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, st); c->prof_events.push_back(e); } } };
-  static const bool cone_on = []() { const char* e = ORBHIP_EXP_ENV("ORBHIP_EXTRACT_CONE"); return !(e && e[0] == '0'); }();
-  const bool cone = cone_on && nframes == 1 && c->cone_wgs > 0;
-  if (!cone) ORBHIP_CHECK_HIP(hipMemsetAsync(c->d_status.p, 0, (size_t)nframes * 4, st));
-  mark();
-  // pyramid chain: a single frame takes the one-launch cone kernel (latency), batches one launch per level (throughput;
-  // ORBHIP_EXTRACT_CONE=0: always per level)
-  if (cone) {
-    ConeArgs ca; std::memset(&ca, 0, sizeof(ca));
-    const uint8_t* T = c->d_tab.as<uint8_t>();
-    ca.nl = nl; ca.spitch0 = G.lv[0].pitch; ca.buf0 = c->cone_buf0; ca.bufk = c->cone_bufk;
-    for (int l = 1; l < nl; l++) {
-      ConeLevel& L = ca.lv[l];
-      L.sw = G.lv[l - 1].w; L.sh = G.lv[l - 1].h; L.dw = G.lv[l].w; L.dh = G.lv[l].h; L.dpitch = G.lv[l].pitch; L.doff = G.lv[l].pyr_off;
-      L.xtab = (const uint2*)(T + c->tab_xofs[l]); L.yofs = (const int*)(T + c->tab_yofs[l]); L.ibeta = (const short*)(T + c->tab_ibeta[l]);
-    }
-    if (c->cone_lds > 64 * 1024)
-      if (int rc = raise_dynamic_lds((const void*)k_pyr_cone, c->device, c->cone_lds)) return rc;
-    hipLaunchKernelGGL(k_pyr_cone, dim3(c->cone_wgs), dim3(CONE_TPB), c->cone_lds, st, ca, (const short*)(T + c->tab_cone), d_imgs, pyr, c->d_status.as<int>());
+// The pyramid of a single frame in ONE launch (latency; k_pyr_cone also clears the frame's status word)
+static int launch_cone(const BatchCall& b) {
+  orbx_ctx* c = b.c; const ExtractorPlan& P = c->P; const GeomDev& G = P.G;
+  ConeArgs ca; std::memset(&ca, 0, sizeof(ca));
+  const uint8_t* T = c->d_tab.as<uint8_t>();
+  ca.nl = G.nlevels; ca.spitch0 = G.lv[0].pitch; ca.buf0 = P.cone.buf0; ca.bufk = P.cone.bufk;
+  for (int l = 1; l < G.nlevels; l++) {
+    ConeLevel& L = ca.lv[l];
+    L.sw = G.lv[l - 1].w; L.sh = G.lv[l - 1].h; L.dw = G.lv[l].w; L.dh = G.lv[l].h; L.dpitch = G.lv[l].pitch; L.doff = G.lv[l].pyr_off;
+    L.xtab = (const uint2*)(T + P.tab_xofs[l]); L.yofs = (const int*)(T + P.tab_yofs[l]); L.ibeta = (const short*)(T + P.tab_ibeta[l]);
   }
-  for (int l = 1; l < nl && !cone; l++) {
+  if (P.cone.lds > 64 * 1024)
+    if (int rc = raise_dynamic_lds((const void*)k_pyr_cone, c->device, P.cone.lds)) return rc;
+  hipLaunchKernelGGL(k_pyr_cone, dim3(P.cone.wgs), dim3(CONE_TPB), P.cone.lds, b.st, ca, (const short*)(T + P.cone.tab), b.d_imgs, c->d_pyr.as<uint8_t>(), c->d_status.as<int>());
+  return 0;
+}
+
+// The pyramid chain of a batch, one launch per level (throughput): k_resize_mfma where the level's tables allow it, else k_resize
+static void launch_resize_levels(const BatchCall& b) {
+  orbx_ctx* c = b.c; const ExtractorPlan& P = c->P; const GeomDev& G = P.G;
+  uint8_t* pyr = c->d_pyr.as<uint8_t>();
+  const uint8_t* T = c->d_tab.as<uint8_t>();
+  for (int l = 1; l < G.nlevels; l++) {
     const LevelDev& S = G.lv[l - 1];
     const LevelDev& D = G.lv[l];
-    const uint8_t* src = (l == 1) ? d_imgs : pyr + S.pyr_off;
-    long long sframe = (l == 1) ? (long long)frame_stride : G.pyr_frame_bytes;
-    const uint8_t* T = c->d_tab.as<uint8_t>();
-    if (c->resize_mfma && (size_t)l < c->rm.size() && c->rm[l].ok && nframes <= 65535) {
-      const orbx_ctx::RmHost& M = c->rm[l];
+    const uint8_t* src = (l == 1) ? b.d_imgs : pyr + S.pyr_off;
+    long long sframe = (l == 1) ? (long long)b.frame_stride : G.pyr_frame_bytes;
+    if (c->resize_mfma && P.rm[l].ok && b.nframes <= 65535) {
+      const RmHost& M = P.rm[l];
       RmLevel R; R.tab = T; R.oW = M.oW; R.oC = M.oC; R.oC0 = M.oC0; R.oRow = M.oRow; R.nchunks = M.nchunks; R.nblocks = M.nblocks; R.sw = S.w; R.sh = S.h; R.dw = D.w; R.dh = D.h;
       const int ntx = (M.nchunks + 3) / 4, ntb = (M.nblocks + RM_RB - 1) / RM_RB;
-      hipLaunchKernelGGL(k_resize_mfma, dim3(ntx * ntb, nframes), dim3(256), 0, st, R, src, S.pitch, sframe, pyr + D.pyr_off, D.pitch, G.pyr_frame_bytes, ntx);
+      hipLaunchKernelGGL(k_resize_mfma, dim3(ntx * ntb, b.nframes), dim3(256), 0, b.st, R, src, S.pitch, sframe, pyr + D.pyr_off, D.pitch, G.pyr_frame_bytes, ntx);
       continue;
     }
-    dim3 grid((D.w + 255) / 256, (D.h + 4 * RS_ROWS - 1) / (4 * RS_ROWS), nframes), block(64, 4);
-    hipLaunchKernelGGL(k_resize, grid, block, 0, st, src, S.pitch, sframe, S.w, S.h, pyr + D.pyr_off, D.pitch,
-                       G.pyr_frame_bytes, D.w, D.h, (const uint2*)(T + c->tab_xofs[l]), (const int*)(T + c->tab_yofs[l]),
-                       (const short*)(T + c->tab_ibeta[l]));
+    dim3 grid((D.w + 255) / 256, (D.h + 4 * RS_ROWS - 1) / (4 * RS_ROWS), b.nframes), block(64, 4);
+    hipLaunchKernelGGL(k_resize, grid, block, 0, b.st, src, S.pitch, sframe, S.w, S.h, pyr + D.pyr_off, D.pitch,
+                       G.pyr_frame_bytes, D.w, D.h, (const uint2*)(T + P.tab_xofs[l]), (const int*)(T + P.tab_yofs[l]),
+                       (const short*)(T + P.tab_ibeta[l]));
   }
-  // (default -1: batches of >= 8 frames run the blur beside FAST + octree - the octree is a handful of long workgroups that leave
-  // most of the chip idle: +3.2 % on the one-stream bench, 112.1k -> 115.5k frames/s; starting the blur of level 0 even earlier,
-  // beside the resize chain, was measured too and adds nothing.  A lone frame stays on one stream: a fork / join costs more
-  // than it hides)
-  // (a lone frame inside a longer device chain - the Tracking step - does fork: the host is ahead of the device there, so the
-  // fork / join costs nothing on the critical path and the blur's 13.6 us run beside FAST + octree: 0.310 -> 0.297 ms per step)
+}
+
+// Where the blur of this call runs.  Returns the side mode (0: on the call's stream; 1: on *side_st beside FAST + octree; 2: beside
+// the octree only).
+// (default -1: batches of >= 8 frames run the blur beside FAST + octree - the octree is a handful of long workgroups that leave
+// most of the chip idle: +3.2 % on the one-stream bench, 112.1k -> 115.5k frames/s; starting the blur of level 0 even earlier,
+// beside the resize chain, was measured too and adds nothing.  A lone frame stays on one stream: a fork / join costs more
+// than it hides)
+// (a lone frame inside a longer device chain - the Tracking step - does fork: the host is ahead of the device there, so the
+// fork / join costs nothing on the critical path and the blur's 13.6 us run beside FAST + octree: 0.310 -> 0.297 ms per step)
+static int pick_side_stream(orbx_ctx* c, int nframes, hipStream_t* side_st) {
   int side_mode = c->ev_fork ? (c->overlap_blur >= 0 ? c->overlap_blur : (nframes >= 8 ? 1 : (nframes == 1 ? c->lone_side_mode : 0))) : 0;
   // The blur of a lone frame inside the per-frame Tracking chain is on that frame's critical path, and the Tracking thread may run
   // beside another thread's bundle adjustment (orbhip_set_thread_priority): it gets a stream of the greatest priority.  Batches do
@@ -2019,89 +1688,121 @@ static int run_batch(orbx_ctx* c, const uint8_t* d_imgs, int w, int h, int strid
   // the copy / compute overlap of a host-fed pipeline (112 k -> 73 k frames/s).  ORBHIP_SIDE_PRIORITY=1 restores round 4's behaviour.
   // Either stream is created on first use: streams that merely exist cost dispatch slots.
   static const bool side_prio_all = []() { const char* v = std::getenv("ORBHIP_SIDE_PRIORITY"); return v && v[0] == '1'; }();
-  hipStream_t side_st = nullptr;
-  if (side_mode) {
-    const bool want_hi = (nframes == 1 && c->lone_side_mode) || side_prio_all;
-    if (want_hi && !c->side_hi) {
-      int lo = 0, hi = 0;
-      if (!(hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo && hipStreamCreateWithPriority(&c->side_hi, hipStreamNonBlocking, hi) == hipSuccess)) c->side_hi = nullptr;
-    }
-    if (want_hi && c->side_hi) side_st = c->side_hi;
-    else {
-      if (!c->side && hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) c->side = nullptr;
-      side_st = c->side;
-    }
-    if (!side_st) side_mode = 0;
+  *side_st = nullptr;
+  if (!side_mode) return 0;
+  const bool want_hi = (nframes == 1 && c->lone_side_mode) || side_prio_all;
+  if (want_hi && !c->side_hi) {
+    int lo = 0, hi = 0;
+    if (!(hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hi != lo && hipStreamCreateWithPriority(&c->side_hi, hipStreamNonBlocking, hi) == hipSuccess)) c->side_hi = nullptr;
   }
+  if (want_hi && c->side_hi) *side_st = c->side_hi;
+  else {
+    if (!c->side && hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) c->side = nullptr;
+    *side_st = c->side;
+  }
+  return *side_st ? side_mode : 0;
+}
+
+// The blur of every level on stream s; side_events: bracket it with the side stream's profiling events
+static void launch_blur(const BatchCall& b, hipStream_t s, bool side_events) {
+  orbx_ctx* c = b.c; const ExtractorPlan& P = c->P;
+  void (*blur_k)(GeomDev, const BlurTile*, const uint8_t*, long long, const uint8_t*, uint8_t*) =
+      c->blur_mfma ? (c->blur_variant ? k_blur7_mfma<1> : k_blur7_mfma<0>) : (c->blur_variant ? k_blur7<1> : k_blur7<0>);
+  // (a lone frame: one 58-row chunk per wave - four times the workgroups, a quarter of the chain per wave)
+  const bool blur_short = c->blur_mfma && b.nframes < 4;
+  const unsigned n_btiles = (unsigned)(c->blur_mfma ? (blur_short ? P.mtiles1.size() : P.mtiles.size()) : P.btiles.size());
+  const BlurTile* d_btl = c->blur_mfma ? (blur_short ? c->d_mtiles1.as<BlurTile>() : c->d_mtiles.as<BlurTile>()) : c->d_btiles.as<BlurTile>();
+  hipEvent_t sb = nullptr, se = nullptr;
+  if (side_events) { (void)hipEventCreate(&sb); (void)hipEventCreate(&se); (void)hipEventRecord(sb, s); }
+  hipLaunchKernelGGL(blur_k, dim3(n_btiles, b.nframes), dim3(256), 0, s, P.G,
+                     d_btl, b.d_imgs, (long long)b.frame_stride, c->d_pyr.as<uint8_t>(), c->d_blur.as<uint8_t>());
+  if (side_events) { (void)hipEventRecord(se, s); c->side_events.push_back(sb); c->side_events.push_back(se); }
+}
+
+// FAST over every cell of every level (k_fast_cells<true>: 32-bit row masks, when every cell interior is <= 32 px wide)
+static void launch_fast(const BatchCall& b) {
+  orbx_ctx* c = b.c; const ExtractorPlan& P = c->P; const GeomDev& G = P.G;
+  void (*fast_k)(GeomDev, const CellDesc*, const uint8_t*, long long, const uint8_t*, int*, uint32_t*, int, int, int, int) =
+      P.fast_narrow ? k_fast_cells<true> : k_fast_cells<false>;
+  hipLaunchKernelGGL(fast_k, dim3((G.ncells_total + FAST_WPB * FAST_CPW - 1) / (FAST_WPB * FAST_CPW), b.nframes), dim3(64 * FAST_WPB), P.fast_lds * FAST_WPB, b.st, G,
+                     c->d_cells.as<CellDesc>(), b.d_imgs, (long long)b.frame_stride, c->d_pyr.as<uint8_t>(), c->d_cellcnt.as<int>(),
+                     c->d_cellkps.as<uint32_t>(), c->iniTh, c->minTh, (int)P.fast_lds, (c->fast_xcd && b.nframes % 8 == 0) ? 1 : 0);
+}
+
+typedef void (*octree_kernel)(GeomDev, const int*, const uint32_t*, uint32_t*, unsigned short*, uint32_t*, int*, int*, int*, uint8_t*, size_t);
+static void launch_octree(const BatchCall& b, octree_kernel k, size_t lds, uint8_t* scratch, size_t row) {
+  orbx_ctx* c = b.c;
+  hipLaunchKernelGGL(k, dim3(c->nlevels, b.nframes), dim3(OCT_TPB), lds, b.st, c->P.G, c->d_cellcnt.as<int>(),
+                     c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(), c->d_knode.as<unsigned short>(),
+                     c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>(), scratch, row);
+}
+// One workgroup per (frame, level).  k_octree<true, .> takes the levels with more than 65535 candidates (32-bit node counters);
+// every other workgroup of it leaves at once.
+static int launch_octrees(const BatchCall& b) {
+  orbx_ctx* c = b.c; const ExtractorPlan& P = c->P;
+  if (!P.octree_gmem && P.octree_wide && b.nframes == 1) {      // a lone frame: both instantiations in one launch
+    const size_t lds2 = std::max(P.octree_lds, P.octree_lds_wide);
+    if (lds2 > 64 * 1024)
+      if (int rc = raise_dynamic_lds((const void*)k_octree_pair, c->device, lds2)) return rc;
+    hipLaunchKernelGGL(k_octree_pair, dim3(2 * c->nlevels, 1), dim3(OCT_TPB), lds2, b.st, P.G, c->d_cellcnt.as<int>(), c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(),
+                       c->d_knode.as<unsigned short>(), c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>());
+  } else if (!P.octree_gmem) {
+    launch_octree(b, k_octree<false, false>, P.octree_lds, nullptr, 0);
+    if (P.octree_wide) launch_octree(b, k_octree<true, false>, P.octree_lds_wide, nullptr, 0);
+  } else {                     // per-level quota beyond the LDS: node arrays in a global scratch row per (frame, level)
+    launch_octree(b, k_octree<false, true>, 0, c->d_octnodes.as<uint8_t>(), P.octree_row);
+    if (P.octree_wide) launch_octree(b, k_octree<true, true>, 0, c->d_octnodes.as<uint8_t>(), P.octree_row);
+  }
+  return 0;
+}
+
+static int run_batch(orbx_ctx* c, const uint8_t* d_imgs, int w, int h, int stride, size_t frame_stride,
+                     int nframes, orbx_keypoint* d_kps, uint8_t* d_desc, int cap, int32_t* d_counts,
+                     hipStream_t st) {
+  ORBHIP_CHECK_HIP(hipSetDevice(c->device));
+  if (int rc = prepare(c, w, h, stride, nframes)) return rc;
+  const ExtractorPlan& P = c->P;
+  const GeomDev& G = P.G;
+  const BatchCall b = {c, d_imgs, frame_stride, nframes, st};
+  uint8_t* pyr = c->d_pyr.as<uint8_t>();
+  auto mark = [&]() { if (c->profiling) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, st); c->prof_events.push_back(e); } } };
+  // pyramid chain: a single frame takes the one-launch cone kernel (latency), batches one launch per level (throughput;
+  // ORBHIP_EXTRACT_CONE=0: always per level)
+  static const bool cone_on = []() { const char* e = ORBHIP_EXP_ENV("ORBHIP_EXTRACT_CONE"); return !(e && e[0] == '0'); }();
+  const bool cone = cone_on && nframes == 1 && P.cone.wgs > 0;
+  if (!cone) ORBHIP_CHECK_HIP(hipMemsetAsync(c->d_status.p, 0, (size_t)nframes * 4, st));
+  mark();
+  if (cone) { if (int rc = launch_cone(b)) return rc; }
+  else launch_resize_levels(b);
+  hipStream_t side_st = nullptr;
+  const int side_mode = pick_side_stream(c, nframes, &side_st);
   c->lone_side_mode = 0;
-  auto launch_blur_side = [&]() -> int {
-    ORBHIP_CHECK_HIP(hipEventRecord(c->ev_fork, st));
+  auto blur_on_side = [&]() -> int {                          // (after ev_fork has been recorded on st)
     ORBHIP_CHECK_HIP(hipStreamWaitEvent(side_st, c->ev_fork, 0));
-    hipEvent_t sb = nullptr, se = nullptr;
-    if (c->profiling) { (void)hipEventCreate(&sb); (void)hipEventCreate(&se); (void)hipEventRecord(sb, side_st); }
-    hipLaunchKernelGGL(blur_k, dim3(n_btiles, nframes), dim3(256), 0, side_st, G,
-                       d_btl, d_imgs, (long long)frame_stride, pyr, c->d_blur.as<uint8_t>());
-    if (c->profiling) { (void)hipEventRecord(se, side_st); c->side_events.push_back(sb); c->side_events.push_back(se); }
+    launch_blur(b, side_st, c->profiling);
     ORBHIP_CHECK_HIP(hipEventRecord(c->ev_join, side_st));
     return 0;
   };
-  if (side_mode == 1) { if (int rc = launch_blur_side()) return rc; }
-  mark();
-  if (G.ncells_total > 0) {
-    if (c->fast_narrow)
-      hipLaunchKernelGGL(k_fast_cells<true>, dim3((G.ncells_total + FAST_WPB * FAST_CPW - 1) / (FAST_WPB * FAST_CPW), nframes), dim3(64 * FAST_WPB), c->fast_lds * FAST_WPB, st, G,
-                         c->d_cells.as<CellDesc>(), d_imgs, (long long)frame_stride, pyr, c->d_cellcnt.as<int>(),
-                         c->d_cellkps.as<uint32_t>(), c->iniTh, c->minTh, (int)c->fast_lds, (c->fast_xcd && nframes % 8 == 0) ? 1 : 0);
-    else
-      hipLaunchKernelGGL(k_fast_cells<false>, dim3((G.ncells_total + FAST_WPB * FAST_CPW - 1) / (FAST_WPB * FAST_CPW), nframes), dim3(64 * FAST_WPB), c->fast_lds * FAST_WPB, st, G,
-                         c->d_cells.as<CellDesc>(), d_imgs, (long long)frame_stride, pyr, c->d_cellcnt.as<int>(),
-                         c->d_cellkps.as<uint32_t>(), c->iniTh, c->minTh, (int)c->fast_lds, (c->fast_xcd && nframes % 8 == 0) ? 1 : 0);
+  if (side_mode == 1) {
+    ORBHIP_CHECK_HIP(hipEventRecord(c->ev_fork, st));
+    if (int rc = blur_on_side()) return rc;
   }
+  mark();
+  if (G.ncells_total > 0) launch_fast(b);
   mark();
   // mode 2: the octree is one latency-bound workgroup per (frame, level) - 6 % VALU-busy, 0.6 waves per SIMD - so the
   // VALU-bound blur runs BESIDE it: the fork is taken after FAST, the octree is submitted first and keeps its slots
   if (side_mode == 2) ORBHIP_CHECK_HIP(hipEventRecord(c->ev_fork, st));
-  if (!c->octree_gmem && c->octree_wide && nframes == 1) {
-    const size_t lds2 = std::max(c->octree_lds, c->octree_lds_wide);
-    if (lds2 > 64 * 1024)
-      if (int rc = raise_dynamic_lds((const void*)k_octree_pair, c->device, lds2)) return rc;
-    hipLaunchKernelGGL(k_octree_pair, dim3(2 * nl, 1), dim3(OCT_TPB), lds2, st, G, c->d_cellcnt.as<int>(), c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(),
-                       c->d_knode.as<unsigned short>(), c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>());
-  } else if (!c->octree_gmem) {
-    hipLaunchKernelGGL((k_octree<false, false>), dim3(nl, nframes), dim3(OCT_TPB), c->octree_lds, st, G, c->d_cellcnt.as<int>(),
-                       c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(), c->d_knode.as<unsigned short>(),
-                       c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>(), (uint8_t*)nullptr, (size_t)0);
-    if (c->octree_wide)        // levels with more than 65535 candidates (32-bit node counters); every other workgroup leaves at once
-      hipLaunchKernelGGL((k_octree<true, false>), dim3(nl, nframes), dim3(OCT_TPB), c->octree_lds_wide, st, G, c->d_cellcnt.as<int>(),
-                         c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(), c->d_knode.as<unsigned short>(),
-                         c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>(), (uint8_t*)nullptr, (size_t)0);
-  } else {                     // per-level quota beyond the LDS: node arrays in a global scratch row per (frame, level)
-    hipLaunchKernelGGL((k_octree<false, true>), dim3(nl, nframes), dim3(OCT_TPB), 0, st, G, c->d_cellcnt.as<int>(),
-                       c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(), c->d_knode.as<unsigned short>(),
-                       c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>(), c->d_octnodes.as<uint8_t>(), c->octree_row);
-    if (c->octree_wide)
-      hipLaunchKernelGGL((k_octree<true, true>), dim3(nl, nframes), dim3(OCT_TPB), 0, st, G, c->d_cellcnt.as<int>(),
-                         c->d_cellkps.as<uint32_t>(), c->d_keys.as<uint32_t>(), c->d_knode.as<unsigned short>(),
-                         c->d_sel.as<uint32_t>(), c->d_selcnt.as<int>(), c->d_nkeys.as<int>(), c->d_status.as<int>(), c->d_octnodes.as<uint8_t>(), c->octree_row);
-  }
-  if (side_mode == 2) {
-    ORBHIP_CHECK_HIP(hipStreamWaitEvent(side_st, c->ev_fork, 0));
-    hipEvent_t sb = nullptr, se = nullptr;
-    if (c->profiling) { (void)hipEventCreate(&sb); (void)hipEventCreate(&se); (void)hipEventRecord(sb, side_st); }
-    hipLaunchKernelGGL(blur_k, dim3(n_btiles, nframes), dim3(256), 0, side_st, G,
-                       d_btl, d_imgs, (long long)frame_stride, pyr, c->d_blur.as<uint8_t>());
-    if (c->profiling) { (void)hipEventRecord(se, side_st); c->side_events.push_back(sb); c->side_events.push_back(se); }
-    ORBHIP_CHECK_HIP(hipEventRecord(c->ev_join, side_st));
-  }
+  if (int rc = launch_octrees(b)) return rc;
+  if (side_mode == 2) { if (int rc = blur_on_side()) return rc; }
   mark();
-  if (side_mode == 0) hipLaunchKernelGGL(blur_k, dim3(n_btiles, nframes), dim3(256), 0, st, G,
-                                         d_btl, d_imgs, (long long)frame_stride, pyr, c->d_blur.as<uint8_t>());
+  if (side_mode == 0) launch_blur(b, st, false);
   else ORBHIP_CHECK_HIP(hipStreamWaitEvent(st, c->ev_join, 0));       // join: describe needs the blurred levels
   mark();
   hipLaunchKernelGGL(k_describe, dim3(G.desc_blocks, nframes), dim3(64 * DESC_WPB), 0, st, G, c->d_sel.as<uint32_t>(),
                      c->d_selcnt.as<int>(), c->d_status.as<int>(), d_imgs, (long long)frame_stride, pyr,
-                     c->d_blur.as<uint8_t>(), d_kps, d_desc, cap, d_counts, c->atan_p[0], c->atan_p[1],
-                     c->atan_p[2], c->atan_p[3], c->factorPI, (c->desc_xcd && nframes % 8 == 0) ? 1 : 0);
+                     c->d_blur.as<uint8_t>(), d_kps, d_desc, cap, d_counts, c->S.atan_p[0], c->S.atan_p[1],
+                     c->S.atan_p[2], c->S.atan_p[3], c->S.factorPI, (c->desc_xcd && nframes % 8 == 0) ? 1 : 0);
   mark();
   ORBHIP_CHECK_HIP(hipGetLastError());
   c->last_img0 = d_imgs; c->last_img_frame_bytes = (long long)frame_stride; c->last_nframes = nframes;
@@ -2124,7 +1825,7 @@ int orbx_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast,
   ORBHIP_REQUIRE(c != nullptr, ORBHIP_ENOMEM, "out of host memory");
   c->nfeatures = nfeatures; c->scaleFactor = scale_factor; c->nlevels = nlevels;
   c->iniTh = ini_th_fast; c->minTh = min_th_fast; c->device = device;
-  build_tables(c);
+  c->S = scale_tables(nfeatures, c->scaleFactor, nlevels);
   (void)hipSetDevice(device);
   // (fork / join events of the blur's side stream; the streams themselves are created by run_batch on first use)
   if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess) c->ev_fork = nullptr;
@@ -2217,11 +1918,11 @@ int orbx_get_tables(const orbx_ctx* c, float* scale, float* inv_scale, float* si
                     int32_t* fpl) {
   ORBHIP_REQUIRE(c != nullptr, ORBHIP_EINVAL, "ctx is NULL");
   for (int i = 0; i < c->nlevels; i++) {
-    if (scale) scale[i] = c->scale[i];
-    if (inv_scale) inv_scale[i] = c->inv_scale[i];
-    if (sigma2) sigma2[i] = c->sigma2[i];
-    if (inv_sigma2) inv_sigma2[i] = c->inv_sigma2[i];
-    if (fpl) fpl[i] = c->quota[i];
+    if (scale) scale[i] = c->S.scale[i];
+    if (inv_scale) inv_scale[i] = c->S.inv_scale[i];
+    if (sigma2) sigma2[i] = c->S.sigma2[i];
+    if (inv_sigma2) inv_sigma2[i] = c->S.inv_sigma2[i];
+    if (fpl) fpl[i] = c->S.quota[i];
   }
   return 0;
 }
@@ -2232,7 +1933,7 @@ int orbx_max_keypoints(const orbx_ctx* c) {
   // all nIni initial nodes unconditionally (src/ORBextractor.cc:589-660): a wide, short level with few features can come
   // back with up to 4 * nIni > N keypoints.  nIni depends on the image aspect ratio (<= MAX_INI), so the bound is taken over it.
   int s = 0;
-  for (int q : c->quota) s += std::max(q + 3, 4 * MAX_INI);
+  for (int q : c->S.quota) s += std::max(q + 3, 4 * MAX_INI);
   return s;
 }
 
@@ -2304,16 +2005,16 @@ int orbx_extract(orbx_ctx* c, const uint8_t* img, int w, int h, int stride, orbx
 int orbx_get_level_image(orbx_ctx* c, int frame, int level, int blurred, uint8_t* out, int* w, int* h) {
   ORBHIP_REQUIRE(c && c->last_nframes > 0, ORBHIP_EINVAL, "no extract call yet");
   ORBHIP_REQUIRE(frame >= 0 && frame < c->last_nframes && level >= 0 && level < c->nlevels, ORBHIP_EINVAL, "bad index");
-  const LevelDev& L = c->G.lv[level];
+  const LevelDev& L = c->P.G.lv[level];
   if (w) *w = L.w;
   if (h) *h = L.h;
   if (!out) return 0;
   ORBHIP_CHECK_HIP(hipSetDevice(c->device));
   ORBHIP_CHECK_HIP(hipDeviceSynchronize());
   const uint8_t* src; int pitch;
-  if (blurred) { src = c->d_blur.as<uint8_t>() + (long long)frame * c->G.blur_frame_bytes + L.blur_off; pitch = L.bpitch; }
+  if (blurred) { src = c->d_blur.as<uint8_t>() + (long long)frame * c->P.G.blur_frame_bytes + L.blur_off; pitch = L.bpitch; }
   else if (level == 0) { src = c->last_img0 + (long long)frame * c->last_img_frame_bytes; pitch = L.pitch; }
-  else { src = c->d_pyr.as<uint8_t>() + (long long)frame * c->G.pyr_frame_bytes + L.pyr_off; pitch = L.pitch; }
+  else { src = c->d_pyr.as<uint8_t>() + (long long)frame * c->P.G.pyr_frame_bytes + L.pyr_off; pitch = L.pitch; }
   ORBHIP_CHECK_HIP(hipMemcpy2D(out, L.w, src, pitch, L.w, L.h, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -2324,35 +2025,34 @@ static void unpack_keys(const std::vector<uint32_t>& k, int32_t* out, int cap) {
   }
 }
 
-int orbx_get_level_candidates(orbx_ctx* c, int frame, int level, int32_t* out, int cap, int* n) {
+// shared front of the two getters below: check the indices, wait for the device, fetch the level's count from the context's `counts` buffer
+static int level_count(orbx_ctx* c, int frame, int level, DevBuf orbx_ctx::*counts, int* n) {
   ORBHIP_REQUIRE(c && c->last_nframes > 0 && n, ORBHIP_EINVAL, "no extract call yet");
   ORBHIP_REQUIRE(frame >= 0 && frame < c->last_nframes && level >= 0 && level < c->nlevels, ORBHIP_EINVAL, "bad index");
   ORBHIP_CHECK_HIP(hipSetDevice(c->device));
   ORBHIP_CHECK_HIP(hipDeviceSynchronize());
-  int nk = 0;
-  ORBHIP_CHECK_HIP(hipMemcpy(&nk, c->d_nkeys.as<int>() + frame * c->nlevels + level, 4, hipMemcpyDeviceToHost));
-  *n = nk;
+  ORBHIP_CHECK_HIP(hipMemcpy(n, (c->*counts).as<int>() + frame * c->nlevels + level, 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int orbx_get_level_candidates(orbx_ctx* c, int frame, int level, int32_t* out, int cap, int* n) {
+  if (int rc = level_count(c, frame, level, &orbx_ctx::d_nkeys, n)) return rc;
+  const int nk = *n;
   if (!out || nk <= 0) return 0;
-  ORBHIP_REQUIRE(nk <= c->G.lv[level].kcap, ORBHIP_EOVERFLOW, "candidate capacity exceeded");
+  ORBHIP_REQUIRE(nk <= c->P.G.lv[level].kcap, ORBHIP_EOVERFLOW, "candidate capacity exceeded");
   std::vector<uint32_t> k(nk);
-  ORBHIP_CHECK_HIP(hipMemcpy(k.data(), c->d_keys.as<uint32_t>() + (long long)frame * c->G.keys_per_frame + c->G.lv[level].key_off,
+  ORBHIP_CHECK_HIP(hipMemcpy(k.data(), c->d_keys.as<uint32_t>() + (long long)frame * c->P.G.keys_per_frame + c->P.G.lv[level].key_off,
                              (size_t)nk * 4, hipMemcpyDeviceToHost));
   unpack_keys(k, out, cap);
   return 0;
 }
 
 int orbx_get_level_selected(orbx_ctx* c, int frame, int level, int32_t* out, int cap, int* n) {
-  ORBHIP_REQUIRE(c && c->last_nframes > 0 && n, ORBHIP_EINVAL, "no extract call yet");
-  ORBHIP_REQUIRE(frame >= 0 && frame < c->last_nframes && level >= 0 && level < c->nlevels, ORBHIP_EINVAL, "bad index");
-  ORBHIP_CHECK_HIP(hipSetDevice(c->device));
-  ORBHIP_CHECK_HIP(hipDeviceSynchronize());
-  int nk = 0;
-  ORBHIP_CHECK_HIP(hipMemcpy(&nk, c->d_selcnt.as<int>() + frame * c->nlevels + level, 4, hipMemcpyDeviceToHost));
-  *n = nk;
-  if (!out || nk <= 0) return 0;
-  nk = std::min(nk, c->G.sel_cap);
+  if (int rc = level_count(c, frame, level, &orbx_ctx::d_selcnt, n)) return rc;
+  if (!out || *n <= 0) return 0;
+  const int nk = std::min(*n, c->P.G.sel_cap);
   std::vector<uint32_t> k(nk);
-  ORBHIP_CHECK_HIP(hipMemcpy(k.data(), c->d_sel.as<uint32_t>() + ((long long)frame * c->nlevels + level) * c->G.sel_cap,
+  ORBHIP_CHECK_HIP(hipMemcpy(k.data(), c->d_sel.as<uint32_t>() + ((long long)frame * c->nlevels + level) * c->P.G.sel_cap,
                              (size_t)nk * 4, hipMemcpyDeviceToHost));
   unpack_keys(k, out, cap);
   return 0;
