@@ -26,6 +26,7 @@ SYMBOLS = [
     "orbv_db_detect_relocalization_candidates_batch_device", "orbv_db_detect_workspace",
     "orbm_undistort_keypoints", "orbm_assign_features_to_grid", "orbm_features_in_area", "orbm_is_in_frustum", "orbm_is_in_frustum_gates",
     "orbm_triangulate_matches", "orbt_track_with_motion_model", "orbt_track_local_map", "orbt_track_reference_keyframe", "orbt_last_call_ms",
+    "orbt_track_local_map_device", "orbt_update_local_keyframes", "orbt_update_local_points", "orbt_update_local_map_device", "orbt_update_local_map_workspace",
     "orbt_image_bounds", "orbt_set_distortion", "orbt_last_undistorted_keypoints",
     "ba_pose_optimization", "ba_pose_optimization_batch_device", "ba_solve", "ba_check_outlier",
     "ba_local_bundle_adjustment", "ba_optimize_sim3", "ba_optimize_sim3_batch_device", "ba_sim3_exp", "ba_sim3_log", "ba_sim3_mul", "ba_sim3_inverse",
@@ -182,6 +183,12 @@ def load():
     L.orbt_track_reference_keyframe.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, i32, vp, vp, i32, vp, vp, C.POINTER(i32), vp, vp, vp,
                                                 C.POINTER(i32), vp, vp, vp, vp]
     L.orbt_track_local_map.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp]
+    L.orbt_track_local_map_device.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.orbt_update_local_keyframes.argtypes = [i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]
+    L.orbt_update_local_points.argtypes = [i32, vp, vp, i32] + [vp] * 7 + [i32, vp, i32, vp, i32, vp, C.POINTER(i32)] + [vp] * 8
+    L.orbt_update_local_map_device.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, vp, i32] + [vp] * 7 + [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp,
+                                               i32, i32, i32] + [vp] * 16
+    L.orbt_update_local_map_workspace.argtypes = [i32, i32, i32, C.POINTER(sz)]
     L.orbm_is_in_frustum_gates.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]
     L.ba_pose_optimization.argtypes = [vp, vp, vp, vp, vp, i32, vp, C.POINTER(i32), C.POINTER(BaSummary)]
     L.ba_pose_optimization_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]

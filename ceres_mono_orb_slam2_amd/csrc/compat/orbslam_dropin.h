@@ -25,11 +25,13 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <algorithm>
 #include <unordered_map>
 #include <utility>
@@ -1487,6 +1489,117 @@ struct FrameOpsT {
     for (int c = 0; c < ncand; c++)
       if (culled[c]) { cands[c]->SetBadFlag(); n++; }                // (:633-635)
     return n;
+  }
+
+  // Tracking::UpdateLocalKeyFrames (src/Tracking.cc:874-977) in ONE library call (orbt_update_local_keyframes), the body of that member
+  // function: `FrameOpsHip::UpdateLocalKeyFrames(current_frame_, local_keyframes_, reference_keyframe_);`.  Only the part of the graph
+  // the function can touch is flattened, through the reference's own accessors: the observers of the frame's points (the voted
+  // keyframes), their GetBestCovisibilityKeyFrames(10), GetChilds() and GetParent(), and local_keyframes_ as the frame before left it.
+  // The two pointer orders the reference's result depends on are passed on as they are: kf_rank = the keyframes' order under
+  // std::less<KeyFrame*> (the iteration order of std::map<KeyFrame*, int> keyframeCounter), the children in the iteration order of the
+  // std::set GetChilds() returns.  Afterwards: the frame's slots whose point is bad are cleared, and - unless nobody voted, where the
+  // reference returns with everything as it was - local_keyframes is replaced, track_reference_for_frame_ = current_frame.id_ is written
+  // on every keyframe of it, and reference_keyframe / current_frame.reference_keyframe_ are set when a voted keyframe is not bad.
+  // Returns the library's status (ORBT_ULM_OK / ORBT_ULM_NO_VOTES).
+  // (Member templates over the frame and keyframe types: instantiated only where they are called, as KeyFrameCulling is.)
+  template <class F, class KF> static int UpdateLocalKeyFrames(F& current_frame, std::vector<KF*>& local_keyframes, KF*& reference_keyframe) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(current_frame.map_points_[0])>::type>::type MP;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::unordered_map<MP*, int> pt_at;
+    const int n_kp = (int)current_frame.map_points_.size();
+    std::vector<int32_t> frame_pt(n_kp, -1), obs_off(1, 0), obs_kf;
+    std::vector<uint8_t> pt_bad;
+    for (int i = 0; i < n_kp; i++) {                                // (:877-892)
+      MP* mp = current_frame.map_points_[i];
+      if (!mp) continue;
+      auto it = pt_at.find(mp);
+      if (it == pt_at.end()) {
+        it = pt_at.emplace(mp, (int)pt_bad.size()).first;
+        const bool bad = mp->isBad();
+        pt_bad.push_back(bad ? 1 : 0);
+        if (!bad) { const auto observations = mp->GetObservations(); for (const auto& o : observations) obs_kf.push_back(kf_index(o.first)); }
+        obs_off.push_back((int32_t)obs_kf.size());
+      }
+      frame_pt[i] = it->second;
+    }
+    const int n_voted = (int)kfs.size();                            // (only these are walked: their rows are the ones the call reads)
+    std::vector<int32_t> cov_off(1, 0), cov_kf, child_off(1, 0), child_kf, parent;
+    for (int k = 0; k < n_voted; k++) {
+      KF* kf = kfs[k];
+      const std::vector<KF*> neighbours = kf->GetBestCovisibilityKeyFrames(10);            // (:932-933)
+      for (size_t j = 0; j < neighbours.size() && j < 10; j++) cov_kf.push_back(kf_index(neighbours[j]));
+      cov_off.push_back((int32_t)cov_kf.size());
+      const std::set<KF*> children = kf->GetChilds();                                    // (:949)
+      for (KF* c : children) child_kf.push_back(kf_index(c));
+      child_off.push_back((int32_t)child_kf.size());
+      KF* par = kf->GetParent();                                                          // (:963)
+      parent.push_back(par ? kf_index(par) : -1);
+    }
+    std::vector<int32_t> prev(local_keyframes.size());
+    for (size_t i = 0; i < local_keyframes.size(); i++) prev[i] = kf_index(local_keyframes[i]);
+    const int nkf = (int)kfs.size(), npts = (int)pt_bad.size();
+    cov_off.resize(nkf + 1, (int32_t)cov_kf.size()); child_off.resize(nkf + 1, (int32_t)child_kf.size()); parent.resize(nkf, -1);
+    std::vector<uint8_t> kf_bad(nkf);
+    for (int k = 0; k < nkf; k++) kf_bad[k] = kfs[k]->isBad() ? 1 : 0;
+    std::vector<int32_t> by_pointer(nkf), kf_rank(nkf);             // the order of std::map<KeyFrame*, int>
+    for (int k = 0; k < nkf; k++) by_pointer[k] = k;
+    std::sort(by_pointer.begin(), by_pointer.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nkf; r++) kf_rank[by_pointer[r]] = r;
+    std::vector<int32_t> frame_pt_out(n_kp, -1), local_kf(std::max(nkf, 1));
+    int32_t n_local = 0, ref = -1, status = 0;
+    dropin::check(orbt_update_local_keyframes(n_kp, frame_pt.data(), npts, pt_bad.data(), obs_off.data(), obs_kf.data(), nkf, kf_bad.data(), kf_rank.data(), parent.data(),
+                                              cov_off.data(), cov_kf.data(), child_off.data(), child_kf.data(), (int)prev.size(), prev.data(), nkf,
+                                              frame_pt_out.data(), local_kf.data(), &n_local, &ref, &status, nullptr), "orbt_update_local_keyframes");
+    for (int i = 0; i < n_kp; i++)
+      if (frame_pt[i] >= 0 && frame_pt_out[i] < 0) current_frame.map_points_[i] = nullptr;          // (:889)
+    if (status == ORBT_ULM_NO_VOTES) return status;                 // (:894-896)
+    local_keyframes.clear();
+    for (int i = 0; i < n_local; i++) {
+      KF* kf = kfs[local_kf[i]];
+      local_keyframes.push_back(kf);
+      kf->track_reference_for_frame_ = current_frame.id_;
+    }
+    if (ref >= 0) { reference_keyframe = kfs[ref]; current_frame.reference_keyframe_ = reference_keyframe; }      // (:973-976)
+    return status;
+  }
+
+  // Tracking::UpdateLocalPoints (src/Tracking.cc:847-872) in ONE library call (orbt_update_local_points):
+  // `FrameOpsHip::UpdateLocalPoints(current_frame_, local_keyframes_, local_map_points_);`.  The slot tables (GetMapPointMatches()) of the
+  // local keyframes only are flattened, never the whole map.  local_map_points is replaced and track_reference_for_frame_ =
+  // current_frame.id_ is written on every point of it.  PRECONDITION (the reference's own): no point carries that id at entry.
+  template <class F, class KF, class MP> static void UpdateLocalPoints(F& current_frame, const std::vector<KF*>& local_keyframes, std::vector<MP*>& local_map_points) {
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*> pts;
+    std::vector<int32_t> slot_off(1, 0), slot_pt;
+    std::vector<uint8_t> pt_bad;
+    for (KF* kf : local_keyframes) {
+      const std::vector<MP*> matches = kf->GetMapPointMatches();    // (:854)
+      for (MP* mp : matches) {
+        if (!mp) { slot_pt.push_back(-1); continue; }
+        auto it = pt_at.find(mp);
+        if (it == pt_at.end()) { it = pt_at.emplace(mp, (int)pts.size()).first; pts.push_back(mp); pt_bad.push_back(mp->isBad() ? 1 : 0); }
+        slot_pt.push_back(it->second);
+      }
+      slot_off.push_back((int32_t)slot_pt.size());
+    }
+    const int npts = (int)pts.size();
+    std::vector<int32_t> local_pt(std::max(npts, 1));
+    int32_t n_local = 0;
+    dropin::check(orbt_update_local_points((int)local_keyframes.size(), slot_off.data(), slot_pt.data(), npts, pt_bad.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr, 0, nullptr, 0, nullptr, npts, local_pt.data(), &n_local, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr), "orbt_update_local_points");
+    local_map_points.clear();
+    for (int j = 0; j < n_local; j++) {
+      MP* mp = pts[local_pt[j]];
+      local_map_points.push_back(mp);
+      mp->track_reference_for_frame_ = current_frame.id_;
+    }
   }
 
  private:

@@ -1493,6 +1493,57 @@ int orbt_track_with_motion_model(orbx_ctx* ctx, const uint8_t* img, int w, int h
   return TrkWindows::no_fit();
 }
 
+// The constants of one TrackLocalMap call
+static void tlm_prepare(TlmIn& I, const float* K4, const float* bounds, const double* Tcw, float log_scale_factor, int nlevels, int n_mp, int n_kp, float th, float nnratio) {
+  std::memset(&I, 0, sizeof(I));
+  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.C.R[3 * r + c] = Tcw[4 * r + c]; I.C.t[r] = Tcw[4 * r + 3]; }
+  for (int k = 0; k < 3; k++) I.C.Ow[k] = -(I.C.R[k] * I.C.t[0] + I.C.R[3 + k] * I.C.t[1] + I.C.R[6 + k] * I.C.t[2]);      // Ow = -Rcw^T tcw (src/Frame.cc:188)
+  I.C.fx = K4[0]; I.C.fy = K4[1]; I.C.cx = K4[2]; I.C.cy = K4[3];
+  I.C.min_x = bounds[0]; I.C.max_x = bounds[1]; I.C.min_y = bounds[2]; I.C.max_y = bounds[3];
+  I.C.cos_limit = 0.5f; I.C.log_scale = log_scale_factor; I.C.nlevels = nlevels;          // isInFrustum(map_point, 0.5) (src/Tracking.cc:822)
+  for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
+  I.th = th; I.ratio = nnratio; I.n_mp = n_mp; I.n_kp_host = n_kp;
+  // a distance can win only if it is <= TH_HIGH and can veto through the ratio test only if ratio * d < TH_HIGH
+  { int dm = TRK_TH_HIGH; while (dm < 255 && nnratio * (float)(dm + 1) < (float)TRK_TH_HIGH) dm++; I.dmax = dm; }
+}
+
+static thread_local uint32_t g_tlm_cand_hw = 0;                // high-water mark of the candidate lists, shared by the two entries
+
+// TrackLocalMap once its inputs lie on the device (the host entry's packed upload, or the caller's arrays): frustum, windows, the
+// greedy pass, the pose solve, ONE download.  *again: the candidate lists were regrown - the caller repeats the call.
+static int tlm_run(ThreadWs& W, const TrkFrame& TF, const TlmIn& I, const TlmIn* dI, const double* d_mp_Xw, const double* d_mp_normal, const float* d_mp_min,
+                   const float* d_mp_max, const uint8_t* d_mp_desc, const uint8_t* d_mp_state, const double* d_slot_Xw, const uint8_t* d_slot_state, int nq, int n_kp,
+                   uint8_t* mp_in_view, int32_t* mp_match, int32_t* slot_owner, uint8_t* outlier_out, orbt_result* res, bool* again) {
+  int rc = 0;
+  *again = false;
+  const int icap = TF.icap;
+  uint32_t& cand_hw = g_tlm_cand_hw;
+  // output block: [pose tail | in_view | match | owner]
+  Carve C; TrkPoseTail P; TrkWindows Q;
+  P.carve(C, icap);
+  const size_t oView = C.take((size_t)std::max(nq, 1)), oMatch = C.take(4 * (size_t)std::max(nq, 1)), oOwner = C.take(4 * (size_t)icap);
+  uint8_t* dblk = W.d<uint8_t>(C.total, &rc);
+  Q.alloc(W, nq, 32u, cand_hw, &rc); P.alloc(W, icap, &rc);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_tlm_frustum, dim3((std::max(nq, 1) + 255) / 256), dim3(256), 0, W.s, dI, d_mp_Xw, d_mp_normal, d_mp_min, d_mp_max,
+                     d_mp_state, dblk + oView, Q.quv, Q.qr, Q.qlo, Q.qhi, Q.qv, Q.total);
+  Q.launch(W.s, TF, d_mp_desc, I.dmax);
+  if ((rc = raise_dynamic_lds((const void*)k_tlm_greedy, W.device, 4 * TLM_MAXMP))) return rc;
+  hipLaunchKernelGGL(k_tlm_greedy, dim3(1), dim3(1024), 4 * TLM_MAXMP, W.s, dI, Q.qv, Q.acc, Q.accn, Q.off, Q.total, Q.pairs, Q.cand_cap, TF.kps4.as<float>(),
+                     (const int32_t*)(TF.blk.as<uint8_t>() + TF.oCnt), icap, d_mp_Xw, d_slot_Xw, d_slot_state, (int32_t*)(dblk + oMatch),
+                     (int32_t*)(dblk + oOwner), (int32_t*)(dblk + P.oFeat), P.oX, P.ouv, P.ow, P.ooff, (double*)(dblk + P.oPose), P.K4, (TrkOut*)(dblk + P.oOut), nq);
+  if ((rc = P.solve(dblk, W.s))) return rc;
+  const uint8_t* hb = W.down(dblk, C.total, &rc);
+  if (rc || (rc = W.sync())) return rc;
+  if (Q.regrown((uint32_t)((const TrkOut*)(hb + P.oOut))->cand_total, cand_hw)) { *again = true; return 0; }
+  if (nq) { std::memcpy(mp_in_view, hb + oView, (size_t)nq); std::memcpy(mp_match, hb + oMatch, 4 * (size_t)nq); }
+  std::memcpy(slot_owner, hb + oOwner, 4 * (size_t)n_kp);
+  const TrkOut* T = P.unpack(hb, I.pose7, n_kp, outlier_out, res);
+  int nview = 0; for (int i = 0; i < nq; i++) nview += mp_in_view[i];
+  res->greedy_rounds = T->rounds; res->reserved = nview;
+  return 0;
+}
+
 int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, const double* Tcw, float log_scale_factor,
                          const double* mp_Xw, const double* mp_normal, const float* mp_min_dist, const float* mp_max_dist, const uint8_t* mp_desc,
                          const uint8_t* mp_state, int n_mp, const double* slot_Xw, const uint8_t* slot_state, int n_kp, float th, float nnratio,
@@ -1503,55 +1554,59 @@ int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, co
   ORBHIP_REQUIRE(n_mp == 0 || (mp_Xw && mp_normal && mp_min_dist && mp_max_dist && mp_desc && mp_state), ORBHIP_EINVAL, "NULL map-point argument");
   const TrkFrame& TF = g_trk_frame;
   ThreadWs& W = thread_ws();
-  static thread_local uint32_t cand_hw = 0;
   int nlevels = 0, rc = 0;
   if ((rc = trk_dims(ctx, -1, nullptr, &nlevels))) return rc;
   const int nq = n_mp;
-  TlmIn I; std::memset(&I, 0, sizeof(I));
-  for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) I.C.R[3 * r + c] = Tcw[4 * r + c]; I.C.t[r] = Tcw[4 * r + 3]; }
-  for (int k = 0; k < 3; k++) I.C.Ow[k] = -(I.C.R[k] * I.C.t[0] + I.C.R[3 + k] * I.C.t[1] + I.C.R[6 + k] * I.C.t[2]);      // Ow = -Rcw^T tcw (src/Frame.cc:188)
-  I.C.fx = K4[0]; I.C.fy = K4[1]; I.C.cx = K4[2]; I.C.cy = K4[3];
-  I.C.min_x = bounds[0]; I.C.max_x = bounds[1]; I.C.min_y = bounds[2]; I.C.max_y = bounds[3];
-  I.C.cos_limit = 0.5f; I.C.log_scale = log_scale_factor; I.C.nlevels = nlevels;          // isInFrustum(map_point, 0.5) (src/Tracking.cc:822)
-  for (int k = 0; k < 4; k++) I.K4[k] = K4[k];
-  I.th = th; I.ratio = nnratio; I.n_mp = n_mp; I.n_kp_host = n_kp;
-  // a distance can win only if it is <= TH_HIGH and can veto through the ratio test only if ratio * d < TH_HIGH
-  { int dm = TRK_TH_HIGH; while (dm < 255 && nnratio * (float)(dm + 1) < (float)TRK_TH_HIGH) dm++; I.dmax = dm; }
+  TlmIn I; tlm_prepare(I, K4, bounds, Tcw, log_scale_factor, nlevels, n_mp, n_kp, th, nnratio);
   for (int attempt = 0; attempt < 2; attempt++) {
     if ((rc = W.begin()) || (rc = trk_require_resident(TF, W.device, ctx, nlevels, -1))) return rc;
     ORBHIP_REQUIRE(n_kp == TF.n_kp, ORBHIP_EINVAL, "n_kp differs from the resident frame's keypoint count");
     if ((rc = trk_pose7(Tcw, I.pose7)) || (rc = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr))) return rc;
-    const int icap = TF.icap;
     ThreadWs::Pack in;
     const int pI = in.add(&I, sizeof(I)), pX = in.add(mp_Xw, 24 * (size_t)nq), pN = in.add(mp_normal, 24 * (size_t)nq), pMi = in.add(mp_min_dist, 4 * (size_t)nq),
               pMa = in.add(mp_max_dist, 4 * (size_t)nq), pD = in.add(mp_desc, 32 * (size_t)nq), pS = in.add(mp_state, (size_t)nq), pSX = in.add(slot_Xw, 24 * (size_t)n_kp),
               pSS = in.add(slot_state, (size_t)n_kp);
     if ((rc = W.commit(in))) return rc;
-    // output block: [pose tail | in_view | match | owner]
-    Carve C; TrkPoseTail P; TrkWindows Q;
-    P.carve(C, icap);
-    const size_t oView = C.take((size_t)std::max(nq, 1)), oMatch = C.take(4 * (size_t)std::max(nq, 1)), oOwner = C.take(4 * (size_t)icap);
-    uint8_t* dblk = W.d<uint8_t>(C.total, &rc);
-    Q.alloc(W, nq, 32u, cand_hw, &rc); P.alloc(W, icap, &rc);
-    if (rc) return rc;
-    const TlmIn* dI = in.dev<TlmIn>(pI);
-    hipLaunchKernelGGL(k_tlm_frustum, dim3((std::max(nq, 1) + 255) / 256), dim3(256), 0, W.s, dI, in.dev<double>(pX), in.dev<double>(pN), in.dev<float>(pMi), in.dev<float>(pMa),
-                       in.dev<uint8_t>(pS), dblk + oView, Q.quv, Q.qr, Q.qlo, Q.qhi, Q.qv, Q.total);
-    Q.launch(W.s, TF, in.dev<uint8_t>(pD), I.dmax);
-    if ((rc = raise_dynamic_lds((const void*)k_tlm_greedy, W.device, 4 * TLM_MAXMP))) return rc;
-    hipLaunchKernelGGL(k_tlm_greedy, dim3(1), dim3(1024), 4 * TLM_MAXMP, W.s, dI, Q.qv, Q.acc, Q.accn, Q.off, Q.total, Q.pairs, Q.cand_cap, TF.kps4.as<float>(),
-                       (const int32_t*)(TF.blk.as<uint8_t>() + TF.oCnt), icap, in.dev<double>(pX), in.dev<double>(pSX), in.dev<uint8_t>(pSS), (int32_t*)(dblk + oMatch),
-                       (int32_t*)(dblk + oOwner), (int32_t*)(dblk + P.oFeat), P.oX, P.ouv, P.ow, P.ooff, (double*)(dblk + P.oPose), P.K4, (TrkOut*)(dblk + P.oOut), nq);
-    if ((rc = P.solve(dblk, W.s))) return rc;
-    const uint8_t* hb = W.down(dblk, C.total, &rc);
-    if (rc || (rc = W.sync())) return rc;
-    if (Q.regrown((uint32_t)((const TrkOut*)(hb + P.oOut))->cand_total, cand_hw)) continue;
-    if (nq) { std::memcpy(mp_in_view, hb + oView, (size_t)nq); std::memcpy(mp_match, hb + oMatch, 4 * (size_t)nq); }
-    std::memcpy(slot_owner, hb + oOwner, 4 * (size_t)n_kp);
-    const TrkOut* T = P.unpack(hb, I.pose7, n_kp, outlier_out, res);
-    int nview = 0; for (int i = 0; i < nq; i++) nview += mp_in_view[i];
-    res->greedy_rounds = T->rounds; res->reserved = nview;
-    return 0;
+    bool again = false;
+    if ((rc = tlm_run(W, TF, I, in.dev<TlmIn>(pI), in.dev<double>(pX), in.dev<double>(pN), in.dev<float>(pMi), in.dev<float>(pMa), in.dev<uint8_t>(pD), in.dev<uint8_t>(pS),
+                      in.dev<double>(pSX), in.dev<uint8_t>(pSS), nq, n_kp, mp_in_view, mp_match, slot_owner, outlier_out, res, &again))) return rc;
+    if (!again) return 0;
+  }
+  return TrkWindows::no_fit();
+}
+
+int orbt_track_local_map_device(orbx_ctx* ctx, const float* K4, const float* bounds, const double* Tcw, float log_scale_factor, const double* d_mp_Xw,
+                                const double* d_mp_normal, const float* d_mp_min_dist, const float* d_mp_max_dist, const uint8_t* d_mp_desc, const uint8_t* d_mp_state,
+                                int n_mp, const double* d_slot_Xw, const uint8_t* d_slot_state, int n_kp, float th, float nnratio, void* stream, uint8_t* mp_in_view,
+                                int32_t* mp_match, int32_t* slot_owner, uint8_t* outlier_out, orbt_result* res) {
+  CallClock call_clock;
+  ORBHIP_REQUIRE(ctx && K4 && bounds && Tcw && res && mp_in_view && mp_match && slot_owner && outlier_out && d_slot_Xw && d_slot_state, ORBHIP_EINVAL, "NULL argument");
+  ORBHIP_REQUIRE(n_mp >= 0 && n_mp <= TLM_MAXMP, ORBHIP_ECAP, "more than 16384 local map points per call");
+  ORBHIP_REQUIRE(n_mp == 0 || (d_mp_Xw && d_mp_normal && d_mp_min_dist && d_mp_max_dist && d_mp_desc && d_mp_state), ORBHIP_EINVAL, "NULL map-point argument");
+  ORBHIP_REQUIRE((uintptr_t)d_mp_Xw % 8 == 0 && (uintptr_t)d_mp_normal % 8 == 0 && (uintptr_t)d_slot_Xw % 8 == 0 && (uintptr_t)d_mp_min_dist % 4 == 0 &&
+                 (uintptr_t)d_mp_max_dist % 4 == 0 && (uintptr_t)d_mp_desc % 16 == 0, ORBHIP_EINVAL, "misaligned device array");
+  const TrkFrame& TF = g_trk_frame;
+  ThreadWs& W = thread_ws();
+  int nlevels = 0, rc = 0;
+  if ((rc = trk_dims(ctx, -1, nullptr, &nlevels))) return rc;
+  TlmIn I; tlm_prepare(I, K4, bounds, Tcw, log_scale_factor, nlevels, n_mp, n_kp, th, nnratio);
+  static thread_local hipEvent_t produced = nullptr;           // what `stream` holds so far, for the call's own stream to wait for
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if ((rc = W.begin()) || (rc = trk_require_resident(TF, W.device, ctx, nlevels, -1))) return rc;
+    ORBHIP_REQUIRE(n_kp == TF.n_kp, ORBHIP_EINVAL, "n_kp differs from the resident frame's keypoint count");
+    if ((rc = trk_pose7(Tcw, I.pose7)) || (rc = orbx_get_tables(ctx, I.scale, nullptr, nullptr, I.inv_sigma2, nullptr))) return rc;
+    if ((hipStream_t)stream != W.s && attempt == 0) {
+      if (!produced) ORBHIP_CHECK_HIP(hipEventCreateWithFlags(&produced, hipEventDisableTiming));
+      ORBHIP_CHECK_HIP(hipEventRecord(produced, (hipStream_t)stream));
+      ORBHIP_CHECK_HIP(hipStreamWaitEvent(W.s, produced, 0));
+    }
+    ThreadWs::Pack in;
+    const int pI = in.add(&I, sizeof(I));
+    if ((rc = W.commit(in))) return rc;
+    bool again = false;
+    if ((rc = tlm_run(W, TF, I, in.dev<TlmIn>(pI), d_mp_Xw, d_mp_normal, d_mp_min_dist, d_mp_max_dist, d_mp_desc, d_mp_state, d_slot_Xw, d_slot_state, n_mp, n_kp,
+                      mp_in_view, mp_match, slot_owner, outlier_out, res, &again))) return rc;
+    if (!again) return 0;
   }
   return TrkWindows::no_fit();
 }
@@ -1689,3 +1744,4 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
 
 #include "orb_pnp.inc"                  /* PnPsolver::iterate with EPnP for a batch of candidates: orbt_pnp_* */
 #include "orb_sim3solver.inc"          /* Sim3Solver::iterate (Horn inside RANSAC) for a batch of loop candidates: orbt_sim3_* */
+#include "orb_localupdate.inc"         /* Tracking::UpdateLocalMap: local keyframes, local points and the gather TrackLocalMap reads: orbt_update_local_* */

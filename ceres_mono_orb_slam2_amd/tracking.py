@@ -238,3 +238,150 @@ def relocalization_search_by_bow(extractor, vocabulary, image, K4, bounds, candi
     k = nk.value
     return dict(kps=kps[:k] if img is not None else None, kps_undistorted=und, desc=desc[:k] if img is not None else None, bow=(bw[:nw.value], bv[:nw.value]),
                 fv=(on[:nf.value], oo[:nf.value + 1], oi[:oo[nf.value]]), owner=owner[:nc, :k], nmatches=nm[:nc], n_keypoints=k)
+
+
+# ---- Tracking::UpdateLocalMap (reference src/Tracking.cc:838-977; include/orbslam_hip.h states the tables and the semantics) ----
+ULM_OK, ULM_NO_VOTES = 0, 1
+_PACKED = (("mp_Xw", np.float64, 3), ("mp_normal", np.float64, 3), ("mp_min_dist", np.float32, 1), ("mp_max_dist", np.float32, 1), ("mp_desc", np.uint8, 32),
+           ("mp_state", np.uint8, 1), ("slot_Xw", np.float64, 3), ("slot_state", np.uint8, 1))
+
+
+def _i32(a):
+    return None if a is None else _c(a, np.int32).reshape(-1)
+
+
+def _a(a):
+    return None if a is None else _addr(a)
+
+
+def update_local_keyframes(frame_pt, pt_bad, obs_off, obs_kf, kf_bad, kf_rank, kf_parent, cov_off, cov_kf, child_off, child_kf, prev_local_kf, cap_kf=None,
+                           votes=True, out=None, check=True):
+    """Tracking::UpdateLocalKeyFrames over the graph alone (orbt_update_local_keyframes).  kf_rank None = index order.  out: optional dict
+    of preset output arrays (frame_pt_out, local_kf[cap_kf], votes).  Returns dict(frame_pt_out, local_kf (the list), n_local_kf, ref_kf
+    (-1 = leave reference_keyframe_ alone), status (ULM_OK / ULM_NO_VOTES), votes).  check=False: a failing call returns dict(rc, n_local_kf)
+    instead of raising (ORBHIP_ECAP writes the count alone)."""
+    L = _lib.load()
+    fp = _i32(frame_pt); pb = _c(pt_bad, np.uint8).reshape(-1); oo = _i32(obs_off); ok_ = _i32(obs_kf)
+    kb = _c(kf_bad, np.uint8).reshape(-1); kr = _i32(kf_rank); kp = _i32(kf_parent); co = _i32(cov_off); ck = _i32(cov_kf); ho = _i32(child_off); hk = _i32(child_kf)
+    pv = _i32(prev_local_kf)
+    npts, nkf = len(pb), len(kb)
+    assert (npts == 0 or len(oo) == npts + 1) and len(kp) == nkf and (kr is None or len(kr) == nkf) and (nkf == 0 or (len(co) == nkf + 1 and len(ho) == nkf + 1))
+    assert (npts == 0 or len(ok_) >= oo[-1]) and (nkf == 0 or (len(ck) >= co[-1] and len(hk) >= ho[-1]))          # (the library checks the rest)
+    cap = max(nkf, len(pv)) if cap_kf is None else int(cap_kf)
+    o = {} if out is None else out
+    o.setdefault("frame_pt_out", np.full(len(fp), -1, np.int32)); o.setdefault("local_kf", np.full(cap, -1, np.int32))
+    if votes:
+        o.setdefault("votes", np.zeros(nkf, np.int32))
+    for k, n in (("frame_pt_out", len(fp)), ("local_kf", cap), ("votes", nkf)):
+        assert o.get(k) is None or (o[k].dtype == np.int32 and o[k].flags.c_contiguous and o[k].size == n), k
+    n = C.c_int(0); ref = C.c_int(-1); st = C.c_int(0)
+    rc = L.orbt_update_local_keyframes(len(fp), _a(fp), npts, _a(pb), _a(oo), _a(ok_), nkf, _a(kb), _a(kr), _a(kp), _a(co), _a(ck), _a(ho), _a(hk), len(pv), _a(pv),
+                                       cap, _a(o["frame_pt_out"]), _a(o["local_kf"]), C.byref(n), C.byref(ref), C.byref(st), _a(o.get("votes")))
+    if not check and rc:
+        return dict(rc=rc, n_local_kf=n.value)
+    _lib.check(rc, "orbt_update_local_keyframes")
+    return dict(frame_pt_out=o["frame_pt_out"], local_kf=o["local_kf"][:n.value], n_local_kf=n.value, ref_kf=ref.value, status=st.value, votes=o.get("votes"))
+
+
+def update_local_points(kf_slot_off, kf_slot_pt, pt_bad, pt_nobs, pt_Xw, pt_normal, pt_min_dist, pt_max_dist, pt_desc, frame_pt, seen_pt, cap_pt, packed=True, out=None,
+                        check=True):
+    """Tracking::UpdateLocalPoints over the slot tables of the local keyframes (row i = the i-th local keyframe) and, with packed=True,
+    the arrays track_local_map takes (orbt_update_local_points).  out: optional dict of preset output arrays.  Returns dict(local_pt (the
+    list), n_local_pt, and the eight packed arrays at their full capacity: mp_*[cap_pt], slot_*[n_kp])."""
+    L = _lib.load()
+    so = _i32(kf_slot_off); sp = _i32(kf_slot_pt); pb = _c(pt_bad, np.uint8).reshape(-1); fp = _i32(frame_pt); se = _i32(seen_pt)
+    npts, nl, nk, cap = len(pb), len(so) - 1, len(fp), int(cap_pt)
+    assert nl >= 0 and len(sp) >= so[-1]
+    rec = [None] * 6
+    if packed:
+        rec = [_i32(pt_nobs), _c(pt_Xw, np.float64).reshape(-1, 3), _c(pt_normal, np.float64).reshape(-1, 3), _c(pt_min_dist, np.float32).reshape(-1),
+               _c(pt_max_dist, np.float32).reshape(-1), _c(pt_desc, np.uint8).reshape(-1, 32)]
+        assert all(len(r) == npts for r in rec)
+    o = {} if out is None else out
+    o.setdefault("local_pt", np.full(cap, -1, np.int32))
+    assert o["local_pt"].dtype == np.int32 and o["local_pt"].size == cap
+    if packed:
+        for k, dt, w in _PACKED:
+            n = (nk if k.startswith("slot") else cap) * w
+            o.setdefault(k, np.zeros(n, dt))
+            assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == n, k
+    n = C.c_int(0)
+    rc = L.orbt_update_local_points(nl, _a(so), _a(sp), npts, _a(pb), *[_a(r) for r in rec], nk, _a(fp), len(se), _a(se), cap, _a(o["local_pt"]), C.byref(n),
+                                    *[_a(o.get(k)) for k, _, _ in _PACKED])
+    if not check and rc:
+        return dict(rc=rc, n_local_pt=n.value)
+    _lib.check(rc, "orbt_update_local_points")
+    r = dict(local_pt=o["local_pt"][:n.value], n_local_pt=n.value)
+    for k, _, w in _PACKED:
+        r[k] = None if o.get(k) is None else (o[k].reshape(-1, w) if w > 1 else o[k])
+    return r
+
+
+def update_local_map_device(T, cap_kf, cap_pt, max_local_slots=None, packed=True, votes=True, out=None):
+    """orbt_update_local_map_device on torch CUDA tensors, enqueued on the current stream, no synchronisation.  T: dict of the resident
+    tables, named as in the header: frame_pt, seen_pt, prev_local_kf, pt_bad, pt_nobs, obs_off, obs_kf, pt_Xw, pt_normal, pt_min_dist,
+    pt_max_dist, pt_desc, kf_bad, kf_rank (or None), kf_parent, cov_off, cov_kf, child_off, child_kf, kf_slot_off, kf_slot_pt (int32 /
+    uint8 / float64 / float32 as there).  max_local_slots None = all slots.  out: optional dict of preset device tensors.  Returns a
+    dict of device tensors: frame_pt_out, local_kf[cap_kf], local_pt[cap_pt], counts[4] = (n_local_kf, ref_kf, n_local_pt, status), votes,
+    the eight packed arrays, status (the d_status word as int32[1]); the workspace is kept alive by the result."""
+    import torch
+    L = _lib.load()
+    dev = T["pt_bad"].device
+    n_kp, n_seen, n_prev = T["frame_pt"].numel(), T["seen_pt"].numel(), T["prev_local_kf"].numel()
+    npts, nkf = T["pt_bad"].numel(), T["kf_bad"].numel()
+    nobs, ncov, nchild, nslots = T["obs_kf"].numel(), T["cov_kf"].numel(), T["child_kf"].numel(), T["kf_slot_pt"].numel()
+    mls = nslots if max_local_slots is None else int(max_local_slots)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbt_update_local_map_workspace(nkf, npts, mls, C.byref(nbytes)), "orbt_update_local_map_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    o = {} if out is None else out
+    tdt = {np.float64: torch.float64, np.float32: torch.float32, np.uint8: torch.uint8}
+    want = [("frame_pt_out", torch.int32, n_kp), ("local_kf", torch.int32, cap_kf), ("local_pt", torch.int32, cap_pt), ("counts", torch.int32, 4)]
+    if votes:
+        want.append(("votes", torch.int32, nkf))
+    if packed:
+        want += [(k, tdt[dt], (n_kp if k.startswith("slot") else cap_pt) * w) for k, dt, w in _PACKED]
+    for k, dt, n in want:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 4), dtype=dt, device=dev)[:n]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    g = T.get
+    _lib.check(L.orbt_update_local_map_device(
+        n_kp, p(g("frame_pt")), n_seen, p(g("seen_pt")), n_prev, p(g("prev_local_kf")), npts, p(g("pt_bad")), p(g("pt_nobs")), nobs, p(g("obs_off")), p(g("obs_kf")),
+        p(g("pt_Xw")), p(g("pt_normal")), p(g("pt_min_dist")), p(g("pt_max_dist")), p(g("pt_desc")), nkf, p(g("kf_bad")), p(g("kf_rank")), p(g("kf_parent")), ncov,
+        p(g("cov_off")), p(g("cov_kf")), nchild, p(g("child_off")), p(g("child_kf")), nslots, p(g("kf_slot_off")), p(g("kf_slot_pt")), mls, int(cap_kf), int(cap_pt),
+        p(o["frame_pt_out"]), p(o["local_kf"]), p(o["local_pt"]), C.c_void_p(o["counts"].data_ptr()), p(o.get("votes")), *[p(o.get(k)) for k, _, _ in _PACKED],
+        C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbt_update_local_map_device")
+    r = dict(o)
+    for k, _, w in _PACKED:
+        if r.get(k) is not None and w > 1:
+            r[k] = r[k].view(-1, w)
+    r["status"] = status; r["_workspace"] = ws
+    return r
+
+
+def track_local_map_device(extractor, K4, bounds, Tcw, log_scale_factor, packed, n_mp, th=1.0, nnratio=0.8):
+    """track_local_map on the packed DEVICE arrays update_local_map_device returned (`packed`: that dict, or any dict of torch CUDA tensors
+    mp_Xw, mp_normal, mp_min_dist, mp_max_dist, mp_desc, mp_state, slot_Xw, slot_state) - orbt_track_local_map_device.  n_mp: the number
+    of rows to run over, at least the count of local map points (the capacity is always right: padding rows have mp_state 0).  The
+    arrays are taken as the current torch stream leaves them.  Returns what track_local_map returns."""
+    import torch
+    L = _lib.load()
+    K4 = _c(K4, np.float32); bounds = _c(bounds, np.float32)
+    T = np.ascontiguousarray(np.asarray(Tcw, np.float64).reshape(-1)[:12])
+    n = int(n_mp); nk = packed["slot_state"].numel()
+    assert packed["mp_state"].numel() >= n and packed["mp_desc"].numel() >= 32 * n and packed["mp_Xw"].numel() >= 3 * n and packed["slot_Xw"].numel() == 3 * nk
+    in_view = np.zeros(max(n, 1), np.uint8); match = np.full(max(n, 1), -1, np.int32)
+    owner = np.full(max(nk, 1), -1, np.int32); outl = np.zeros(max(nk, 1), np.uint8)
+    res = TrackResult()
+    p = lambda k: C.c_void_p(packed[k].data_ptr())                                  # noqa: E731
+    _lib.check(L.orbt_track_local_map_device(extractor._h, _addr(K4), _addr(bounds), _addr(T), float(log_scale_factor), p("mp_Xw"), p("mp_normal"), p("mp_min_dist"),
+                                             p("mp_max_dist"), p("mp_desc"), p("mp_state"), n, p("slot_Xw"), p("slot_state"), nk, float(th), float(nnratio),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream), _addr(in_view), _addr(match), _addr(owner), _addr(outl), C.byref(res)),
+               "orbt_track_local_map_device")
+    return dict(in_view=in_view[:n].view(np.bool_), match=match[:n], owner=owner[:nk], outlier=outl[:nk].view(np.bool_), pose7=np.array(res.pose7[:], np.float64),
+                nmatches=res.nmatches, n_inliers=res.n_inliers, n_correspondences=res.n_correspondences, n_in_view=res.reserved, greedy_rounds=res.greedy_rounds)

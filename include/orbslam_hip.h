@@ -825,6 +825,87 @@ int orbt_track_local_map(orbx_ctx* ctx, const float* K4, const float* bounds, co
                          const uint8_t* mp_desc, const uint8_t* mp_state, int n_mp, const double* slot_Xw, const uint8_t* slot_state,
                          int n_kp, float th, float nnratio, uint8_t* mp_in_view, int32_t* mp_match, int32_t* slot_owner,
                          uint8_t* outlier, orbt_result* res);
+/* The same with the map-point and slot arrays as DEVICE pointers: the packed mp_* / slot_* arrays orbt_update_local_map_device wrote on
+ * `stream` (the call's own stream waits for the work enqueued on `stream` so far; NULL = the default stream).  n_mp is given by the
+ * caller: at least the number of local map points and at most 16384 - the rows from the count up to cap_pt carry mp_state = 0, so
+ * n_mp = cap_pt needs no knowledge of the count; such rows come back as "not in view, -1".  The arrays d_mp_Xw, d_mp_normal and
+ * d_slot_Xw are 8-byte, d_mp_min_dist and d_mp_max_dist 4-byte, d_mp_desc 16-byte aligned.  Outputs are host arrays, the call is synchronous, and it
+ * runs the same kernels on the same bytes as orbt_track_local_map: the results are identical.                                     */
+int orbt_track_local_map_device(orbx_ctx* ctx, const float* K4, const float* bounds, const double* Tcw, float log_scale_factor,
+                                const double* d_mp_Xw, const double* d_mp_normal, const float* d_mp_min_dist, const float* d_mp_max_dist,
+                                const uint8_t* d_mp_desc, const uint8_t* d_mp_state, int n_mp, const double* d_slot_Xw,
+                                const uint8_t* d_slot_state, int n_kp, float th, float nnratio, void* stream, uint8_t* mp_in_view,
+                                int32_t* mp_match, int32_t* slot_owner, uint8_t* outlier, orbt_result* res);
+
+/* ---- Tracking::UpdateLocalMap (src/Tracking.cc:838-977) = UpdateLocalKeyFrames (:874-977) + UpdateLocalPoints (:847-872), and what
+ * SearchLocalPoints (:793-826) fixes from that state, so that the result IS orbt_track_local_map's input.  All ids are int32.
+ *   points 0..npts-1: pt_bad (isBad()), pt_nobs (Observations()), the observers as CSR obs_off[npts + 1] into obs_kf[] (any order
+ *     within a point), the records pt_Xw[3] / pt_normal[3] (double), pt_min_dist / pt_max_dist (float), pt_desc[32].
+ *   keyframes 0..nkf-1: kf_bad; kf_rank[nkf], a permutation: the position of the keyframe in the caller's std::map<KeyFrame*, ...>
+ *     order (the reference iterates keyframeCounter in pointer order, :906; NULL = index order); kf_parent (-1 = none); the best
+ *     covisibles as CSR cov_off / cov_kf, at most 10 per keyframe in GetBestCovisibilityKeyFrames(10) order; the children as CSR
+ *     child_off / child_kf in the caller's std::set order; the slot table as CSR kf_slot_off / kf_slot_pt (point id or -1).
+ *   frame: frame_pt[n_kp] (point id or -1); seen_pt[n_seen]: the points whose last_seen_frame_id_ already equals the current frame id
+ *     without sitting in a slot (the outliers TrackWithMotionModel discarded, :655-659); prev_local_kf[n_prev <= nkf]: local_keyframes_
+ *     of the frame before.
+ *   PRECONDITION: no keyframe or point carries track_reference_for_frame_ == the current frame id at entry (one UpdateLocalMap per
+ *     frame id).
+ * UpdateLocalKeyFrames, quirks included: (1) a slot whose point is bad is cleared (frame_pt_out); (2) every other held point adds one
+ * vote to each observer; (3) nobody voted: status = ORBT_ULM_NO_VOTES, local_kf = prev_local_kf unchanged, ref_kf = -1 ("leave
+ * reference_keyframe_ alone"); (4) otherwise the voted keyframes that are not bad in ascending kf_rank, marked; (5) ref_kf = the first
+ * of them whose count is strictly greater than all before it (:913; -1 when every voted keyframe is bad); (6) the walk of :924-971 over
+ * the VOTED keyframes (the reference takes its end iterator before the first append, :924-925, so an appended keyframe is never
+ * visited itself): it stops when the size of the growing list is > 80, tested at the top of each iteration; per keyframe the first neighbour that is not
+ * bad and not marked, then the first such child, then the parent if it is not marked (isBad() is NOT asked of the parent) - and after
+ * a parent the whole walk ends (:968).  A voted list longer than 80 is kept whole.
+ * UpdateLocalPoints: over local_kf in order and the slots in order, a point is appended at its first occurrence if it is not bad.
+ * SearchLocalPoints' part: mp_state[j] = 0 when the point sits in a slot of frame_pt_out or is in seen_pt, else 1 with pt_nobs > 0,
+ * else 3; rows j >= n_local_pt up to cap_pt get mp_state = 0 (their other fields are not written); slot_state[f] = 0 for an empty slot,
+ * else 1 / 3 by pt_nobs, slot_Xw[f] = the point's position (zeros for an empty slot).
+ *
+ * Host pointers, synchronous, one packed upload and one download each.  ORBHIP_EINVAL before any device work for negative counts, CSR
+ * offsets that do not ascend from 0, ids out of range, a kf_rank that is not a permutation, more than 10 covisibles in a row, NULL
+ * where an array is needed; ORBHIP_ENODEV without a GPU; ORBHIP_ECAP, with only the count written, when a list does not fit.
+ * orbt_update_local_keyframes: the graph alone.  votes[nkf] is nullable.                                                            */
+#define ORBT_ULM_OK 0
+#define ORBT_ULM_NO_VOTES 1
+int orbt_update_local_keyframes(int n_kp, const int32_t* frame_pt, int npts, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, int nkf,
+                                const uint8_t* kf_bad, const int32_t* kf_rank, const int32_t* kf_parent, const int32_t* cov_off, const int32_t* cov_kf,
+                                const int32_t* child_off, const int32_t* child_kf, int n_prev, const int32_t* prev_local_kf, int cap_kf, int32_t* frame_pt_out,
+                                int32_t* local_kf, int32_t* n_local_kf, int32_t* ref_kf, int32_t* status, int32_t* votes);
+/* orbt_update_local_points: its OWN small tables - row i of kf_slot_off[n_local_kf + 1] / kf_slot_pt is the slot table of the i-th
+ * local keyframe, the points are numbered by the caller over what those tables and the frame name; frame_pt = the frame's slots (a
+ * bad point's slot counts as cleared).  The eight packed outputs mp_Xw[3 cap_pt], mp_normal[3 cap_pt], mp_min_dist, mp_max_dist,
+ * mp_desc[32 cap_pt], mp_state[cap_pt], slot_Xw[3 n_kp], slot_state[n_kp] are given all or none; without them pt_nobs and the records
+ * may be NULL.                                                                                                                    */
+int orbt_update_local_points(int n_local_kf, const int32_t* kf_slot_off, const int32_t* kf_slot_pt, int npts, const uint8_t* pt_bad, const int32_t* pt_nobs,
+                             const double* pt_Xw, const double* pt_normal, const float* pt_min_dist, const float* pt_max_dist, const uint8_t* pt_desc, int n_kp,
+                             const int32_t* frame_pt, int n_seen, const int32_t* seen_pt, int cap_pt, int32_t* local_pt, int32_t* n_local_pt, double* mp_Xw,
+                             double* mp_normal, float* mp_min_dist, float* mp_max_dist, uint8_t* mp_desc, uint8_t* mp_state, double* slot_Xw, uint8_t* slot_state);
+/* Both stages over caller-resident DEVICE tables, enqueued on `stream`, no synchronisation inside.  nobs = obs_off[npts], ncov, nchild
+ * and nslots = the lengths of the four CSR entry arrays, given by the caller; max_local_slots bounds the slots of the local keyframes
+ * together (it sizes the launches: 80 keyframes x their largest slot table, or nslots).  Outputs in caller device buffers:
+ * d_frame_pt_out[n_kp] (nullable), d_local_kf[cap_kf], d_local_pt[cap_pt], d_counts[4] = {n_local_kf, ref_kf, n_local_pt, status},
+ * d_votes[nkf] (nullable), the eight packed arrays (all or none).  Counts, NULLs and alignment (4 bytes for 32-bit arrays, 16 bytes
+ * for the double / descriptor records, the packed outputs and the workspace) are checked on the host; the data is bounds-checked on
+ * the device: an entry out of range is treated as absent and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = index
+ * (or kf_rank not a permutation), 4 = n_local_kf > cap_kf, 8 = n_local_pt > cap_pt, 16 = the local keyframes hold more than
+ * max_local_slots slots.  With bit 4 or 16 the points stage sees an empty list; with bit 8 every packed row is padding; d_counts keeps
+ * the wanted counts and nothing is written beyond a capacity.  A row of cov_kf longer than 10 is walked whole.
+ * `d_workspace`: orbt_update_local_map_workspace(...) bytes, 16-byte aligned, not shared with concurrent calls; it is cleared by
+ * every call.                                                                                                                     */
+int orbt_update_local_map_device(int n_kp, const int32_t* d_frame_pt, int n_seen, const int32_t* d_seen_pt, int n_prev, const int32_t* d_prev_local_kf, int npts,
+                                 const uint8_t* d_pt_bad, const int32_t* d_pt_nobs, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                 const double* d_pt_Xw, const double* d_pt_normal, const float* d_pt_min_dist, const float* d_pt_max_dist, const uint8_t* d_pt_desc,
+                                 int nkf, const uint8_t* d_kf_bad, const int32_t* d_kf_rank, const int32_t* d_kf_parent, int ncov, const int32_t* d_cov_off,
+                                 const int32_t* d_cov_kf, int nchild, const int32_t* d_child_off, const int32_t* d_child_kf, int nslots,
+                                 const int32_t* d_kf_slot_off, const int32_t* d_kf_slot_pt, int max_local_slots, int cap_kf, int cap_pt, int32_t* d_frame_pt_out,
+                                 int32_t* d_local_kf, int32_t* d_local_pt, int32_t* d_counts, int32_t* d_votes, double* d_mp_Xw, double* d_mp_normal,
+                                 float* d_mp_min_dist, float* d_mp_max_dist, uint8_t* d_mp_desc, uint8_t* d_mp_state, double* d_slot_Xw, uint8_t* d_slot_state,
+                                 uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbt_update_local_map_device needs (host arithmetic), each section rounded up to 256 bytes: four 32-bit arrays
+ * of nkf entries and one of nkf + 1, two of npts, one of max(1, ceil(max_local_slots / 256)) entries (the compaction tiles), 8 bytes. */
+int orbt_update_local_map_workspace(int nkf, int npts, int max_local_slots, size_t* bytes);
 
 /* ---- Tracking::TrackReferenceKeyFrame's data-parallel core in one call (src/Tracking.cc:566-615): Frame::ComputeBoW (src/Frame.cc:
  * 322-327, the vocabulary descent), ORBmatcher::SearchByBoW(reference_keyframe_, current_frame_, ...) (src/ORBmatcher.cc:151-256,
