@@ -1602,6 +1602,114 @@ struct FrameOpsT {
     }
   }
 
+  // KeyFrame::UpdateConnections (src/KeyFrame.cc:314-398) on every keyframe of `keyframes`, in order, in ONE library call
+  // (orbl_update_connections): `FrameOpsHip::UpdateConnections({current_keyframe_});` in LocalMapping (src/LocalMapping.cc:161, :487),
+  // `FrameOpsHip::UpdateConnections(current_connected_keyframes_, &loop_connections);` for the loop of LoopClosing::CorrectLoop
+  // (src/LoopClosing.cc:551-573), which then holds what :561-572 put into loop_connections.  Only the part of the graph the loop can touch
+  // is flattened: the targets, the observers of their points, and connected_keyframe_weights_ of those keyframes (the keyframes these
+  // maps name are indexed too, with empty rows: nothing is ever sent to them).  kf_rank = the order under std::less<KeyFrame*>, which is the
+  // iteration order of keyframe_counter, the tie-break of both sorts and the order of the std::set.  Written back on the keyframes the
+  // loop would have written: connected_keyframe_weights_, ordered_connected_keyframes_, ordered_weights_, and for a first connection
+  // parent_ + AddChild and is_first_connection_ - members the reference keeps protected: the friend declaration of INTEGRATION.md
+  // section 4.  Each keyframe's members are read and written under its mutex_connections_; the caller holds what the reference's call
+  // sites hold (nothing in LocalMapping, Map::mutex_map_update_ in CorrectLoop).  A keyframe listed twice: nothing is called, nothing is
+  // changed, returns -1.  Otherwise returns the number of keyframes written.
+  // (A member template over the keyframe type, as KeyFrameCulling is.)
+  template <class KF> static int UpdateConnections(const std::vector<KF*>& keyframes, std::map<KF*, std::set<KF*> >* loop_connections = nullptr, int th = 15) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(keyframes[0]->GetMapPointMatches()[0])>::type>::type MP;
+    const int ntgt = (int)keyframes.size();
+    if (ntgt == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::vector<int32_t> tgt_kf(ntgt);
+    for (int t = 0; t < ntgt; t++) {
+      if (kf_at.count(keyframes[t])) return -1;
+      tgt_kf[t] = kf_index(keyframes[t]);                           // (targets are numbered first: index = list position)
+    }
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<int32_t> slot_off(1, 0), slot_pt, obs_off(1, 0), obs_kf, prev_off(1, 0), prev_kf;
+    std::vector<uint8_t> tgt_flags(ntgt, 0), pt_bad;
+    for (int t = 0; t < ntgt; t++) {
+      KF* kf = keyframes[t];
+      { std::unique_lock<std::mutex> lock = lock_connections(kf, 0); tgt_flags[t] = (kf->is_first_connection_ && kf->id_ != 0) ? 1 : 0; }      // (:392)
+      const std::vector<MP*> matches = kf->GetMapPointMatches();    // (:319-322)
+      for (MP* mp : matches) {
+        if (!mp) { slot_pt.push_back(-1); continue; }
+        auto it = pt_at.find(mp);
+        if (it == pt_at.end()) {
+          it = pt_at.emplace(mp, (int)pt_bad.size()).first;
+          const bool bad = mp->isBad();                             // (:333)
+          pt_bad.push_back(bad ? 1 : 0);
+          if (!bad) { const auto observations = mp->GetObservations(); for (const auto& o : observations) obs_kf.push_back(kf_index(o.first)); }      // (:335)
+          obs_off.push_back((int32_t)obs_kf.size());
+        }
+        slot_pt.push_back(it->second);
+      }
+      slot_off.push_back((int32_t)slot_pt.size());
+      if (loop_connections) {
+        const std::vector<KF*> previous = kf->GetVectorCovisibleKeyFrames();               // (LoopClosing.cc:556-557)
+        for (KF* p : previous) prev_kf.push_back(kf_index(p));
+        prev_off.push_back((int32_t)prev_kf.size());
+      }
+    }
+    const int n_rows = (int)kfs.size();                             // (targets and observers: the rows the call can read)
+    std::vector<int32_t> conn_off(1, 0), conn_kf, conn_w;
+    for (int k = 0; k < n_rows; k++) {
+      std::map<KF*, int> weights;
+      { std::unique_lock<std::mutex> lock = lock_connections(kfs[k], 0); weights = kfs[k]->connected_keyframe_weights_; }
+      for (const auto& w : weights) { conn_kf.push_back(kf_index(w.first)); conn_w.push_back(w.second); }
+      conn_off.push_back((int32_t)conn_kf.size());
+    }
+    const int nkf = (int)kfs.size(), npts = (int)pt_bad.size(), nconn = (int)conn_kf.size();
+    conn_off.resize(nkf + 1, (int32_t)nconn);
+    std::vector<int32_t> by_pointer(nkf), kf_rank(nkf);
+    for (int k = 0; k < nkf; k++) by_pointer[k] = k;
+    std::sort(by_pointer.begin(), by_pointer.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nkf; r++) kf_rank[by_pointer[r]] = r;
+    // capacities no call exceeds: a written map is a counter (at most nkf - 1 entries) or an input row plus one entry per target
+    const size_t cap = std::min((size_t)nkf * (size_t)std::max(nkf - 1, 0), (size_t)nconn + 2 * (size_t)ntgt * (size_t)nkf);
+    const size_t cap_link = loop_connections ? (size_t)ntgt * (size_t)nkf : 0;
+    if (cap > 0x7FFFFFFFu || cap_link > 0x7FFFFFFFu) throw std::runtime_error("FrameOpsT::UpdateConnections: keyframe list too large for one call");
+    std::vector<int32_t> tgt_status(ntgt), tgt_parent(ntgt), aff_kf(nkf), oconn_off(nkf + 1), oord_off(nkf + 1), oconn_kf(std::max<size_t>(cap, 1)),
+        oconn_w(std::max<size_t>(cap, 1)), oord_kf(std::max<size_t>(cap, 1)), oord_w(std::max<size_t>(cap, 1)), link_off(ntgt + 1), link_kf(std::max<size_t>(cap_link, 1));
+    int32_t counts[4] = {0, 0, 0, 0};
+    dropin::check(orbl_update_connections(ntgt, tgt_kf.data(), tgt_flags.data(), slot_off.data(), slot_pt.data(), nkf, npts, obs_off.data(), obs_kf.data(), pt_bad.data(),
+                                          kf_rank.data(), conn_off.data(), conn_kf.data(), conn_w.data(), loop_connections ? prev_off.data() : nullptr,
+                                          loop_connections ? prev_kf.data() : nullptr, th, nkf, (int)cap, (int)cap, (int)cap_link, tgt_status.data(),
+                                          tgt_parent.data(), aff_kf.data(), oconn_off.data(), oconn_kf.data(), oconn_w.data(), oord_off.data(), oord_kf.data(),
+                                          oord_w.data(), loop_connections ? link_off.data() : nullptr, loop_connections ? link_kf.data() : nullptr, counts),
+                  "orbl_update_connections");
+    for (int i = 0; i < counts[0]; i++) {                           // (:383-390, :172-193)
+      KF* kf = kfs[aff_kf[i]];
+      std::map<KF*, int> weights;
+      for (int e = oconn_off[i]; e < oconn_off[i + 1]; e++) weights.emplace_hint(weights.end(), kfs[oconn_kf[e]], oconn_w[e]);      // (rows come in map order)
+      std::vector<KF*> ordered; std::vector<int> ordered_w;
+      ordered.reserve(oord_off[i + 1] - oord_off[i]); ordered_w.reserve(oord_off[i + 1] - oord_off[i]);
+      for (int e = oord_off[i]; e < oord_off[i + 1]; e++) { ordered.push_back(kfs[oord_kf[e]]); ordered_w.push_back(oord_w[e]); }
+      std::unique_lock<std::mutex> lock = lock_connections(kf, 0);
+      kf->connected_keyframe_weights_.swap(weights); kf->ordered_connected_keyframes_.swap(ordered); kf->ordered_weights_.swap(ordered_w);
+    }
+    for (int t = 0; t < ntgt; t++) {
+      KF* kf = keyframes[t];
+      if (tgt_status[t] == 0 && tgt_parent[t] >= 0) {               // (:392-396; AddChild takes the parent's lock itself)
+        KF* parent = kfs[tgt_parent[t]];
+        { std::unique_lock<std::mutex> lock = lock_connections(kf, 0); kf->parent_ = parent; kf->is_first_connection_ = false; }
+        parent->AddChild(kf);
+      }
+      if (loop_connections) {                                       // (LoopClosing.cc:561-572)
+        std::set<KF*>& links = (*loop_connections)[kf];
+        links.clear();
+        for (int e = link_off[t]; e < link_off[t + 1]; e++) links.insert(kfs[link_kf[e]]);
+      }
+    }
+    return counts[0];
+  }
+
  private:
   // the reference's KeyFrame::mutex_connections_ when the type has it
   template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {

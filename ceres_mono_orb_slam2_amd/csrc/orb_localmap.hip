@@ -389,3 +389,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_mappoint.inc"
 // LocalMapping::KeyFrameCulling for the whole candidate list, order-dependent state included (orbl_keyframe_culling*)
 #include "orb_kfculling.inc"
+// KeyFrame::UpdateConnections for a whole keyframe list, AddConnection re-sorts and loop links included (orbl_update_connections*)
+#include "orb_updateconn.inc"

@@ -1,5 +1,6 @@
 """Host mirror of the LocalMapping thread's device-resident steps (include/orbslam_hip.h: orbl_*; reference
-src/LocalMapping.cc:196-396 CreateNewMapPoints, :398-505 SearchInNeighbors, :576-637 KeyFrameCulling).  Thin ctypes layer: arrays in, arrays out."""
+src/LocalMapping.cc:196-396 CreateNewMapPoints, :398-505 SearchInNeighbors, :576-637 KeyFrameCulling; src/KeyFrame.cc:314-398 UpdateConnections).
+Thin ctypes layer: arrays in, arrays out."""
 import ctypes as C
 
 import numpy as np
@@ -242,3 +243,104 @@ def keyframe_culling_device(cand_kf, cand_flags, slot_off, slot_pt, slot_level, 
                                               p(o["n_map_points"]), p(o.get("pt_bad")), p(o.get("pt_nobs")), p(o.get("obs_erased")), p(status), p(ws),
                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_keyframe_culling_device")
     return CullingResult(status=status, _workspace=ws, **o)
+
+
+ECAP = -4                            # ORBHIP_ECAP
+UC_OFFSETS, UC_INDEX, UC_CAP_AFF, UC_CAP_CONN, UC_CAP_ORD, UC_CAP_LINK = 1, 2, 4, 8, 16, 32      # *d_status bits of orbl_update_connections_device
+
+
+def _uc_default_caps(ntgt, nkf, nconn, links):
+    """capacities no call can exceed: a final map is a counter (at most nkf - 1 entries) or an input row plus one entry per target"""
+    cap = min(nkf * max(nkf - 1, 0), nconn + 2 * ntgt * nkf)
+    return nkf, cap, cap, (ntgt * nkf if links else 0)
+
+
+def update_connections(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, conn_off, conn_kf, conn_w, tgt_flags=None, pt_bad=None, kf_rank=None,
+                       prev_off=None, prev_kf=None, th=15, links=None, caps=None, out=None, check=True):
+    """KeyFrame::UpdateConnections on the keyframes tgt_kf, one after the other, in one call (orbl_update_connections;
+    include/orbslam_hip.h states the inputs and the semantics).  tgt_flags, pt_bad, kf_rank and the pair prev_off / prev_kf may be None;
+    links (default: whether prev is given) asks for the loop links.  caps = (cap_aff, cap_conn, cap_ord, cap_link), default: bounds no call
+    exceeds.  out: optional dict of preset output arrays of those capacities (aff_kf, conn_off, conn_kf, conn_w, ord_off, ord_kf, ord_w,
+    link_off, link_kf, tgt_status, tgt_parent, counts).  Returns a dict of int32 arrays trimmed to the written counts, with counts =
+    {n_aff, n_conn, n_ord, n_link} and rc; check=False returns rc = ORBHIP_ECAP with only counts filled instead of raising."""
+    L = _lib.load()
+    tk = _c(tgt_kf, np.int32).reshape(-1); ntgt = len(tk)
+    tf = _c(tgt_flags, np.uint8).reshape(-1) if tgt_flags is not None else None
+    so = _c(slot_off, np.int32).reshape(-1); sp = _c(slot_pt, np.int32).reshape(-1)
+    oo = _c(obs_off, np.int32).reshape(-1); ok_ = _c(obs_kf, np.int32).reshape(-1)
+    pb = _c(pt_bad, np.uint8).reshape(-1) if pt_bad is not None else None
+    kr = _c(kf_rank, np.int32).reshape(-1) if kf_rank is not None else None
+    co = _c(conn_off, np.int32).reshape(-1); ck = _c(conn_kf, np.int32).reshape(-1); cw = _c(conn_w, np.int32).reshape(-1)
+    po = _c(prev_off, np.int32).reshape(-1) if prev_off is not None else None
+    pk = _c(prev_kf, np.int32).reshape(-1) if prev_kf is not None else None
+    if pk is not None and pk.size == 0:
+        pk = np.zeros(1, np.int32)                              # (an empty list still needs a pointer: the pair is given or not)
+    npts = len(oo) - 1
+    assert len(so) == ntgt + 1 and npts >= 0 and len(co) == int(nkf) + 1 and len(ck) == len(cw) and (tf is None or len(tf) == ntgt)
+    assert (pb is None or len(pb) == npts) and (kr is None or len(kr) == nkf) and (po is None or len(po) == ntgt + 1)
+    assert len(sp) >= so[-1] and len(ok_) >= oo[-1] and len(ck) >= co[-1] and (po is None or pk is None or len(pk) >= po[-1])      # (the library checks the rest)
+    links = po is not None if links is None else links
+    cap_aff, cap_conn, cap_ord, cap_link = _uc_default_caps(ntgt, int(nkf), len(ck), links) if caps is None else caps
+    o = {} if out is None else out
+    sizes = dict(tgt_status=ntgt, tgt_parent=ntgt, aff_kf=cap_aff, conn_off=cap_aff + 1, conn_kf=cap_conn, conn_w=cap_conn, ord_off=cap_aff + 1, ord_kf=cap_ord,
+                 ord_w=cap_ord, counts=4)
+    if links:
+        sizes.update(link_off=ntgt + 1, link_kf=cap_link)
+    for k, n in sizes.items():
+        o.setdefault(k, np.zeros(n, np.int32))
+        assert o[k].dtype == np.int32 and o[k].flags.c_contiguous and o[k].size == n, k
+    rc = L.orbl_update_connections(ntgt, _addr(tk), _addr(tf), _addr(so), _addr(sp), int(nkf), npts, _addr(oo), _addr(ok_), _addr(pb), _addr(kr), _addr(co), _addr(ck),
+                                   _addr(cw), _addr(po), _addr(pk), int(th), cap_aff, cap_conn, cap_ord, cap_link, _addr(o["tgt_status"]), _addr(o["tgt_parent"]),
+                                   _addr(o["aff_kf"]), _addr(o["conn_off"]), _addr(o["conn_kf"]), _addr(o["conn_w"]), _addr(o["ord_off"]), _addr(o["ord_kf"]),
+                                   _addr(o["ord_w"]), _addr(o.get("link_off")), _addr(o.get("link_kf")), _addr(o["counts"]))
+    if rc == ECAP and not check:
+        return dict(rc=rc, counts=o["counts"])
+    _lib.check(rc, "orbl_update_connections")
+    n_aff, n_conn, n_ord, n_link = (int(v) for v in o["counts"])
+    r = dict(rc=0, counts=o["counts"], tgt_status=o["tgt_status"], tgt_parent=o["tgt_parent"], aff_kf=o["aff_kf"][:n_aff], conn_off=o["conn_off"][:n_aff + 1],
+             conn_kf=o["conn_kf"][:n_conn], conn_w=o["conn_w"][:n_conn], ord_off=o["ord_off"][:n_aff + 1], ord_kf=o["ord_kf"][:n_ord], ord_w=o["ord_w"][:n_ord],
+             link_off=None, link_kf=None)
+    if links:
+        r.update(link_off=o["link_off"], link_kf=o["link_kf"][:n_link])
+    return r
+
+
+def update_connections_device(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, conn_off, conn_kf, conn_w, tgt_flags=None, pt_bad=None, kf_rank=None,
+                              prev_off=None, prev_kf=None, th=15, links=None, caps=None, out=None, workspace=None):
+    """orbl_update_connections_device on torch CUDA tensors (int32 / uint8 as in update_connections; None where a pointer may be NULL),
+    enqueued on the current stream, nothing synchronised.  out: optional dict of preset device tensors of the capacities; workspace:
+    optional uint8 tensor to reuse (it is cleared by every call).  Returns a dict of device tensors of FULL capacity - counts[4] holds
+    the wanted sizes, status (uint32 as int32[1]) the UC_* bits - and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    dev = tgt_kf.device
+    ntgt, nslots, npts, nobs, nconn = tgt_kf.numel(), slot_pt.numel(), obs_off.numel() - 1, obs_kf.numel(), conn_kf.numel()
+    nprev = prev_kf.numel() if prev_kf is not None else 0
+    links = prev_off is not None if links is None else links
+    cap_aff, cap_conn, cap_ord, cap_link = _uc_default_caps(ntgt, int(nkf), nconn, links) if caps is None else caps
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_update_connections_workspace(ntgt, int(nkf), npts, nslots, nconn, C.byref(nbytes)), "orbl_update_connections_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else out
+    sizes = dict(tgt_status=ntgt, tgt_parent=ntgt, aff_kf=cap_aff, conn_off=cap_aff + 1, conn_kf=cap_conn, conn_w=cap_conn, ord_off=cap_aff + 1, ord_kf=cap_ord,
+                 ord_w=cap_ord, counts=4, status=1)
+    if links:
+        sizes.update(link_off=ntgt + 1, link_kf=cap_link)
+    for k, n in sizes.items():
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        assert o[k].dtype == torch.int32 and o[k].is_contiguous() and o[k].numel() == n, k
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_update_connections_device(ntgt, p(tgt_kf), p(tgt_flags), nslots, p(slot_off), p(slot_pt), int(nkf), npts, nobs, p(obs_off), p(obs_kf), p(pt_bad),
+                                                p(kf_rank), nconn, p(conn_off), p(conn_kf), p(conn_w), nprev, p(prev_off), p(prev_kf), int(th), cap_aff, cap_conn,
+                                                cap_ord, cap_link, p(o["tgt_status"]), p(o["tgt_parent"]), p(o["aff_kf"]), p(o["conn_off"]), p(o["conn_kf"]),
+                                                p(o["conn_w"]), p(o["ord_off"]), p(o["ord_kf"]), p(o["ord_w"]), p(o.get("link_off")), p(o.get("link_kf")),
+                                                p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "orbl_update_connections_device")
+    r = dict(o)
+    r.setdefault("link_off", None); r.setdefault("link_kf", None)
+    r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
+    return r

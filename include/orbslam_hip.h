@@ -559,6 +559,62 @@ int orbl_keyframe_culling_device(int ncand, const int32_t* d_cand_kf, const uint
  * three per point - each rounded up to 256 bytes; ncand does not enter. */
 int orbl_keyframe_culling_workspace(int ncand, int nslots, int npts, int nobs, size_t* bytes);
 
+/* ---- KeyFrame::UpdateConnections (src/KeyFrame.cc:314-398) with AddConnection / UpdateBestCovisibles (:158-193) for a WHOLE list of
+ * keyframes in ONE call, with the exact sequential semantics of calling it on each in turn, and the new loop links that
+ * LoopClosing::CorrectLoop derives while it walks such a list (src/LoopClosing.cc:551-573).  Keyframes are 0..nkf-1, points 0..npts-1.
+ *   targets, in call order: tgt_kf[t] in [0, nkf), distinct; tgt_flags[t] (nullable = all 0): bit 0 = is_first_connection_ && id_ != 0.
+ *   slots: slot_off[ntgt + 1] (CSR, slot_off[0] = 0) into slot_pt[s] = the target's map_points_ in slot order: a point index or -1 for a
+ *     null slot; a point may be listed twice and then counts twice.
+ *   points: pt_bad[p] (nullable = all 0) = isBad(); obs_off[npts + 1] (CSR) into obs_kf[e] = the observing keyframes, in any order.
+ *   kf_rank[nkf] (nullable = index order): a permutation, the keyframe's position in the caller's pointer order (std::less<KeyFrame*>).
+ *     It is the iteration order of keyframe_counter, breaks the ties of both sort(pairs) calls and orders std::set<KeyFrame*>.
+ *   tables of EVERY keyframe at entry: conn_off[nkf + 1] (CSR) into conn_kf[e] / conn_w[e] = connected_keyframe_weights_, in any order
+ *     inside a row; a row names a keyframe at most once and never itself.
+ *   prev_off[ntgt + 1] / prev_kf[] (nullable as a pair): ordered_connected_keyframes_ of every target at entry; read for the links only.
+ *   th: 15 in the reference (:353), >= 1.
+ * For each target A in order: 1. every slot of A with a point that is not bad adds one to counter[k] for every observer k != A.
+ *   2. empty counter: tgt_status = 1, tgt_parent = -1, nothing of A changes.  3. in ascending kf_rank: the maximum moves on a strictly
+ *   greater count (the lowest rank among the maxima wins); every k with counter[k] >= th joins `pairs` and AddConnection(k <- A,
+ *   counter[k]) runs; empty `pairs` become {kmax} with AddConnection(kmax <- A, nmax).  4. A's map = the WHOLE counter, A's list = `pairs`
+ *   by descending (weight, kf_rank); tgt_parent = the front of that list when bit 0 is set, else -1; tgt_status = 0.
+ *   AddConnection(B <- A, w): nothing when B's map holds A with weight w; else map[A] = w and B's list = ALL of B's map by descending
+ *   (weight, kf_rank) - the reference's re-sort, which brings entries below th into the list.
+ *   Links: with P(A) = A's list as it stands when A's turn begins, link(A) = keys of A's map after its turn \ P(A) \ {every target}.
+ * Outputs: tgt_status[ntgt], tgt_parent[ntgt]; counts[4] = {n_aff, n_conn, n_ord, n_link}; the keyframes the loop wrote (own update with a
+ * non-empty counter, or an AddConnection that changed something) in ascending index as aff_kf[n_aff]; their new maps as oconn_off[n_aff +
+ * 1] / oconn_kf / oconn_w, rows in ascending kf_rank (the map's iteration order); their new lists as oord_off[n_aff + 1] / oord_kf /
+ * oord_w; link_off[ntgt + 1] / link_kf (nullable; needs prev_*), rows in ascending kf_rank.  oconn_off / oord_off hold cap_aff + 1 entries,
+ * the lists cap_aff / cap_conn / cap_ord / cap_link.  Every element inside the counts is written, nothing beyond them.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for negative counts or
+ * capacities, offsets that do not ascend from 0, ids out of range, duplicate targets, a kf_rank that is not a permutation, a conn row
+ * naming a keyframe twice or itself, th < 1, NULL where an array is needed, one of the prev pair without the other, a link output
+ * without prev; ORBHIP_ENODEV without a GPU; ORBHIP_ECAP, with only counts[] (the wanted sizes) written, when a list does not fit.  */
+int orbl_update_connections(int ntgt, const int32_t* tgt_kf, const uint8_t* tgt_flags, const int32_t* slot_off, const int32_t* slot_pt, int nkf, int npts,
+                            const int32_t* obs_off, const int32_t* obs_kf, const uint8_t* pt_bad, const int32_t* kf_rank, const int32_t* conn_off,
+                            const int32_t* conn_kf, const int32_t* conn_w, const int32_t* prev_off, const int32_t* prev_kf, int th, int cap_aff, int cap_conn,
+                            int cap_ord, int cap_link, int32_t* tgt_status, int32_t* tgt_parent, int32_t* aff_kf, int32_t* oconn_off, int32_t* oconn_kf,
+                            int32_t* oconn_w, int32_t* oord_off, int32_t* oord_kf, int32_t* oord_w, int32_t* link_off, int32_t* link_kf, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nslots = slot_off[ntgt], nobs = obs_off[npts], nconn =
+ * conn_off[nkf], nprev = prev_off[ntgt] given by the caller).  d_counts[4] always holds the WANTED counts.  *d_status (nullable; zeroed
+ * first): 1 = offsets, 2 = an index out of range, a kf_rank that is not a permutation or a duplicate target, 4 / 8 / 16 / 32 = cap_aff /
+ * cap_conn / cap_ord / cap_link exceeded (the elements below the capacity are still written, none beyond it).  An out-of-range entry is
+ * treated as ABSENT (of a keyframe listed twice the last instance counts).  PRECONDITION, not checked here: no conn row names a keyframe
+ * twice.  Counts, NULL pointers and 4-byte alignment are checked on the host.  `d_workspace`: at least
+ * orbl_update_connections_workspace(...) bytes of device memory, 8-byte aligned, not shared with concurrent calls; it is cleared by every
+ * call, so calls may reuse it.                                                                                                        */
+int orbl_update_connections_device(int ntgt, const int32_t* d_tgt_kf, const uint8_t* d_tgt_flags, int nslots, const int32_t* d_slot_off,
+                                   const int32_t* d_slot_pt, int nkf, int npts, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                   const uint8_t* d_pt_bad, const int32_t* d_kf_rank, int nconn, const int32_t* d_conn_off, const int32_t* d_conn_kf,
+                                   const int32_t* d_conn_w, int nprev, const int32_t* d_prev_off, const int32_t* d_prev_kf, int th, int cap_aff, int cap_conn,
+                                   int cap_ord, int cap_link, int32_t* d_tgt_status, int32_t* d_tgt_parent, int32_t* d_aff_kf, int32_t* d_oconn_off,
+                                   int32_t* d_oconn_kf, int32_t* d_oconn_w, int32_t* d_oord_off, int32_t* d_oord_kf, int32_t* d_oord_w, int32_t* d_link_off,
+                                   int32_t* d_link_kf, int32_t* d_counts, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_update_connections_device needs (host arithmetic).  With cells = ntgt * nkf: the votes and the position of
+ * every target in every input row (4 bytes per cell each), the link marks (1) and candidates (4), the gathered entries of the final maps
+ * (12 bytes for each of nconn + 2 * cells), seven 32-bit words per keyframe and six per target, two per keyframe for the checks - each
+ * section rounded up to 256 bytes; npts and nslots do not enter. */
+int orbl_update_connections_workspace(int ntgt, int nkf, int npts, int nslots, int nconn, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
