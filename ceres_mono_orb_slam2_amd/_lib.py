@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("ORBHIP_LIB") or os.path.join(_HERE, "lib", "liborbsla
 SYMBOLS = [
     "orbhip_last_error", "orbhip_device_count", "orbhip_version", "orbhip_set_default_device", "orbhip_get_default_device", "orbhip_set_thread_priority", "orbhip_copy_pinned_async", "orbl_create_new_map_points", "orbl_fuse_batch", "orbl_update_map_points", "orbl_update_map_points_device", "orbl_update_map_points_workspace", "orbl_keyframe_culling", "orbl_keyframe_culling_device", "orbl_keyframe_culling_workspace",
     "orbl_update_connections", "orbl_update_connections_device", "orbl_update_connections_workspace",
+    "orbl_correct_loop", "orbl_correct_loop_device", "orbl_correct_loop_workspace",
+    "orbl_propagate_global_ba", "orbl_propagate_global_ba_device", "orbl_propagate_global_ba_workspace",
     "orbt_relocalization_search_by_bow",
     "orbt_initialize", "orbt_initialize_batch_device", "orbt_initialize_workspace",
     "orbt_pnp_ransac_params", "orbt_pnp_iterate", "orbt_pnp_iterate_batch_device", "orbt_pnp_iterate_workspace",
@@ -225,6 +227,12 @@ def load():
     L.orbl_update_connections.argtypes = [i32, vp, vp, vp, vp, i32, i32] + [vp] * 9 + [i32] * 5 + [vp] * 12
     L.orbl_update_connections_device.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp] + [i32] * 5 + [vp] * 15
     L.orbl_update_connections_workspace.argtypes = [i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.orbl_correct_loop.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, i32] + [vp] * 8 + [i32] + [vp] * 7
+    L.orbl_correct_loop_device.argtypes = [i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32] + [vp] * 5 + [i32] + [vp] * 10
+    L.orbl_correct_loop_workspace.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    L.orbl_propagate_global_ba.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 9
+    L.orbl_propagate_global_ba_device.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 12
+    L.orbl_propagate_global_ba_workspace.argtypes = [i32, i32, C.POINTER(sz)]
     L.orbt_initialize.argtypes = [vp, i32, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, C.POINTER(InitReport), C.POINTER(InitTrace)]
     L.orbt_initialize_batch_device.argtypes = [i32, vp, vp, i32, vp, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbt_initialize_workspace.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]

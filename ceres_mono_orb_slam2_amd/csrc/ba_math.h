@@ -30,6 +30,28 @@ BA_HD void quat_to_R(const double* q, double* R) {
   R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
 
+// Eigen::Quaterniond(R) for a row-major 3x3 m: the matrix -> quaternion conversion branches on the trace and, when it is not positive,
+// on the largest diagonal element (no normalisation, no sign convention on w).  q = [x, y, z, w].  Shared by the pose codec
+// (ba_matrix4d_to_pose7) and by the Sim3 of an SE3 pose (LoopClosing::CorrectLoop: Sophus::RxSO3d(1.0, R)).
+BA_HD void rot_to_quat(const double (&m)[3][3], double* q) {
+  double t = m[0][0] + m[1][1] + m[2][2];
+  if (t > 0.0) {
+    t = sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m[2][1] - m[1][2]) * t; q[1] = (m[0][2] - m[2][0]) * t; q[2] = (m[1][0] - m[0][1]) * t;
+  } else {
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m[k][j] - m[j][k]) * t; q[j] = (m[j][i] + m[i][j]) * t; q[k] = (m[k][i] + m[i][k]) * t;
+  }
+}
+
 // q+ = dq (x) q with dq = [sin|d|/|d| d, cos|d|]  (d = half-angle vector)
 BA_HD void quat_plus(const double* q, const double* d, double* out) {
   double n = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);

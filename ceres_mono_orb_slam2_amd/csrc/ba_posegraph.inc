@@ -257,13 +257,9 @@ __global__ __launch_bounds__(128) void k_pg_poses(const double* __restrict__ lie
   if (v >= n) return;
   double S[7];
   s3_exp(lie_opt + 7 * (size_t)v, S);
-  const double s = S[0] * S[0] + S[1] * S[1] + S[2] * S[2] + S[3] * S[3];
-  const double inv = 1.0 / sqrt(s);
-  const double q[4] = {S[0] * inv, S[1] * inv, S[2] * inv, S[3] * inv};
-  double R[9];
-  quat_to_R(q, R);
-  const double inv_s = 1. / s;
-  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) Tiw[12 * (size_t)v + 4 * i + j] = R[3 * i + j]; Tiw[12 * (size_t)v + 4 * i + 3] = inv_s * S[4 + i]; }
+  double T[12];
+  s3_to_pose34(S, T);
+  for (int i = 0; i < 12; i++) Tiw[12 * (size_t)v + i] = T[i];
 }
 __global__ __launch_bounds__(256) void k_pg_points(const double* __restrict__ lie_orig, const double* __restrict__ lie_opt,
                                                    const int* __restrict__ pt_ref, double* __restrict__ pts, int npts) {

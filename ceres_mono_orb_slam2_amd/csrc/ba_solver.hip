@@ -1738,22 +1738,7 @@ int ba_matrix4d_to_pose7(const double* T, double* pose7) {
   ORBHIP_REQUIRE(T && pose7, ORBHIP_EINVAL, "NULL argument");
   const double m[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
   double q[4];                                                  // x y z w
-  double t = m[0][0] + m[1][1] + m[2][2];
-  if (t > 0.0) {
-    t = std::sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (m[2][1] - m[1][2]) * t; q[1] = (m[0][2] - m[2][0]) * t; q[2] = (m[1][0] - m[0][1]) * t;
-  } else {
-    int i = 0;
-    if (m[1][1] > m[0][0]) i = 1;
-    if (m[2][2] > m[i][i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (m[k][j] - m[j][k]) * t; q[j] = (m[j][i] + m[i][j]) * t; q[k] = (m[k][i] + m[i][k]) * t;
-  }
+  rot_to_quat(m, q);
   pose7[0] = T[3]; pose7[1] = T[7]; pose7[2] = T[11];
   pose7[3] = q[0]; pose7[4] = q[1]; pose7[5] = q[2]; pose7[6] = q[3];
   return 0;

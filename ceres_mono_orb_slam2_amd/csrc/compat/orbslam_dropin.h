@@ -1710,6 +1710,204 @@ struct FrameOpsT {
     return counts[0];
   }
 
+  // LoopClosing::CorrectLoop, src/LoopClosing.cc:437-523, in ONE library call (orbl_correct_loop) followed by the UpdateConnections
+  // drop-in: `FrameOpsHip::CorrectLoopPoses(current_keyframe_, current_connected_keyframes_, sophus_sim3_Scw_, sophus_corrected_sim3,
+  // sophus_non_corrected_sim3);` under the mutex_map_update_ the caller holds, as the reference does.  Only the group's slots and the
+  // observers of their points are flattened; conn_rank = the group's order under std::less<KF*>, the iteration order of
+  // sophus_corrected_sim3.  Written back: both Sim3 maps, and on the moved points SetWorldPos, corrected_by_keyframe_,
+  // corrected_reference_, normal_vector_ / min_distance_ / max_distance_ (under mutex_pose_ when the type has it: the friend declaration
+  // of INTEGRATION.md section 4), then SetPose on the group, then UpdateConnections() of the group in map order (:522 - it reads nothing
+  // the correction writes).  The scale-factor table is the current keyframe's (every keyframe copies the one extractor's).  Sim3T is
+  // Sophus::Sim3d or anything whose data() is its storage.  Returns the number of points moved.
+  // (A member template over the keyframe type: data models without these members stay instantiable.)
+  template <class KF, class Sim3T>
+  static int CorrectLoopPoses(KF* current_keyframe, const std::vector<KF*>& current_connected_keyframes, const Sim3T& Scw, std::map<KF*, Sim3T>& corrected_sim3,
+                              std::map<KF*, Sim3T>& non_corrected_sim3, int th = 15) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(current_keyframe->GetMapPointMatches()[0])>::type>::type MP;
+    typedef typename std::decay<decltype(current_keyframe->GetPose())>::type M4;
+    const int nconn = (int)current_connected_keyframes.size();
+    if (nconn == 0 || current_connected_keyframes.back() != current_keyframe)
+      throw std::runtime_error("FrameOpsT::CorrectLoopPoses: the current keyframe must be the last entry of current_connected_keyframes");
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::vector<int32_t> conn_kf(nconn), conn_rank(nconn), by_pointer(nconn);
+    for (int c = 0; c < nconn; c++) {
+      if (kf_at.count(current_connected_keyframes[c])) throw std::runtime_error("FrameOpsT::CorrectLoopPoses: a keyframe is listed twice");
+      conn_kf[c] = kf_index(current_connected_keyframes[c]);          // (the group is numbered first: index = list position)
+      by_pointer[c] = c;
+    }
+    std::sort(by_pointer.begin(), by_pointer.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nconn; r++) conn_rank[by_pointer[r]] = r;
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*> pts;
+    std::vector<int32_t> slot_off(1, 0), slot_pt, obs_off(1, 0), obs_kf, ref_kf, ref_level;
+    std::vector<uint8_t> pt_bad, pt_done;
+    std::vector<double> X;
+    for (int c = 0; c < nconn; c++) {
+      const std::vector<MP*> matches = current_connected_keyframes[c]->GetMapPointMatches();      // (:482)
+      for (MP* mp : matches) {
+        if (!mp) { slot_pt.push_back(-1); continue; }
+        auto it = pt_at.find(mp);
+        if (it == pt_at.end()) {
+          it = pt_at.emplace(mp, (int)pts.size()).first;
+          pts.push_back(mp);
+          const bool bad = mp->isBad();
+          pt_bad.push_back(bad ? 1 : 0);
+          pt_done.push_back(mp->corrected_by_keyframe_ == current_keyframe->id_ ? 1 : 0);         // (:491)
+          const Vector3d P = mp->GetWorldPos();
+          for (int k = 0; k < 3; k++) X.push_back(P[k]);
+          int ref = 0, level = 0;
+          if (!bad) {                                                 // (what UpdateNormalAndDepth snapshots, src/MapPoint.cc:339-371)
+            const auto observations = mp->GetObservations();
+            KF* rk = mp->GetReferenceKeyFrame();
+            size_t kp = 0;
+            for (const auto& o : observations) { obs_kf.push_back(kf_index(o.first)); if (o.first == rk) kp = o.second; }
+            if (!observations.empty()) {
+              if (!rk) throw std::runtime_error("FrameOpsT::CorrectLoopPoses: a map point with observations has no reference keyframe");
+              ref = kf_index(rk); level = rk->undistort_keypoints_[kp].octave;
+            }
+          }
+          obs_off.push_back((int32_t)obs_kf.size()); ref_kf.push_back(ref); ref_level.push_back(level);
+        }
+        slot_pt.push_back(it->second);
+      }
+      slot_off.push_back((int32_t)slot_pt.size());
+    }
+    const int nkf = (int)kfs.size(), npts = (int)pts.size();
+    std::vector<double> Tcw(12 * (size_t)nkf), center(3 * (size_t)nkf);
+    for (int k = 0; k < nkf; k++) {
+      const M4 T = kfs[k]->GetPose();
+      const Vector3d O = kfs[k]->GetCameraCenter();
+      for (int r = 0; r < 3; r++) { for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c); center[3 * (size_t)k + r] = O[r]; }
+    }
+    const std::vector<float> table(current_keyframe->scale_factors_.begin(), current_keyframe->scale_factors_.begin() + current_keyframe->n_scale_levels_);
+    std::vector<double> corrected(7 * (size_t)nconn), non_corrected(7 * (size_t)nconn), normal(3 * (size_t)std::max(npts, 1));
+    std::vector<float> mm(2 * (size_t)std::max(npts, 1));
+    std::vector<int32_t> owner(std::max(npts, 1), -1);
+    std::vector<uint8_t> wrote(std::max(npts, 1), 0);
+    if (obs_kf.empty()) obs_kf.push_back(0);
+    if (slot_pt.empty()) slot_pt.push_back(-1);
+    X.resize(std::max<size_t>(X.size(), 3)); pt_bad.resize(std::max(npts, 1)); pt_done.resize(std::max(npts, 1)); ref_kf.resize(std::max(npts, 1)); ref_level.resize(std::max(npts, 1));
+    int32_t counts[2] = {0, 0};
+    dropin::check(orbl_correct_loop(nkf, Tcw.data(), center.data(), nconn, conn_kf.data(), conn_rank.data(), Scw.data(), slot_off.data(), slot_pt.data(), npts, X.data(),
+                                    pt_bad.data(), pt_done.data(), obs_off.data(), obs_kf.data(), ref_kf.data(), ref_level.data(), table.data(), (int)table.size(),
+                                    corrected.data(), non_corrected.data(), owner.data(), normal.data(), mm.data(), wrote.data(), counts),
+                  "orbl_correct_loop");
+    for (int c = 0; c < nconn; c++) {                                 // (:438, :461, :468)
+      Sim3T Sc = Scw, Sn = Scw;
+      for (int k = 0; k < 7; k++) { Sc.data()[k] = corrected[7 * (size_t)c + k]; Sn.data()[k] = non_corrected[7 * (size_t)c + k]; }
+      corrected_sim3[current_connected_keyframes[c]] = Sc; non_corrected_sim3[current_connected_keyframes[c]] = Sn;
+    }
+    for (int p = 0; p < npts; p++) {                                  // (:500-503)
+      if (owner[p] < 0) continue;
+      MP* mp = pts[p];
+      Vector3d P, v;
+      for (int k = 0; k < 3; k++) { P[k] = X[3 * (size_t)p + k]; v[k] = normal[3 * (size_t)p + k]; }
+      mp->SetWorldPos(P);
+      mp->corrected_by_keyframe_ = current_keyframe->id_;
+      mp->corrected_reference_ = kfs[owner[p]]->id_;
+      if (wrote[p]) {
+        std::unique_lock<std::mutex> lock = lock_pose(mp, 0);
+        mp->max_distance_ = mm[2 * (size_t)p + 1]; mp->min_distance_ = mm[2 * (size_t)p]; mp->normal_vector_ = v;
+      }
+    }
+    std::vector<KF*> in_map_order(nconn);
+    for (int r = 0; r < nconn; r++) {                                 // (:519, :522)
+      const int k = conn_kf[by_pointer[r]];
+      M4 T = kfs[k]->GetPose();
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = Tcw[12 * (size_t)k + 4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      kfs[k]->SetPose(T);
+      in_map_order[r] = kfs[k];
+    }
+    UpdateConnections(in_map_order, (std::map<KF*, std::set<KF*> >*)nullptr, th);
+    return counts[0];
+  }
+
+  // The write-back of LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:681-739, in ONE library call (orbl_propagate_global_ba):
+  // `FrameOpsHip::PropagateGlobalBA(map_, nLoopKF);` under mutex_map_update_, before map_->InformNewBigChange().  The tree is read
+  // through GetChilds() from keyframe_origins_ and from every keyframe of the map (kf_parent[c] = p iff c is in p->GetChilds()).
+  // Written back: global_BA_Tcw_ and n_BA_global_for_keyframe_ of the keyframes the walk carried the correction to, global_BA_Bef_Tcw_
+  // and SetPose of every keyframe it reached, SetWorldPos of every point it moved.  The one departure include/orbslam_hip.h states: the
+  // points of a flagged keyframe the walk does not reach stay put.  Returns the number of points moved.
+  template <class MapT> static int PropagateGlobalBA(MapT* map, unsigned long nLoopKF) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(map->GetAllKeyFrames()[0])>::type>::type KF;
+    typedef typename std::remove_pointer<typename std::decay<decltype(map->GetAllMapPoints()[0])>::type>::type MP;
+    typedef typename std::decay<decltype(map->GetAllKeyFrames()[0]->GetPose())>::type M4;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::vector<int32_t> origin_kf;
+    for (KF* kf : map->keyframe_origins_) origin_kf.push_back(kf_index(kf));
+    for (KF* kf : map->GetAllKeyFrames()) kf_index(kf);
+    const std::vector<MP*> points = map->GetAllMapPoints();
+    const int npts = (int)points.size();
+    std::vector<int32_t> pt_ref(std::max(npts, 1), 0);
+    std::vector<uint8_t> pt_bad(std::max(npts, 1), 0), pt_in(std::max(npts, 1), 0), moved(std::max(npts, 1), 0);
+    std::vector<double> X(3 * (size_t)std::max(npts, 1), 0.0), GX(3 * (size_t)std::max(npts, 1), 0.0);
+    for (int p = 0; p < npts; p++) {
+      MP* mp = points[p];
+      pt_bad[p] = mp->isBad() ? 1 : 0;
+      if (pt_bad[p]) continue;
+      pt_in[p] = mp->n_BA_global_for_keyframe_ == nLoopKF ? 1 : 0;
+      const Vector3d P = mp->GetWorldPos();
+      for (int k = 0; k < 3; k++) { X[3 * (size_t)p + k] = P[k]; GX[3 * (size_t)p + k] = mp->global_BA_pose_[k]; }
+      if (pt_in[p]) continue;
+      KF* rk = mp->GetReferenceKeyFrame();
+      if (!rk) throw std::runtime_error("FrameOpsT::PropagateGlobalBA: a map point without a reference keyframe");
+      pt_ref[p] = kf_index(rk);
+    }
+    std::vector<int32_t> parent;
+    for (size_t k = 0; k < kfs.size(); k++) {                          // (kfs grows while children that the map does not list turn up)
+      const auto childs = kfs[k]->GetChilds();
+      for (KF* c : childs) { const int ci = kf_index(c); if ((size_t)ci >= parent.size()) parent.resize(ci + 1, -1); parent[ci] = (int32_t)k; }
+    }
+    const int nkf = (int)kfs.size();
+    parent.resize(nkf, -1);
+    std::vector<double> Tcw(12 * (size_t)nkf), gba(12 * (size_t)nkf), bef(12 * (size_t)nkf);
+    std::vector<uint8_t> in_gba(nkf), reached(nkf, 0), in_before;
+    for (int k = 0; k < nkf; k++) {
+      const M4 T = kfs[k]->GetPose();
+      for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) { Tcw[12 * (size_t)k + 4 * r + c] = T(r, c); gba[12 * (size_t)k + 4 * r + c] = kfs[k]->global_BA_Tcw_(r, c); }
+      in_gba[k] = kfs[k]->n_BA_global_for_keyframe_ == nLoopKF ? 1 : 0;
+    }
+    in_before = in_gba;
+    int32_t counts[4] = {0, 0, 0, 0};
+    dropin::check(orbl_propagate_global_ba(nkf, Tcw.data(), gba.data(), in_gba.data(), parent.data(), (int)origin_kf.size(), origin_kf.data(), nullptr, npts, X.data(),
+                                           pt_bad.data(), pt_in.data(), GX.data(), pt_ref.data(), bef.data(), reached.data(), moved.data(), counts),
+                  "orbl_propagate_global_ba");
+    auto to_m4 = [](const M4& like, const double* t) {
+      M4 T = like;
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = t[4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      return T;
+    };
+    for (int k = 0; k < nkf; k++) {                                   // (:693-695, :700-701)
+      if (!reached[k]) continue;
+      KF* kf = kfs[k];
+      const M4 like = kf->GetPose();
+      if (!in_before[k]) { kf->global_BA_Tcw_ = to_m4(like, gba.data() + 12 * (size_t)k); kf->n_BA_global_for_keyframe_ = nLoopKF; }
+      kf->global_BA_Bef_Tcw_ = to_m4(like, bef.data() + 12 * (size_t)k);
+      kf->SetPose(to_m4(like, Tcw.data() + 12 * (size_t)k));
+    }
+    for (int p = 0; p < npts; p++) {                                  // (:715, :737)
+      if (!moved[p]) continue;
+      Vector3d P;
+      for (int k = 0; k < 3; k++) P[k] = X[3 * (size_t)p + k];
+      points[p]->SetWorldPos(P);
+    }
+    return counts[2];
+  }
+
  private:
   // the reference's KeyFrame::mutex_connections_ when the type has it
   template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {

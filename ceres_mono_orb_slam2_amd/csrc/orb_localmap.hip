@@ -23,6 +23,7 @@
 #include "common.h"
 #include "orb_frame.h"
 #include "tri_math.h"
+#include "sim3_math.h"
 
 namespace orbhip {
 
@@ -391,3 +392,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_kfculling.inc"
 // KeyFrame::UpdateConnections for a whole keyframe list, AddConnection re-sorts and loop links included (orbl_update_connections*)
 #include "orb_updateconn.inc"
+// LoopClosing::CorrectLoop's pose / point correction and the global-BA write-back (orbl_correct_loop*, orbl_propagate_global_ba*)
+#include "orb_mapcorrect.inc"

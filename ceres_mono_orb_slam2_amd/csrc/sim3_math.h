@@ -7,6 +7,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "ba_math.h"
+
 namespace orbhip {
 
 #define S3_HD __host__ __device__ __forceinline__
@@ -52,6 +54,18 @@ S3_HD void s3_mul(const double* A, const double* B, double* out) {
   const double w = A[3] * B[3] - A[0] * B[0] - A[1] * B[1] - A[2] * B[2];
   out[0] = x; out[1] = y; out[2] = z; out[3] = w;
   out[4] = A[4] + t[0]; out[5] = A[5] + t[1]; out[6] = A[6] + t[2];
+}
+
+// Sim3 -> SE3 as the loop-closing write-backs do it (src/CeresOptimizer.cc:916-929, src/LoopClosing.cc:508-516): T = [R | t / s], row-major
+// 3x4, R from the normalised quaternion, the translation times 1 / s
+S3_HD void s3_to_pose34(const double* S, double* T) {
+  const double s = S[0] * S[0] + S[1] * S[1] + S[2] * S[2] + S[3] * S[3];
+  const double inv = 1.0 / sqrt(s);
+  const double q[4] = {S[0] * inv, S[1] * inv, S[2] * inv, S[3] * inv};
+  double R[9];
+  quat_to_R(q, R);
+  const double inv_s = 1. / s;
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T[4 * i + j] = R[3 * i + j]; T[4 * i + 3] = inv_s * S[4 + i]; }
 }
 
 // exp: tangent -> qt7.  translation = W upsilon, W = A Om + B Om^2 + C I  (closed form of int_0^1 exp(t(sigma I + Om)) dt)

@@ -615,6 +615,90 @@ int orbl_update_connections_device(int ntgt, const int32_t* d_tgt_kf, const uint
  * section rounded up to 256 bytes; npts and nslots do not enter. */
 int orbl_update_connections_workspace(int ntgt, int nkf, int npts, int nslots, int nconn, size_t* bytes);
 
+/* ---- LoopClosing::CorrectLoop, the part that moves the map (src/LoopClosing.cc:437-523): the corrected and non-corrected Sim3 of the
+ * current keyframe's covisibility group, the correction of every map point those keyframes hold, UpdateNormalAndDepth of each moved
+ * point, SetPose([R | t/s]) of each keyframe - with the exact semantics of the sequential loop.  Keyframes are 0..nkf-1, points 0..npts-1.
+ *   kf_Tcw[nkf][12] (row-major 3x4, IN/OUT), kf_center[nkf][3] (nullable, IN/OUT): only the rows of the group are rewritten.
+ *   conn_kf[nconn] = current_connected_keyframes_: distinct, the LAST entry is the current keyframe, nconn >= 1.
+ *   conn_rank[nconn] (nullable = list order): a permutation, the keyframe's position under std::less<KeyFrame*> - the iteration order
+ *     of sophus_corrected_sim3.   Scw[7]: Sophus storage [qx,qy,qz,qw, tx,ty,tz], |q|^2 = scale.
+ *   slot_off[nconn + 1] / slot_pt[]: CSR of GetMapPointMatches() per connected keyframe: a point index or -1.
+ *   X[npts][3] (IN/OUT); pt_bad[npts] (nullable); pt_done[npts] (nullable) = corrected_by_keyframe_ == current_keyframe_->id_ at entry.
+ *   For the normals, as in orbl_update_map_points: obs_off[npts + 1] / obs_kf[] in the point's std::map order, ref_kf[npts],
+ *     ref_level[npts], scale_factors[n_levels] - all nullable AS A SET (with normal, min_max, nd_written): then no normals are computed.
+ *     With them kf_center is needed.
+ * With A o B the product of two such matrices as 4x4 ones (last row 0 0 0 1), every sum in index order k = 0..3, and Twc what
+ * KeyFrame::SetPose stores (Rwc = Rcw^T, Ow = -(Rwc tcw), each dot product (a0 b0 + a1 b1) + a2 b2):
+ *   non_corrected[c] = Sim3(Tcw of conn_kf[c]): the matrix -> quaternion branches of ba_matrix4d_to_pose7, un-normalised, scale 1.
+ *   corrected[last] = Scw; corrected[c] = ba_sim3_mul(Sim3(Tcw[c] o Twc[current]), Scw) otherwise.
+ *   owner of p = the connected keyframe of lowest conn_rank that lists p; only points that are neither bad nor done take part.
+ *   X[p] <- corrected[o]^-1 * (non_corrected[o] * X[p]) for the owner o;  pt_owner[p] = its keyframe index, or -1 (every element written):
+ *     the caller sets corrected_by_keyframe_ and corrected_reference_ from it.
+ *   new pose of conn_kf[c] = [R | t/s] of corrected[c] (the arithmetic of ba_essential_graph_correct); new centre = -(R^T t/s).
+ *   normal / min_max / nd_written of every MOVED point as orbl_update_map_points computes them from the new position, where the centre
+ *     of an observing (or the reference) keyframe k is its NEW centre when k is in the group and conn_rank(k) < conn_rank(owner), strictly -
+ *     SetPose (:519) follows a keyframe's own points - and its centre at entry otherwise.  Rows of points that did not move are untouched.
+ *   counts[2] = {n_moved, n_contested (moved points listed by two or more connected keyframes)}.
+ * corrected[nconn][7] / non_corrected[nconn][7] are the two KeyFrameAndSim3 maps OptimizeEssentialGraph and SearchAndFuse take.  The
+ * per-keyframe UpdateConnections() at :522 reads nothing this call writes: run orbl_update_connections on the list in conn_rank order
+ * afterwards.  Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, NULLs,
+ * offsets that do not ascend from 0, indices out of range, a duplicate in conn_kf, a conn_rank that is not a permutation, a level
+ * outside [0, n_levels) or n_levels outside [1, 64], an Scw that is not finite or has |q|^2 = 0; ORBHIP_ENODEV without a GPU.          */
+int orbl_correct_loop(int nkf, double* kf_Tcw, double* kf_center, int nconn, const int32_t* conn_kf, const int32_t* conn_rank, const double* Scw,
+                      const int32_t* slot_off, const int32_t* slot_pt, int npts, double* X, const uint8_t* pt_bad, const uint8_t* pt_done, const int32_t* obs_off,
+                      const int32_t* obs_kf, const int32_t* ref_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, double* corrected,
+                      double* non_corrected, int32_t* pt_owner, double* normal, float* min_max, uint8_t* nd_written, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nslots = slot_off[nconn], nobs = obs_off[npts] given by
+ * the caller).  Counts, NULL pointers and alignment (8 bytes for the 64-bit arrays and the workspace, 4 for the 32-bit ones) are checked
+ * on the host; the data is bounds-checked on the device: an entry out of range counts as ABSENT - a connected keyframe that is not
+ * there (zeros in its two Sim3 rows; of a keyframe listed twice the last instance counts; without a usable current keyframe nothing
+ * moves), a slot that is empty, a point whose normal is not written - and sets a bit in *d_status (nullable; zeroed first): 1 = offsets,
+ * 2 = a keyframe index (conn_kf and its duplicates, obs_kf, ref_kf), 4 = a point index, 8 = conn_rank is not a permutation, 16 = a level,
+ * 32 = Scw not finite or |q|^2 = 0 (the arithmetic still runs).  nd_written[p] is written for EVERY p here (0 where the point did not
+ * move).  `d_workspace`: at least orbl_correct_loop_workspace(...) bytes, not shared with concurrent calls, reusable by the next.     */
+int orbl_correct_loop_device(int nkf, double* d_kf_Tcw, double* d_kf_center, int nconn, const int32_t* d_conn_kf, const int32_t* d_conn_rank, const double* d_Scw,
+                             int nslots, const int32_t* d_slot_off, const int32_t* d_slot_pt, int npts, double* d_X, const uint8_t* d_pt_bad,
+                             const uint8_t* d_pt_done, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf, const int32_t* d_ref_kf,
+                             const int32_t* d_ref_level, const float* d_scale_factors, int n_levels, double* d_corrected, double* d_non_corrected,
+                             int32_t* d_pt_owner, double* d_normal, float* d_min_max, uint8_t* d_nd_written, int32_t* d_counts, uint32_t* d_status,
+                             void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_correct_loop_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nconn, npts,
+ * 4 * nkf, 8 * npts, 4 * nconn, 56 * nconn, 96 * nconn, 24 * nconn. */
+int orbl_correct_loop_workspace(int nkf, int nconn, int npts, size_t* bytes);
+
+/* ---- The write-back of the global bundle adjustment (LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:681-739): the walk of
+ * the spanning tree from keyframe_origins_ that carries global_BA_Tcw_ to the keyframes created while the BA ran, and the move of every
+ * map point to its BA position or through its reference keyframe's correction.
+ *   kf_Tcw[nkf][12], kf_gba_Tcw[nkf][12] (global_BA_Tcw_), kf_in_gba[nkf] (n_BA_global_for_keyframe_ == nLoopKF): IN/OUT.
+ *   kf_parent[nkf]: p iff the keyframe is in p->GetChilds(), else -1 (origins; bad keyframes, whose parent erased them).
+ *   origin_kf[n_origin] = keyframe_origins_ (an origin's own parent entry is not read).  kf_center[nkf][3] (nullable, IN/OUT).
+ *   X[npts][3] (IN/OUT), pt_bad (nullable), pt_in_gba / pt_gba_X[npts][3] (nullable as a pair), pt_ref_kf[npts].
+ * A keyframe is REACHED when its parent chain ends in an origin.  A reached keyframe that is not in the BA gets
+ * gba[c] = (Tcw[c] o Twc[parent]) o gba[parent] (the product and Twc of orbl_correct_loop; every right-hand operand at its value from
+ * before any SetPose of this call) and is marked as in the BA.  Every reached keyframe k: kf_bef_Tcw[k] = Tcw[k] (global_BA_Bef_Tcw_; rows
+ * of the others untouched), Tcw[k] = gba[k], the centre follows; kf_reached[nkf] is written for all.  A point that is not bad: in the BA:
+ * X = pt_gba_X (pt_moved = 1); else with a reached reference keyframe: Xc = Rbef X + tbef, X = Rwc Xc + twc with the inverse of the NEW
+ * pose (pt_moved = 2); else untouched (0).  counts[4] = {n_reached, n_propagated, n_points_moved, n_stale}.
+ * ONE departure from the reference: a keyframe flagged as in the BA that the walk does not reach - the reference would read a stale
+ * global_BA_Bef_Tcw_ for the points it is the reference of; here they stay put and are counted in n_stale.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, NULLs, an origin,
+ * parent (also k's own index) or reference keyframe out of range; a cycle among the parents leaves its keyframes unreached;
+ * ORBHIP_ENODEV without a GPU.                                                                                                      */
+int orbl_propagate_global_ba(int nkf, double* kf_Tcw, double* kf_gba_Tcw, uint8_t* kf_in_gba, const int32_t* kf_parent, int n_origin, const int32_t* origin_kf,
+                             double* kf_center, int npts, double* X, const uint8_t* pt_bad, const uint8_t* pt_in_gba, const double* pt_gba_X,
+                             const int32_t* pt_ref_kf, double* kf_bef_Tcw, uint8_t* kf_reached, uint8_t* pt_moved, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside.  Counts, NULL pointers and alignment are checked on
+ * the host, the data on the device: an index out of range counts as absent (an origin that is not there, a keyframe without a parent, a
+ * point that stays) and sets bit 1 of *d_status (nullable; zeroed first); 2 = a cycle in kf_parent (its keyframes are not reached);
+ * 4 = n_stale > 0.  The tree is walked by one workgroup, one level per round, for any depth and any nkf.
+ * `d_workspace`: at least orbl_propagate_global_ba_workspace(...) bytes, not shared with concurrent calls, reusable by the next.     */
+int orbl_propagate_global_ba_device(int nkf, double* d_kf_Tcw, double* d_kf_gba_Tcw, uint8_t* d_kf_in_gba, const int32_t* d_kf_parent, int n_origin,
+                                    const int32_t* d_origin_kf, double* d_kf_center, int npts, double* d_X, const uint8_t* d_pt_bad, const uint8_t* d_pt_in_gba,
+                                    const double* d_pt_gba_X, const int32_t* d_pt_ref_kf, double* d_kf_bef_Tcw, uint8_t* d_kf_reached, uint8_t* d_pt_moved,
+                                    int32_t* d_counts, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_propagate_global_ba_device needs (host arithmetic): nkf bytes rounded up to 256, at least 256. */
+int orbl_propagate_global_ba_workspace(int nkf, int npts, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
