@@ -11,6 +11,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "align.h"
+#include "orb_argcheck.h"
 
 namespace orbhip {
 
@@ -203,6 +204,73 @@ struct ThreadWs {
   }
 };
 ThreadWs& thread_ws();          // (capi_common.hip)
+
+// One host-pointer call's staging: a host entry point is its *_device entry plus this round trip.
+// The entry states every array ONCE, with its element type and its count, and gets a piece: dev() is what the device entry takes
+// (valid after commit()), host() the pinned copy of what came back (valid after finish()).
+//   in(host, count)        uploaded; dev() is nullptr when host is NULL or count is 0
+//   csr(off, rows)         CSR offsets: rows + 1 entries, or a single 0 when there are no rows (off is then not read)
+//   out<T>(count, wanted)  a slot of the result block; dev() is nullptr when it is not wanted
+//   inout(host, count)     a table the launches change in place: uploaded with the inputs, gathered into the result block by finish()
+//   scratch(bytes)         the device entry's *_workspace: scratch_dev()
+// commit() is ONE host-to-device copy and finish() one device-to-device copy per in/out table, ONE device-to-host copy and ONE stream
+// synchronise, the copies of host memory through ThreadWs::copy.  The blocks are ThreadWs slots (no hipMalloc / hipFree on a warm
+// call) and every piece of them starts on a 256-byte boundary (Carve).
+struct RoundTrip {
+  static constexpr size_t NONE = ~(size_t)0;
+  template <typename T> struct Piece {
+    const RoundTrip* rt; int up; size_t res;                   // its piece of the upload (-1: none), its offset in the result block (NONE: none)
+    T* dev() const { return up >= 0 ? rt->pack.template dev<T>(up) : res != NONE ? (T*)(rt->dres + res) : nullptr; }
+    const T* host() const { return (const T*)(rt->hres + res); }
+    const T& operator[](size_t i) const { return host()[i]; }
+  };
+  explicit RoundTrip(ThreadWs& w) : W(w) {}
+  RoundTrip(const RoundTrip&) = delete;                      // (the pieces point back to it)
+  template <typename T> Piece<const T> in(const T* host, size_t count) { return {this, host && count ? pack.add(host, count * sizeof(T)) : -1, NONE}; }
+  Piece<const int32_t> csr(const int32_t* off, size_t rows) { return !off ? in(off, 0) : rows ? in(off, rows + 1) : in(&zero, 1); }
+  template <typename T> Piece<T> out(size_t count, bool wanted = true) { return {this, -1, wanted ? res.take(count * sizeof(T)) : NONE}; }
+  template <typename T> Piece<T> inout(T* host, size_t count) {
+    Piece<T> p{this, host && count ? pack.add(host, count * sizeof(T)) : -1, NONE};
+    if (p.up >= 0) { p.res = res.take(count * sizeof(T)); gathers.push_back({p.up, p.res}); }
+    return p;
+  }
+  void scratch(size_t bytes) { scratch_bytes = bytes; }
+  void* scratch_dev() const { return dscratch; }
+  hipStream_t stream() const { return W.s; }
+  int commit() {
+    int rc = 0;
+    dres = W.d<uint8_t>(res.total, &rc); dscratch = W.d<uint8_t>(scratch_bytes, &rc);
+    return rc ? rc : W.commit(pack);
+  }
+  int finish() {
+    for (const Gather& g : gathers) {
+      const ThreadWs::Pack::Piece& q = pack.pieces[g.up];
+      ORBHIP_CHECK_HIP(hipMemcpyAsync(dres + g.res, pack.dbase + q.off, q.bytes, hipMemcpyDeviceToDevice, W.s));
+    }
+    if (res.total == 0) return W.sync();                     // (nothing to bring back: the launches are still waited for)
+    int rc = 0;
+    hres = W.down(dres, res.total, &rc);
+    return rc ? rc : W.sync();
+  }
+  // the whole array (or its first `count` entries) into the caller's buffer; nothing for a slot that was not wanted
+  template <typename T> void copy_out(const Piece<T>& p, T* dst, size_t count) const { if (count && p.res != NONE) std::memcpy(dst, p.host(), count * sizeof(T)); }
+
+  ThreadWs& W; ThreadWs::Pack pack; Carve res; size_t scratch_bytes = 0;
+  struct Gather { int up; size_t res; };
+  std::vector<Gather> gathers;
+  uint8_t* dres = nullptr; void* dscratch = nullptr; const uint8_t* hres = nullptr;
+  const int32_t zero = 0;
+};
+
+template <typename T> using HostIn = RoundTrip::Piece<const T>;      // what in() and csr() give
+template <typename T> using HostOut = RoundTrip::Piece<T>;           // what out() and inout() give
+
+// a check of orb_argcheck.h inside an entry point: the message of a failed one becomes the error and the call ends with ORBHIP_EINVAL
+#define ORBHIP_ARG(check)                                                                         \
+  do {                                                                                            \
+    const std::string _m = (check);                                                               \
+    if (!_m.empty()) { ::orbhip::set_error("%s", _m.c_str()); return ORBHIP_EINVAL; }             \
+  } while (0)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to (function, device) and is shared by every host thread and every context:
 // the largest value requested so far is kept per (function, device) under a lock and only ever RAISED - a per-thread or

@@ -302,56 +302,35 @@ int orbl_keyframe_culling(int ncand, const int32_t* cand_kf, const uint8_t* cand
   ORBHIP_REQUIRE(std::isfinite(ratio), ORBHIP_EINVAL, "orbl_keyframe_culling: ratio is not finite");
   ORBHIP_REQUIRE(ncand == 0 || (cand_kf && slot_off && culled && n_redundant && n_map_points), ORBHIP_EINVAL, "orbl_keyframe_culling: NULL candidate argument");
   ORBHIP_REQUIRE(npts == 0 || obs_off, ORBHIP_EINVAL, "orbl_keyframe_culling: NULL obs_off");
+  static const char E[] = "orbl_keyframe_culling";
   int nslots = 0, nobs = 0;
-  if (ncand > 0) {
-    ORBHIP_REQUIRE(slot_off[0] == 0, ORBHIP_EINVAL, "orbl_keyframe_culling: slot_off must start at 0");
-    for (int c = 0; c < ncand; c++) ORBHIP_REQUIRE(slot_off[c] <= slot_off[c + 1], ORBHIP_EINVAL, "orbl_keyframe_culling: slot_off decreases");
-    nslots = slot_off[ncand];
-  }
-  if (npts > 0) {
-    ORBHIP_REQUIRE(obs_off[0] == 0, ORBHIP_EINVAL, "orbl_keyframe_culling: obs_off must start at 0");
-    for (int p = 0; p < npts; p++) ORBHIP_REQUIRE(obs_off[p] <= obs_off[p + 1], ORBHIP_EINVAL, "orbl_keyframe_culling: obs_off decreases");
-    nobs = obs_off[npts];
-  }
+  ORBHIP_ARG(check_csr(E, "slot_off", slot_off, ncand, &nslots));
+  ORBHIP_ARG(check_csr(E, "obs_off", obs_off, npts, &nobs));
   ORBHIP_REQUIRE(nslots == 0 || (slot_pt && slot_level), ORBHIP_EINVAL, "orbl_keyframe_culling: NULL slot argument");
   ORBHIP_REQUIRE(nobs == 0 || (obs_kf && obs_level), ORBHIP_EINVAL, "orbl_keyframe_culling: NULL observation argument");
-  for (int c = 0; c < ncand; c++) ORBHIP_REQUIRE(cand_kf[c] >= 0 && cand_kf[c] < nkf, ORBHIP_EINVAL, "orbl_keyframe_culling: candidate keyframe index out of range");
-  for (int s = 0; s < nslots; s++) {
-    ORBHIP_REQUIRE(slot_pt[s] >= 0 && slot_pt[s] < npts, ORBHIP_EINVAL, "orbl_keyframe_culling: slot point index out of range");
-    ORBHIP_REQUIRE(slot_level[s] >= 0, ORBHIP_EINVAL, "orbl_keyframe_culling: negative slot level");
-  }
-  for (int e = 0; e < nobs; e++) {
-    ORBHIP_REQUIRE(obs_kf[e] >= 0 && obs_kf[e] < nkf, ORBHIP_EINVAL, "orbl_keyframe_culling: observation keyframe index out of range");
-    ORBHIP_REQUIRE(obs_level[e] >= 0, ORBHIP_EINVAL, "orbl_keyframe_culling: negative observation level");
-  }
+  ORBHIP_ARG(check_index(E, "cand_kf", cand_kf, ncand, nkf));
+  ORBHIP_ARG(check_index(E, "slot_pt", slot_pt, nslots, npts));
+  ORBHIP_ARG(check_not_negative(E, "slot_level", slot_level, nslots));
+  ORBHIP_ARG(check_index(E, "obs_kf", obs_kf, nobs, nkf));
+  ORBHIP_ARG(check_not_negative(E, "obs_level", obs_level, nobs));
   ThreadWs& W = thread_ws();
   int rc = W.begin();
   if (rc) return rc;
-  ThreadWs::Pack in;
-  const int pK = ncand ? in.add(cand_kf, 4 * (size_t)ncand) : -1, pF = ncand && cand_flags ? in.add(cand_flags, (size_t)ncand) : -1;
-  const int pSO = ncand ? in.add(slot_off, 4 * ((size_t)ncand + 1)) : -1, pSP = nslots ? in.add(slot_pt, 4 * (size_t)nslots) : -1;
-  const int pSL = nslots ? in.add(slot_level, 4 * (size_t)nslots) : -1, pOO = npts ? in.add(obs_off, 4 * ((size_t)npts + 1)) : -1;
-  const int pOK = nobs ? in.add(obs_kf, 4 * (size_t)nobs) : -1, pOL = nobs ? in.add(obs_level, 4 * (size_t)nobs) : -1;
-  const int pB = npts && pt_bad ? in.add(pt_bad, (size_t)npts) : -1, pN = npts && pt_nobs ? in.add(pt_nobs, 4 * (size_t)npts) : -1;
-  // outputs in one block: [culled | n_redundant | n_map_points | pt_bad_out | pt_nobs_out | obs_erased]
-  Carve out;
-  const size_t oC = out.take((size_t)ncand), oR = out.take(4 * (size_t)ncand), oM = out.take(4 * (size_t)ncand), oB = out.take((size_t)npts), oN = out.take(4 * (size_t)npts),
-               oE = out.take((size_t)nobs);
-  const size_t o = out.total;
-  uint8_t* dblk = W.d<uint8_t>(std::max<size_t>(o, 256), &rc);
-  void* dws = W.d<uint8_t>(cull_workspace(nslots, npts, nobs).total, &rc);
-  if (rc || (rc = W.commit(in))) return rc;
-  if ((rc = orbl_keyframe_culling_device(ncand, in.dev<int32_t>(pK), in.dev<uint8_t>(pF), nslots, in.dev<int32_t>(pSO), in.dev<int32_t>(pSP), in.dev<int32_t>(pSL), nkf,
-                                         npts, nobs, in.dev<int32_t>(pOO), in.dev<int32_t>(pOK), in.dev<int32_t>(pOL), in.dev<uint8_t>(pB), in.dev<int32_t>(pN), th_obs,
-                                         ratio, dblk + oC, (int32_t*)(dblk + oR), (int32_t*)(dblk + oM), pt_bad_out ? dblk + oB : nullptr,
-                                         pt_nobs_out ? (int32_t*)(dblk + oN) : nullptr, obs_erased ? dblk + oE : nullptr, nullptr, dws, W.s))) return rc;
-  if (o == 0) return W.sync();
-  const uint8_t* hb = W.down(dblk, o, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  if (ncand) { std::memcpy(culled, hb + oC, (size_t)ncand); std::memcpy(n_redundant, hb + oR, 4 * (size_t)ncand); std::memcpy(n_map_points, hb + oM, 4 * (size_t)ncand); }
-  if (pt_bad_out && npts) std::memcpy(pt_bad_out, hb + oB, (size_t)npts);
-  if (pt_nobs_out && npts) std::memcpy(pt_nobs_out, hb + oN, 4 * (size_t)npts);
-  if (obs_erased && nobs) std::memcpy(obs_erased, hb + oE, (size_t)nobs);
+  const size_t nc = (size_t)ncand, ns = (size_t)nslots, np = (size_t)npts, no = (size_t)nobs;
+  RoundTrip R(W);
+  const HostIn<int32_t> d_cand = R.in(cand_kf, nc), d_slot_off = R.csr(slot_off, nc), d_slot_pt = R.in(slot_pt, ns), d_slot_level = R.in(slot_level, ns);
+  const HostIn<int32_t> d_obs_off = R.csr(obs_off, np), d_obs_kf = R.in(obs_kf, no), d_obs_level = R.in(obs_level, no), d_nobs = R.in(pt_nobs, np);
+  const HostIn<uint8_t> d_flags = R.in(cand_flags, nc), d_bad = R.in(pt_bad, np);
+  const HostOut<uint8_t> o_culled = R.out<uint8_t>(nc), o_bad = R.out<uint8_t>(np, pt_bad_out != nullptr), o_erased = R.out<uint8_t>(no, obs_erased != nullptr);
+  const HostOut<int32_t> o_red = R.out<int32_t>(nc), o_mp = R.out<int32_t>(nc), o_nobs = R.out<int32_t>(np, pt_nobs_out != nullptr);
+  R.scratch(cull_workspace(nslots, npts, nobs).total);
+  if ((rc = R.commit())) return rc;
+  if ((rc = orbl_keyframe_culling_device(ncand, d_cand.dev(), d_flags.dev(), nslots, d_slot_off.dev(), d_slot_pt.dev(), d_slot_level.dev(), nkf, npts, nobs,
+                                         d_obs_off.dev(), d_obs_kf.dev(), d_obs_level.dev(), d_bad.dev(), d_nobs.dev(), th_obs, ratio, o_culled.dev(), o_red.dev(),
+                                         o_mp.dev(), o_bad.dev(), o_nobs.dev(), o_erased.dev(), nullptr, R.scratch_dev(), R.stream()))) return rc;
+  if ((rc = R.finish())) return rc;
+  R.copy_out(o_culled, culled, nc); R.copy_out(o_red, n_redundant, nc); R.copy_out(o_mp, n_map_points, nc);
+  R.copy_out(o_bad, pt_bad_out, np); R.copy_out(o_nobs, pt_nobs_out, np); R.copy_out(o_erased, obs_erased, no);
   return 0;
 }
 

@@ -394,18 +394,18 @@ static int ulm_enqueue(const UlmArgs& A, int stages, hipStream_t st) {
   return 0;
 }
 
-// host checks of one CSR: offsets ascend from 0, every entry in [lo_id, n_ids), rows of at most max_row entries (0 = any)
-static int ulm_check_csr(const int32_t* off, const int32_t* val, int rows, int lo_id, int n_ids, int max_row, int* total) {
+// host checks of one CSR of entry point E: the offsets (argcheck), every entry in [0, n_ids) or -1 where none_ok, rows of at most max_row
+// entries (0 = any)
+static int ulm_check_csr(const char* E, const char* off_name, const char* val_name, const int32_t* off, const int32_t* val, int rows, bool none_ok, int n_ids,
+                         int max_row, int* total) {
   *total = 0;
   if (rows == 0) return 0;
-  ORBHIP_REQUIRE(off && off[0] == 0, ORBHIP_EINVAL, "orbt_update_local_map: a CSR offset array is NULL or does not start at 0");
-  for (int r = 0; r < rows; r++) {
-    ORBHIP_REQUIRE(off[r] <= off[r + 1], ORBHIP_EINVAL, "orbt_update_local_map: CSR offsets decrease");
-    ORBHIP_REQUIRE(max_row == 0 || off[r + 1] - off[r] <= max_row, ORBHIP_EINVAL, "orbt_update_local_map: more than 10 best covisibles in a row");
-  }
-  *total = off[rows];
-  ORBHIP_REQUIRE(*total == 0 || val, ORBHIP_EINVAL, "orbt_update_local_map: NULL CSR entries");
-  for (int e = 0; e < *total; e++) ORBHIP_REQUIRE(val[e] >= lo_id && val[e] < n_ids, ORBHIP_EINVAL, "orbt_update_local_map: CSR entry out of range");
+  if (!off) { set_error("%s: %s is NULL", E, off_name); return ORBHIP_EINVAL; }
+  ORBHIP_ARG(check_csr(E, off_name, off, rows, total));
+  for (int r = 0; max_row && r < rows; r++)
+    if (off[r + 1] - off[r] > max_row) { set_error("%s: more than %d entries in row %d of %s", E, max_row, r, off_name); return ORBHIP_EINVAL; }
+  if (*total && !val) { set_error("%s: %s is NULL", E, val_name); return ORBHIP_EINVAL; }
+  ORBHIP_ARG(check_index(E, val_name, val, *total, n_ids, none_ok));
   return 0;
 }
 
@@ -482,50 +482,38 @@ int orbt_update_local_keyframes(int n_kp, const int32_t* frame_pt, int npts, con
   ORBHIP_REQUIRE(npts == 0 || pt_bad, ORBHIP_EINVAL, "orbt_update_local_keyframes: NULL pt_bad");
   ORBHIP_REQUIRE(nkf == 0 || (kf_bad && kf_parent), ORBHIP_EINVAL, "orbt_update_local_keyframes: NULL keyframe argument");
   ORBHIP_REQUIRE(n_prev == 0 || prev_local_kf, ORBHIP_EINVAL, "orbt_update_local_keyframes: NULL prev_local_kf");
+  static const char E[] = "orbt_update_local_keyframes";
   int nobs = 0, ncov = 0, nchild = 0, rc = 0;
-  if ((rc = ulm_check_csr(obs_off, obs_kf, npts, 0, nkf, 0, &nobs)) || (rc = ulm_check_csr(cov_off, cov_kf, nkf, 0, nkf, 10, &ncov)) ||
-      (rc = ulm_check_csr(child_off, child_kf, nkf, 0, nkf, 0, &nchild))) return rc;
-  for (int i = 0; i < n_kp; i++) ORBHIP_REQUIRE(frame_pt[i] >= -1 && frame_pt[i] < npts, ORBHIP_EINVAL, "orbt_update_local_keyframes: frame point id out of range");
-  for (int i = 0; i < n_prev; i++) ORBHIP_REQUIRE(prev_local_kf[i] >= 0 && prev_local_kf[i] < nkf, ORBHIP_EINVAL, "orbt_update_local_keyframes: previous local keyframe out of range");
-  for (int k = 0; k < nkf; k++) ORBHIP_REQUIRE(kf_parent[k] >= -1 && kf_parent[k] < nkf, ORBHIP_EINVAL, "orbt_update_local_keyframes: parent out of range");
-  if (kf_rank) {
-    std::vector<uint8_t> hit((size_t)nkf, 0);
-    for (int k = 0; k < nkf; k++) {
-      ORBHIP_REQUIRE(kf_rank[k] >= 0 && kf_rank[k] < nkf && !hit[kf_rank[k]], ORBHIP_EINVAL, "orbt_update_local_keyframes: kf_rank is not a permutation");
-      hit[kf_rank[k]] = 1;
-    }
-  }
+  if ((rc = ulm_check_csr(E, "obs_off", "obs_kf", obs_off, obs_kf, npts, false, nkf, 0, &nobs)) ||
+      (rc = ulm_check_csr(E, "cov_off", "cov_kf", cov_off, cov_kf, nkf, false, nkf, 10, &ncov)) ||
+      (rc = ulm_check_csr(E, "child_off", "child_kf", child_off, child_kf, nkf, false, nkf, 0, &nchild))) return rc;
+  ORBHIP_ARG(check_index(E, "frame_pt", frame_pt, n_kp, npts, true));
+  ORBHIP_ARG(check_index(E, "prev_local_kf", prev_local_kf, n_prev, nkf));
+  ORBHIP_ARG(check_index(E, "kf_parent", kf_parent, nkf, nkf, true));
+  if (kf_rank) ORBHIP_ARG(check_permutation(E, "kf_rank", kf_rank, nkf));
   ThreadWs& W = thread_ws();
   if ((rc = W.begin())) return rc;
-  ThreadWs::Pack in;
-  const int pF = n_kp ? in.add(frame_pt, 4 * (size_t)n_kp) : -1, pB = npts ? in.add(pt_bad, (size_t)npts) : -1, pOO = npts ? in.add(obs_off, 4 * ((size_t)npts + 1)) : -1;
-  const int pOK = nobs ? in.add(obs_kf, 4 * (size_t)nobs) : -1, pKB = nkf ? in.add(kf_bad, (size_t)nkf) : -1, pKR = nkf && kf_rank ? in.add(kf_rank, 4 * (size_t)nkf) : -1;
-  const int pKP = nkf ? in.add(kf_parent, 4 * (size_t)nkf) : -1, pCO = nkf ? in.add(cov_off, 4 * ((size_t)nkf + 1)) : -1, pCK = ncov ? in.add(cov_kf, 4 * (size_t)ncov) : -1;
-  const int pHO = nkf ? in.add(child_off, 4 * ((size_t)nkf + 1)) : -1, pHK = nchild ? in.add(child_kf, 4 * (size_t)nchild) : -1;
-  const int pPV = n_prev ? in.add(prev_local_kf, 4 * (size_t)n_prev) : -1;
-  // outputs in one block: [counts | frame_pt_out | local_kf | votes]
-  Carve out;
-  const size_t oC = out.take(16), oF = out.take(4 * (size_t)n_kp), oL = out.take(4 * (size_t)cap_kf), oV = out.take(4 * (size_t)nkf);
-  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
-  void* dws = W.d<uint8_t>(std::max<size_t>(ulm_workspace(nkf, npts, 0).total, 256), &rc);
-  if (rc || (rc = W.commit(in))) return rc;
+  const size_t nk = (size_t)nkf, np = (size_t)npts;
+  RoundTrip R(W);
+  const HostIn<int32_t> d_frame = R.in(frame_pt, (size_t)n_kp), d_prev = R.in(prev_local_kf, (size_t)n_prev), d_rank = R.in(kf_rank, nk), d_parent = R.in(kf_parent, nk);
+  const HostIn<int32_t> d_obs_off = R.csr(obs_off, np), d_cov_off = R.csr(cov_off, nk), d_child_off = R.csr(child_off, nk);
+  const HostIn<int32_t> d_obs_kf = R.in(obs_kf, (size_t)nobs), d_cov_kf = R.in(cov_kf, (size_t)ncov), d_child_kf = R.in(child_kf, (size_t)nchild);
+  const HostIn<uint8_t> d_pt_bad = R.in(pt_bad, np), d_kf_bad = R.in(kf_bad, nk);
+  const HostOut<int32_t> o_counts = R.out<int32_t>(4), o_frame = R.out<int32_t>((size_t)n_kp), o_local = R.out<int32_t>((size_t)cap_kf), o_votes = R.out<int32_t>(nk, votes != nullptr);
+  R.scratch(std::max<size_t>(ulm_workspace(nkf, npts, 0).total, 256));
+  if ((rc = R.commit())) return rc;
   UlmArgs A; std::memset(&A, 0, sizeof(A));
   A.n_kp = n_kp; A.n_prev = n_prev; A.npts = npts; A.nobs = nobs; A.nkf = nkf; A.ncov = ncov; A.nchild = nchild; A.cap_kf = cap_kf; A.host_n_list = -1; A.host_total = -1;
-  A.frame_pt = in.dev<int32_t>(pF); A.prev_kf = in.dev<int32_t>(pPV); A.pt_bad = in.dev<uint8_t>(pB); A.obs_off = in.dev<int32_t>(pOO); A.obs_kf = in.dev<int32_t>(pOK);
-  A.kf_bad = in.dev<uint8_t>(pKB); A.kf_rank = in.dev<int32_t>(pKR); A.kf_parent = in.dev<int32_t>(pKP); A.cov_off = in.dev<int32_t>(pCO); A.cov_kf = in.dev<int32_t>(pCK);
-  A.child_off = in.dev<int32_t>(pHO); A.child_kf = in.dev<int32_t>(pHK);
-  A.frame_pt_out = (int32_t*)(dblk + oF); A.local_kf = (int32_t*)(dblk + oL); A.counts = (int32_t*)(dblk + oC); A.votes_out = votes ? (int32_t*)(dblk + oV) : nullptr;
-  ulm_bind(A, dws);
-  if ((rc = ulm_enqueue(A, 1, W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, out.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  const int32_t* hc = (const int32_t*)(hb + oC);
-  *n_local_kf = hc[0];
-  ORBHIP_REQUIRE(hc[0] <= cap_kf, ORBHIP_ECAP, "orbt_update_local_keyframes: more local keyframes than cap_kf");
-  *ref_kf = hc[1]; *status = hc[3];
-  if (n_kp) std::memcpy(frame_pt_out, hb + oF, 4 * (size_t)n_kp);
-  if (hc[0]) std::memcpy(local_kf, hb + oL, 4 * (size_t)hc[0]);
-  if (votes && nkf) std::memcpy(votes, hb + oV, 4 * (size_t)nkf);
+  A.frame_pt = d_frame.dev(); A.prev_kf = d_prev.dev(); A.pt_bad = d_pt_bad.dev(); A.obs_off = d_obs_off.dev(); A.obs_kf = d_obs_kf.dev();
+  A.kf_bad = d_kf_bad.dev(); A.kf_rank = d_rank.dev(); A.kf_parent = d_parent.dev(); A.cov_off = d_cov_off.dev(); A.cov_kf = d_cov_kf.dev();
+  A.child_off = d_child_off.dev(); A.child_kf = d_child_kf.dev();
+  A.frame_pt_out = o_frame.dev(); A.local_kf = o_local.dev(); A.counts = o_counts.dev(); A.votes_out = o_votes.dev();
+  ulm_bind(A, R.scratch_dev());
+  if ((rc = ulm_enqueue(A, 1, R.stream())) || (rc = R.finish())) return rc;
+  *n_local_kf = o_counts[0];
+  ORBHIP_REQUIRE(o_counts[0] <= cap_kf, ORBHIP_ECAP, "orbt_update_local_keyframes: more local keyframes than cap_kf");
+  *ref_kf = o_counts[1]; *status = o_counts[3];
+  R.copy_out(o_frame, frame_pt_out, (size_t)n_kp); R.copy_out(o_local, local_kf, (size_t)o_counts[0]); R.copy_out(o_votes, votes, nk);
   return 0;
 }
 
@@ -542,55 +530,45 @@ int orbt_update_local_points(int n_local_kf, const int32_t* kf_slot_off, const i
   bool all = false;
   ORBHIP_REQUIRE(ulm_packed_all_or_none(packed, 8, &all), ORBHIP_EINVAL, "orbt_update_local_points: the packed outputs are given all or none");
   ORBHIP_REQUIRE(!all || npts == 0 || (pt_nobs && pt_Xw && pt_normal && pt_min_dist && pt_max_dist && pt_desc), ORBHIP_EINVAL, "orbt_update_local_points: NULL point record argument");
+  static const char E[] = "orbt_update_local_points";
   int nslots = 0, rc = 0;
-  if ((rc = ulm_check_csr(kf_slot_off, kf_slot_pt, n_local_kf, -1, npts, 0, &nslots))) return rc;
-  for (int i = 0; i < n_kp; i++) ORBHIP_REQUIRE(frame_pt[i] >= -1 && frame_pt[i] < npts, ORBHIP_EINVAL, "orbt_update_local_points: frame point id out of range");
-  for (int i = 0; i < n_seen; i++) ORBHIP_REQUIRE(seen_pt[i] >= 0 && seen_pt[i] < npts, ORBHIP_EINVAL, "orbt_update_local_points: seen point id out of range");
+  if ((rc = ulm_check_csr(E, "kf_slot_off", "kf_slot_pt", kf_slot_off, kf_slot_pt, n_local_kf, true, npts, 0, &nslots))) return rc;
+  ORBHIP_ARG(check_index(E, "frame_pt", frame_pt, n_kp, npts, true));
+  ORBHIP_ARG(check_index(E, "seen_pt", seen_pt, n_seen, npts));
   ThreadWs& W = thread_ws();
   if ((rc = W.begin())) return rc;
-  const int32_t zero_off[1] = {0};
-  ThreadWs::Pack in;
-  const int pSO = in.add(n_local_kf ? kf_slot_off : zero_off, 4 * ((size_t)n_local_kf + 1)), pSP = nslots ? in.add(kf_slot_pt, 4 * (size_t)nslots) : -1;
-  const int pB = npts ? in.add(pt_bad, (size_t)npts) : -1, pF = n_kp ? in.add(frame_pt, 4 * (size_t)n_kp) : -1, pSe = n_seen ? in.add(seen_pt, 4 * (size_t)n_seen) : -1;
-  const bool rec = all && npts > 0;
-  const int pN = rec ? in.add(pt_nobs, 4 * (size_t)npts) : -1, pX = rec ? in.add(pt_Xw, 24 * (size_t)npts) : -1, pNo = rec ? in.add(pt_normal, 24 * (size_t)npts) : -1;
-  const int pMi = rec ? in.add(pt_min_dist, 4 * (size_t)npts) : -1, pMa = rec ? in.add(pt_max_dist, 4 * (size_t)npts) : -1, pD = rec ? in.add(pt_desc, 32 * (size_t)npts) : -1;
-  // outputs in one block: [counts | local_pt | mp_Xw | mp_normal | mp_min | mp_max | mp_desc | mp_state | slot_Xw | slot_state]
-  Carve out;
-  const size_t oC = out.take(16), oL = out.take(4 * (size_t)cap_pt);
-  const size_t oX = out.take(all ? 24 * (size_t)cap_pt : 0), oNo = out.take(all ? 24 * (size_t)cap_pt : 0), oMi = out.take(all ? 4 * (size_t)cap_pt : 0);
-  const size_t oMa = out.take(all ? 4 * (size_t)cap_pt : 0), oD = out.take(all ? 32 * (size_t)cap_pt : 0), oS = out.take(all ? (size_t)cap_pt : 0);
-  const size_t oSX = out.take(all ? 24 * (size_t)n_kp : 0), oSS = out.take(all ? (size_t)n_kp : 0);
-  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
-  void* dws = W.d<uint8_t>(std::max<size_t>(ulm_workspace(0, npts, nslots).total, 256), &rc);
-  if (rc || (rc = W.commit(in))) return rc;
+  const size_t np = (size_t)npts, cap = (size_t)cap_pt, nf = (size_t)n_kp;
+  RoundTrip R(W);
+  const HostIn<int32_t> d_slot_off = R.csr(kf_slot_off, (size_t)n_local_kf), d_slot_pt = R.in(kf_slot_pt, (size_t)nslots);
+  const HostIn<int32_t> d_frame = R.in(frame_pt, nf), d_seen = R.in(seen_pt, (size_t)n_seen), d_nobs = R.in(all ? pt_nobs : nullptr, np);
+  const HostIn<uint8_t> d_bad = R.in(pt_bad, np), d_desc = R.in(all ? pt_desc : nullptr, 32 * np);
+  const HostIn<double> d_Xw = R.in(all ? pt_Xw : nullptr, 3 * np), d_normal = R.in(all ? pt_normal : nullptr, 3 * np);
+  const HostIn<float> d_min = R.in(all ? pt_min_dist : nullptr, np), d_max = R.in(all ? pt_max_dist : nullptr, np);
+  const HostOut<int32_t> o_counts = R.out<int32_t>(4), o_local = R.out<int32_t>(cap);
+  const HostOut<double> o_Xw = R.out<double>(3 * cap, all), o_normal = R.out<double>(3 * cap, all), o_slot_Xw = R.out<double>(3 * nf, all);
+  const HostOut<float> o_min = R.out<float>(cap, all), o_max = R.out<float>(cap, all);
+  const HostOut<uint8_t> o_desc = R.out<uint8_t>(32 * cap, all), o_state = R.out<uint8_t>(cap, all), o_slot_state = R.out<uint8_t>(nf, all);
+  R.scratch(std::max<size_t>(ulm_workspace(0, npts, nslots).total, 256));
+  if ((rc = R.commit())) return rc;
   UlmArgs A; std::memset(&A, 0, sizeof(A));
   A.n_kp = n_kp; A.n_seen = n_seen; A.npts = npts; A.nslots = nslots; A.max_slots = nslots; A.cap_pt = cap_pt; A.host_n_list = n_local_kf; A.host_total = nslots;
-  A.frame_pt = in.dev<int32_t>(pF); A.seen_pt = in.dev<int32_t>(pSe); A.pt_bad = in.dev<uint8_t>(pB); A.pt_nobs = in.dev<int32_t>(pN);
-  A.pt_Xw = in.dev<double>(pX); A.pt_normal = in.dev<double>(pNo); A.pt_min = in.dev<float>(pMi); A.pt_max = in.dev<float>(pMa); A.pt_desc = in.dev<uint8_t>(pD);
-  A.slot_off = in.dev<int32_t>(pSO); A.slot_pt = in.dev<int32_t>(pSP);
-  A.local_pt = (int32_t*)(dblk + oL); A.counts = (int32_t*)(dblk + oC);
-  if (all) {
-    A.mp_Xw = (double*)(dblk + oX); A.mp_normal = (double*)(dblk + oNo); A.mp_min = (float*)(dblk + oMi); A.mp_max = (float*)(dblk + oMa); A.mp_desc = dblk + oD;
-    A.mp_state = dblk + oS; A.slot_Xw = (double*)(dblk + oSX); A.slot_state = dblk + oSS;
-  }
-  ulm_bind(A, dws);
+  A.frame_pt = d_frame.dev(); A.seen_pt = d_seen.dev(); A.pt_bad = d_bad.dev(); A.pt_nobs = d_nobs.dev();
+  A.pt_Xw = d_Xw.dev(); A.pt_normal = d_normal.dev(); A.pt_min = d_min.dev(); A.pt_max = d_max.dev(); A.pt_desc = d_desc.dev();
+  A.slot_off = d_slot_off.dev(); A.slot_pt = d_slot_pt.dev();
+  A.local_pt = o_local.dev(); A.counts = o_counts.dev();
+  A.mp_Xw = o_Xw.dev(); A.mp_normal = o_normal.dev(); A.mp_min = o_min.dev(); A.mp_max = o_max.dev(); A.mp_desc = o_desc.dev();
+  A.mp_state = o_state.dev(); A.slot_Xw = o_slot_Xw.dev(); A.slot_state = o_slot_state.dev();
+  ulm_bind(A, R.scratch_dev());
   A.pos_off = const_cast<int32_t*>(A.slot_off);                     // (positions are the rows: the slot prefix IS the CSR; the points stage only reads it)
-  if ((rc = ulm_enqueue(A, 2, W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, out.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  const int n = ((const int32_t*)(hb + oC))[2];
+  if ((rc = ulm_enqueue(A, 2, R.stream())) || (rc = R.finish())) return rc;
+  const int n = o_counts[2];
   *n_local_pt = n;
   ORBHIP_REQUIRE(n <= cap_pt, ORBHIP_ECAP, "orbt_update_local_points: more local map points than cap_pt");
-  if (n) std::memcpy(local_pt, hb + oL, 4 * (size_t)n);
-  if (all) {
-    if (n) {
-      std::memcpy(mp_Xw, hb + oX, 24 * (size_t)n); std::memcpy(mp_normal, hb + oNo, 24 * (size_t)n); std::memcpy(mp_min_dist, hb + oMi, 4 * (size_t)n);
-      std::memcpy(mp_max_dist, hb + oMa, 4 * (size_t)n); std::memcpy(mp_desc, hb + oD, 32 * (size_t)n);
-    }
-    if (cap_pt) std::memcpy(mp_state, hb + oS, (size_t)cap_pt);
-    if (n_kp) { std::memcpy(slot_Xw, hb + oSX, 24 * (size_t)n_kp); std::memcpy(slot_state, hb + oSS, (size_t)n_kp); }
-  }
+  // the lists up to n: what lies behind them in the caller's arrays is not touched (mp_state is padded up to cap_pt by the gather)
+  const size_t nn = (size_t)n;
+  R.copy_out(o_local, local_pt, nn);
+  R.copy_out(o_Xw, mp_Xw, 3 * nn); R.copy_out(o_normal, mp_normal, 3 * nn); R.copy_out(o_min, mp_min_dist, nn); R.copy_out(o_max, mp_max_dist, nn);
+  R.copy_out(o_desc, mp_desc, 32 * nn); R.copy_out(o_state, mp_state, cap); R.copy_out(o_slot_Xw, slot_Xw, 3 * nf); R.copy_out(o_slot_state, slot_state, nf);
   return 0;
 }
 

@@ -440,87 +440,57 @@ int orbl_correct_loop(int nkf, double* kf_Tcw, double* kf_center, int nconn, con
   ORBHIP_REQUIRE(!nd || (n_levels > 0 && n_levels <= 64), ORBHIP_EINVAL, "orbl_correct_loop: n_levels out of range");
   ORBHIP_REQUIRE(mc_finite(Scw, 7) && (Scw[0] * Scw[0] + Scw[1] * Scw[1]) + (Scw[2] * Scw[2] + Scw[3] * Scw[3]) > 0.0, ORBHIP_EINVAL,
                  "orbl_correct_loop: Scw is not finite or its quaternion is zero");
-  ORBHIP_REQUIRE(slot_off[0] == 0, ORBHIP_EINVAL, "orbl_correct_loop: slot_off must start at 0");
-  for (int c = 0; c < nconn; c++) ORBHIP_REQUIRE(slot_off[c] <= slot_off[c + 1], ORBHIP_EINVAL, "orbl_correct_loop: slot_off decreases");
-  const int nslots = slot_off[nconn];
+  static const char E[] = "orbl_correct_loop";
+  int nslots = 0, nobs = 0;
+  ORBHIP_ARG(check_csr(E, "slot_off", slot_off, nconn, &nslots));
   ORBHIP_REQUIRE(nslots == 0 || slot_pt, ORBHIP_EINVAL, "orbl_correct_loop: NULL slot_pt");
-  int nobs = 0;
-  if (nd && npts > 0) {
-    ORBHIP_REQUIRE(obs_off[0] == 0, ORBHIP_EINVAL, "orbl_correct_loop: obs_off must start at 0");
-    for (int p = 0; p < npts; p++) ORBHIP_REQUIRE(obs_off[p] <= obs_off[p + 1], ORBHIP_EINVAL, "orbl_correct_loop: obs_off decreases");
-    nobs = obs_off[npts];
+  if (nd) {
+    ORBHIP_ARG(check_csr(E, "obs_off", obs_off, npts, &nobs));
     ORBHIP_REQUIRE(nobs == 0 || obs_kf, ORBHIP_EINVAL, "orbl_correct_loop: NULL obs_kf");
   }
-  std::vector<int32_t> seen((size_t)nkf, -1);
-  for (int c = 0; c < nconn; c++) {
-    ORBHIP_REQUIRE(conn_kf[c] >= 0 && conn_kf[c] < nkf, ORBHIP_EINVAL, "orbl_correct_loop: connected keyframe index out of range");
-    ORBHIP_REQUIRE(seen[conn_kf[c]] < 0, ORBHIP_EINVAL, "orbl_correct_loop: a keyframe is listed twice in conn_kf");
-    seen[conn_kf[c]] = c;
-  }
-  if (conn_rank) {
-    std::vector<uint8_t> hit((size_t)nconn, 0);
-    for (int c = 0; c < nconn; c++) {
-      ORBHIP_REQUIRE(conn_rank[c] >= 0 && conn_rank[c] < nconn && !hit[conn_rank[c]], ORBHIP_EINVAL, "orbl_correct_loop: conn_rank is not a permutation");
-      hit[conn_rank[c]] = 1;
-    }
-  }
-  for (int s = 0; s < nslots; s++) ORBHIP_REQUIRE(slot_pt[s] >= -1 && slot_pt[s] < npts, ORBHIP_EINVAL, "orbl_correct_loop: slot point index out of range");
+  ORBHIP_ARG(check_listed_once(E, "conn_kf", conn_kf, nconn, nkf));
+  if (conn_rank) ORBHIP_ARG(check_permutation(E, "conn_rank", conn_rank, nconn));
+  ORBHIP_ARG(check_index(E, "slot_pt", slot_pt, nslots, npts, true));
   if (nd) {
-    for (int e = 0; e < nobs; e++) ORBHIP_REQUIRE(obs_kf[e] >= 0 && obs_kf[e] < nkf, ORBHIP_EINVAL, "orbl_correct_loop: observation keyframe index out of range");
-    for (int p = 0; p < npts; p++) {
-      if (obs_off[p] == obs_off[p + 1] || (pt_bad && pt_bad[p])) continue;             // (no normal: its reference keyframe is not read)
-      ORBHIP_REQUIRE(ref_kf[p] >= 0 && ref_kf[p] < nkf, ORBHIP_EINVAL, "orbl_correct_loop: reference keyframe index out of range");
-      ORBHIP_REQUIRE(ref_level[p] >= 0 && ref_level[p] < n_levels, ORBHIP_EINVAL, "orbl_correct_loop: level out of range");
-    }
+    ORBHIP_ARG(check_index(E, "obs_kf", obs_kf, nobs, nkf));
+    const auto read = [&](int p) { return obs_off[p] != obs_off[p + 1] && !(pt_bad && pt_bad[p]); };          // (no normal: its reference keyframe is not read)
+    ORBHIP_ARG(check_index_if(E, "ref_kf", ref_kf, npts, nkf, read));
+    ORBHIP_ARG(check_index_if(E, "ref_level", ref_level, npts, n_levels, read));
   }
   ThreadWs& W = thread_ws();
   int rc = W.begin();
   if (rc) return rc;
-  ThreadWs::Pack in;
-  const size_t np = (size_t)npts, nc = (size_t)nconn;
-  const int pT = in.add(kf_Tcw, 96 * (size_t)nkf), pC = kf_center ? in.add(kf_center, 24 * (size_t)nkf) : -1, pK = in.add(conn_kf, 4 * nc);
-  const int pR = conn_rank ? in.add(conn_rank, 4 * nc) : -1, pS = in.add(Scw, 56), pSO = in.add(slot_off, 4 * (nc + 1)), pSP = nslots ? in.add(slot_pt, 4 * (size_t)nslots) : -1;
-  const int pX = npts ? in.add(X, 24 * np) : -1, pB = npts && pt_bad ? in.add(pt_bad, np) : -1, pD = npts && pt_done ? in.add(pt_done, np) : -1;
-  const int32_t zero_off[1] = {0};
-  const int pOO = nd ? in.add(npts ? obs_off : zero_off, 4 * (np + 1)) : -1, pOK = nd && nobs ? in.add(obs_kf, 4 * (size_t)nobs) : -1;
-  const int pRK = nd ? in.add(ref_kf, 4 * np) : -1, pRL = nd ? in.add(ref_level, 4 * np) : -1, pSF = nd ? in.add(scale_factors, 4 * (size_t)n_levels) : -1;
-  // outputs in one block: [counts, status | corrected | non_corrected | pt_owner | normal | min_max | nd_written]; the in/out tables come back from the upload block
-  Carve out;
-  const size_t oC = out.take(32), oSc = out.take(56 * nc), oSn = out.take(56 * nc), oO = out.take(4 * np), oN = out.take(nd ? 24 * np : 0), oM = out.take(nd ? 8 * np : 0),
-               oW = out.take(nd ? np : 0);
-  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
-  void* dws = W.d<uint8_t>(ml_workspace(nkf, nconn, npts).total, &rc);
-  if (rc || (rc = W.commit(in))) return rc;
-  if ((rc = orbl_correct_loop_device(nkf, in.dev<double>(pT), in.dev<double>(pC), nconn, in.dev<int32_t>(pK), in.dev<int32_t>(pR), in.dev<double>(pS), nslots,
-                                     in.dev<int32_t>(pSO), in.dev<int32_t>(pSP), npts, in.dev<double>(pX), in.dev<uint8_t>(pB), in.dev<uint8_t>(pD), nobs,
-                                     in.dev<int32_t>(pOO), in.dev<int32_t>(pOK), in.dev<int32_t>(pRK), in.dev<int32_t>(pRL), in.dev<float>(pSF), n_levels,
-                                     (double*)(dblk + oSc), (double*)(dblk + oSn), (int32_t*)(dblk + oO), nd ? (double*)(dblk + oN) : nullptr,
-                                     nd ? (float*)(dblk + oM) : nullptr, nd ? dblk + oW : nullptr, (int32_t*)(dblk + oC), (uint32_t*)(dblk + oC + 16), dws, W.s)))
+  const size_t nk = (size_t)nkf, nc = (size_t)nconn, np = (size_t)npts;
+  const bool run_nd = nd && npts > 0;                               // (without points the device entry takes the normal / depth set as absent)
+  RoundTrip R(W);
+  const HostOut<double> t_Tcw = R.inout(kf_Tcw, 12 * nk), t_center = R.inout(kf_center, 3 * nk), t_X = R.inout(X, 3 * np);
+  const HostIn<int32_t> d_conn = R.in(conn_kf, nc), d_rank = R.in(conn_rank, nc), d_slot_off = R.csr(slot_off, nc), d_slot_pt = R.in(slot_pt, (size_t)nslots);
+  const HostIn<int32_t> d_obs_off = R.csr(run_nd ? obs_off : nullptr, np), d_obs_kf = R.in(run_nd ? obs_kf : nullptr, (size_t)nobs);
+  const HostIn<int32_t> d_ref = R.in(run_nd ? ref_kf : nullptr, np), d_lvl = R.in(run_nd ? ref_level : nullptr, np);
+  const HostIn<uint8_t> d_bad = R.in(pt_bad, np), d_done = R.in(pt_done, np);
+  const HostIn<double> d_Scw = R.in(Scw, 7);
+  const HostIn<float> d_sf = R.in(run_nd ? scale_factors : nullptr, (size_t)n_levels);
+  const HostOut<int32_t> o_counts = R.out<int32_t>(2), o_owner = R.out<int32_t>(np);
+  const HostOut<double> o_corr = R.out<double>(7 * nc), o_non = R.out<double>(7 * nc), o_normal = R.out<double>(3 * np, run_nd);
+  const HostOut<float> o_mm = R.out<float>(2 * np, run_nd);
+  const HostOut<uint8_t> o_wrote = R.out<uint8_t>(np, run_nd);
+  const HostOut<uint32_t> o_status = R.out<uint32_t>(1);
+  R.scratch(ml_workspace(nkf, nconn, npts).total);
+  if ((rc = R.commit())) return rc;
+  if ((rc = orbl_correct_loop_device(nkf, t_Tcw.dev(), t_center.dev(), nconn, d_conn.dev(), d_rank.dev(), d_Scw.dev(), nslots, d_slot_off.dev(), d_slot_pt.dev(), npts,
+                                     t_X.dev(), d_bad.dev(), d_done.dev(), nobs, d_obs_off.dev(), d_obs_kf.dev(), d_ref.dev(), d_lvl.dev(), d_sf.dev(), n_levels,
+                                     o_corr.dev(), o_non.dev(), o_owner.dev(), o_normal.dev(), o_mm.dev(), o_wrote.dev(), o_counts.dev(), o_status.dev(),
+                                     R.scratch_dev(), R.stream())))
     return rc;
-  // one download: the output block, and behind it the tables that changed in place
-  Carve back;
-  const size_t bO = back.take(out.total), bT = back.take(96 * (size_t)nkf), bC = back.take(kf_center ? 24 * (size_t)nkf : 0), bX = back.take(24 * np);
-  uint8_t* dback = W.d<uint8_t>(back.total, &rc);
-  if (rc) return rc;
-  ORBHIP_CHECK_HIP(hipMemcpyAsync(dback + bO, dblk, out.total, hipMemcpyDeviceToDevice, W.s));
-  ORBHIP_CHECK_HIP(hipMemcpyAsync(dback + bT, in.dev<double>(pT), 96 * (size_t)nkf, hipMemcpyDeviceToDevice, W.s));
-  if (kf_center) ORBHIP_CHECK_HIP(hipMemcpyAsync(dback + bC, in.dev<double>(pC), 24 * (size_t)nkf, hipMemcpyDeviceToDevice, W.s));
-  if (npts) ORBHIP_CHECK_HIP(hipMemcpyAsync(dback + bX, in.dev<double>(pX), 24 * np, hipMemcpyDeviceToDevice, W.s));
-  const uint8_t* hb = W.down(dback, back.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  std::memcpy(counts, hb + bO + oC, 8);
-  std::memcpy(corrected, hb + bO + oSc, 56 * nc); std::memcpy(non_corrected, hb + bO + oSn, 56 * nc);
-  std::memcpy(kf_Tcw, hb + bT, 96 * (size_t)nkf);
-  if (kf_center) std::memcpy(kf_center, hb + bC, 24 * (size_t)nkf);
-  if (npts) { std::memcpy(X, hb + bX, 24 * np); std::memcpy(pt_owner, hb + bO + oO, 4 * np); }
-  if (nd && npts) {
-    const uint8_t* hw = hb + bO + oW;
-    const int32_t* ho = (const int32_t*)(hb + bO + oO);
-    for (int p = 0; p < npts; p++) {
-      if (ho[p] < 0) continue;                                                 // (rows of points that did not move are not touched)
-      nd_written[p] = hw[p];
-      if (hw[p]) { std::memcpy(normal + 3 * (size_t)p, hb + bO + oN + 24 * (size_t)p, 24); std::memcpy(min_max + 2 * (size_t)p, hb + bO + oM + 8 * (size_t)p, 8); }
-    }
+  if ((rc = R.finish())) return rc;
+  R.copy_out(o_counts, counts, 2);
+  R.copy_out(o_corr, corrected, 7 * nc); R.copy_out(o_non, non_corrected, 7 * nc);
+  R.copy_out(t_Tcw, kf_Tcw, 12 * nk); R.copy_out(t_center, kf_center, 3 * nk); R.copy_out(t_X, X, 3 * np);
+  R.copy_out(o_owner, pt_owner, np);
+  for (size_t p = 0; run_nd && p < np; p++) {
+    if (o_owner[p] < 0) continue;                                   // (rows of points that did not move are not touched)
+    nd_written[p] = o_wrote[p];
+    if (o_wrote[p]) { std::copy_n(&o_normal[3 * p], 3, normal + 3 * p); std::copy_n(&o_mm[2 * p], 2, min_max + 2 * p); }
   }
   return 0;
 }
@@ -578,52 +548,39 @@ int orbl_propagate_global_ba(int nkf, double* kf_Tcw, double* kf_gba_Tcw, uint8_
   ORBHIP_REQUIRE(n_origin == 0 || origin_kf, ORBHIP_EINVAL, "orbl_propagate_global_ba: NULL origin_kf");
   ORBHIP_REQUIRE(npts == 0 || (X && pt_ref_kf && pt_moved), ORBHIP_EINVAL, "orbl_propagate_global_ba: NULL point argument");
   ORBHIP_REQUIRE((pt_in_gba != nullptr) == (pt_gba_X != nullptr), ORBHIP_EINVAL, "orbl_propagate_global_ba: pt_in_gba and pt_gba_X are given together");
-  for (int i = 0; i < n_origin; i++) ORBHIP_REQUIRE(origin_kf[i] >= 0 && origin_kf[i] < nkf, ORBHIP_EINVAL, "orbl_propagate_global_ba: origin keyframe index out of range");
-  for (int k = 0; k < nkf; k++) ORBHIP_REQUIRE(kf_parent[k] >= -1 && kf_parent[k] < nkf && kf_parent[k] != k, ORBHIP_EINVAL, "orbl_propagate_global_ba: parent index out of range");
-  for (int p = 0; p < npts; p++) {
-    if ((pt_bad && pt_bad[p]) || (pt_in_gba && pt_in_gba[p])) continue;               // (its reference keyframe is not read)
-    ORBHIP_REQUIRE(pt_ref_kf[p] >= 0 && pt_ref_kf[p] < nkf, ORBHIP_EINVAL, "orbl_propagate_global_ba: reference keyframe index out of range");
-  }
+  static const char E[] = "orbl_propagate_global_ba";
+  ORBHIP_ARG(check_index(E, "origin_kf", origin_kf, n_origin, nkf));
+  ORBHIP_ARG(check_index(E, "kf_parent", kf_parent, nkf, nkf, true));
+  for (int k = 0; k < nkf; k++) ORBHIP_REQUIRE(kf_parent[k] != k, ORBHIP_EINVAL, "orbl_propagate_global_ba: a keyframe is its own kf_parent");
+  const auto read = [&](int p) { return !(pt_bad && pt_bad[p]) && !(pt_in_gba && pt_in_gba[p]); };           // (else its reference keyframe is not read)
+  ORBHIP_ARG(check_index_if(E, "pt_ref_kf", pt_ref_kf, npts, nkf, read));
   ThreadWs& W = thread_ws();
   int rc = W.begin();
   if (rc) return rc;
   const size_t nk = (size_t)nkf, np = (size_t)npts;
-  ThreadWs::Pack in;
-  const int pT = nkf ? in.add(kf_Tcw, 96 * nk) : -1, pG = nkf ? in.add(kf_gba_Tcw, 96 * nk) : -1, pF = nkf ? in.add(kf_in_gba, nk) : -1;
-  const int pO = nkf && kf_center ? in.add(kf_center, 24 * nk) : -1, pX = npts ? in.add(X, 24 * np) : -1;
-  const int pP = nkf ? in.add(kf_parent, 4 * nk) : -1, pOr = n_origin ? in.add(origin_kf, 4 * (size_t)n_origin) : -1, pB = npts && pt_bad ? in.add(pt_bad, np) : -1;
-  const int pIn = npts && pt_in_gba ? in.add(pt_in_gba, np) : -1, pGX = npts && pt_in_gba ? in.add(pt_gba_X, 24 * np) : -1, pRf = npts ? in.add(pt_ref_kf, 4 * np) : -1;
-  // one download: [counts, status | bef | reached | moved] and behind it the tables that changed in place
-  Carve back;
-  const size_t oC = back.take(32), oBf = back.take(96 * nk), oRe = back.take(nk), oMv = back.take(np);
-  const size_t bT = back.take(96 * nk), bG = back.take(96 * nk), bF = back.take(nk), bO = back.take(kf_center ? 24 * nk : 0), bX = back.take(24 * np);
-  uint8_t* dblk = W.d<uint8_t>(back.total, &rc);
-  void* dws = W.d<uint8_t>(gb_workspace_bytes(nkf), &rc);
-  if (rc || (rc = W.commit(in))) return rc;
-  const bool has_in = npts && pt_in_gba;
-  if ((rc = orbl_propagate_global_ba_device(nkf, in.dev<double>(pT), in.dev<double>(pG), in.dev<uint8_t>(pF), in.dev<int32_t>(pP), n_origin, in.dev<int32_t>(pOr),
-                                            in.dev<double>(pO), npts, in.dev<double>(pX), in.dev<uint8_t>(pB), has_in ? in.dev<uint8_t>(pIn) : nullptr,
-                                            has_in ? in.dev<double>(pGX) : nullptr, in.dev<int32_t>(pRf), (double*)(dblk + oBf), dblk + oRe, dblk + oMv,
-                                            (int32_t*)(dblk + oC), (uint32_t*)(dblk + oC + 16), dws, W.s)))
+  RoundTrip R(W);
+  const HostOut<double> t_Tcw = R.inout(kf_Tcw, 12 * nk), t_gba = R.inout(kf_gba_Tcw, 12 * nk), t_center = R.inout(kf_center, 3 * nk), t_X = R.inout(X, 3 * np);
+  const HostOut<uint8_t> t_in_gba = R.inout(kf_in_gba, nk);
+  const HostIn<int32_t> d_parent = R.in(kf_parent, nk), d_origin = R.in(origin_kf, (size_t)n_origin), d_ref = R.in(pt_ref_kf, np);
+  const HostIn<uint8_t> d_bad = R.in(pt_bad, np), d_pt_in = R.in(pt_in_gba, np);
+  const HostIn<double> d_gba_X = R.in(pt_gba_X, 3 * np);
+  const HostOut<int32_t> o_counts = R.out<int32_t>(4);
+  const HostOut<double> o_bef = R.out<double>(12 * nk);
+  const HostOut<uint8_t> o_reached = R.out<uint8_t>(nk), o_moved = R.out<uint8_t>(np);
+  const HostOut<uint32_t> o_status = R.out<uint32_t>(1);
+  R.scratch(gb_workspace_bytes(nkf));
+  if ((rc = R.commit())) return rc;
+  if ((rc = orbl_propagate_global_ba_device(nkf, t_Tcw.dev(), t_gba.dev(), t_in_gba.dev(), d_parent.dev(), n_origin, d_origin.dev(), t_center.dev(), npts, t_X.dev(),
+                                            d_bad.dev(), d_pt_in.dev(), d_gba_X.dev(), d_ref.dev(), o_bef.dev(), o_reached.dev(), o_moved.dev(), o_counts.dev(),
+                                            o_status.dev(), R.scratch_dev(), R.stream())))
     return rc;
-  if (nkf) {
-    ORBHIP_CHECK_HIP(hipMemcpyAsync(dblk + bT, in.dev<double>(pT), 96 * nk, hipMemcpyDeviceToDevice, W.s));
-    ORBHIP_CHECK_HIP(hipMemcpyAsync(dblk + bG, in.dev<double>(pG), 96 * nk, hipMemcpyDeviceToDevice, W.s));
-    ORBHIP_CHECK_HIP(hipMemcpyAsync(dblk + bF, in.dev<uint8_t>(pF), nk, hipMemcpyDeviceToDevice, W.s));
-    if (kf_center) ORBHIP_CHECK_HIP(hipMemcpyAsync(dblk + bO, in.dev<double>(pO), 24 * nk, hipMemcpyDeviceToDevice, W.s));
-  }
-  if (npts) ORBHIP_CHECK_HIP(hipMemcpyAsync(dblk + bX, in.dev<double>(pX), 24 * np, hipMemcpyDeviceToDevice, W.s));
-  const uint8_t* hb = W.down(dblk, back.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  std::memcpy(counts, hb + oC, 16);
-  if (nkf) {
-    std::memcpy(kf_Tcw, hb + bT, 96 * nk); std::memcpy(kf_gba_Tcw, hb + bG, 96 * nk); std::memcpy(kf_in_gba, hb + bF, nk);
-    if (kf_center) std::memcpy(kf_center, hb + bO, 24 * nk);
-    std::memcpy(kf_reached, hb + oRe, nk);
-    const uint8_t* hr = hb + oRe;
-    for (int k = 0; k < nkf; k++) if (hr[k]) std::memcpy(kf_bef_Tcw + 12 * (size_t)k, hb + oBf + 96 * (size_t)k, 96);      // (rows of unreached keyframes are not touched)
-  }
-  if (npts) { std::memcpy(X, hb + bX, 24 * np); std::memcpy(pt_moved, hb + oMv, np); }
+  if ((rc = R.finish())) return rc;
+  R.copy_out(o_counts, counts, 4);
+  R.copy_out(t_Tcw, kf_Tcw, 12 * nk); R.copy_out(t_gba, kf_gba_Tcw, 12 * nk); R.copy_out(t_in_gba, kf_in_gba, nk); R.copy_out(t_center, kf_center, 3 * nk);
+  R.copy_out(o_reached, kf_reached, nk);
+  for (size_t k = 0; k < nk; k++)
+    if (o_reached[k]) std::copy_n(&o_bef[12 * k], 12, kf_bef_Tcw + 12 * k);          // (rows of unreached keyframes are not touched)
+  R.copy_out(t_X, X, 3 * np); R.copy_out(o_moved, pt_moved, np);
   return 0;
 }
 

@@ -309,47 +309,45 @@ int orbl_update_map_points(int npts, const int32_t* obs_off, const double* X, co
   ORBHIP_REQUIRE(!nd || (X && ref_kf && ref_level && (nobs == 0 || obs_kf) && (nkf == 0 || kf_center) && scale_factors && normal && min_max && nd_written),
                  ORBHIP_EINVAL, "orbl_update_map_points: NULL normal / depth argument");
   ORBHIP_REQUIRE(!nd || (n_levels > 0 && n_levels <= 64), ORBHIP_EINVAL, "orbl_update_map_points: n_levels out of range");
-  ORBHIP_REQUIRE(obs_off[0] == 0 && obs_off[npts] == nobs, ORBHIP_EINVAL, "orbl_update_map_points: obs_off must run from 0 to nobs");
-  for (int p = 0; p < npts; p++) ORBHIP_REQUIRE(obs_off[p] <= obs_off[p + 1], ORBHIP_EINVAL, "orbl_update_map_points: obs_off decreases");
+  static const char E[] = "orbl_update_map_points";
+  int total = 0;
+  ORBHIP_ARG(check_csr(E, "obs_off", obs_off, npts, &total));
+  ORBHIP_REQUIRE(total == nobs, ORBHIP_EINVAL, "orbl_update_map_points: obs_off must run from 0 to nobs");
   if (nd) {
-    for (int e = 0; e < nobs; e++) ORBHIP_REQUIRE(obs_kf[e] >= 0 && obs_kf[e] < nkf, ORBHIP_EINVAL, "orbl_update_map_points: keyframe index out of range");
-    for (int p = 0; p < npts; p++) {
-      if (obs_off[p] == obs_off[p + 1] || (pt_good && !pt_good[p])) continue;        // (left unchanged: its reference keyframe is not read)
-      ORBHIP_REQUIRE(ref_kf[p] >= 0 && ref_kf[p] < nkf, ORBHIP_EINVAL, "orbl_update_map_points: reference keyframe index out of range");
-      ORBHIP_REQUIRE(ref_level[p] >= 0 && ref_level[p] < n_levels, ORBHIP_EINVAL, "orbl_update_map_points: level out of range");
-    }
+    ORBHIP_ARG(check_index(E, "obs_kf", obs_kf, nobs, nkf));
+    const auto read = [&](int p) { return obs_off[p] != obs_off[p + 1] && !(pt_good && !pt_good[p]); };      // (a point left unchanged: its reference keyframe is not read)
+    ORBHIP_ARG(check_index_if(E, "ref_kf", ref_kf, npts, nkf, read));
+    ORBHIP_ARG(check_index_if(E, "ref_level", ref_level, npts, n_levels, read));
   }
   ThreadWs& W = thread_ws();
   int rc = W.begin();
   if (rc) return rc;
-  ThreadWs::Pack in;
-  const int pO = in.add(obs_off, 4 * ((size_t)npts + 1)), pG = pt_good ? in.add(pt_good, (size_t)npts) : -1;
-  const int pD = desc ? in.add(obs_desc, 32 * (size_t)nobs) : -1, pK = obs_kf_good && desc ? in.add(obs_kf_good, (size_t)nobs) : -1;
-  const int pX = nd ? in.add(X, 24 * (size_t)npts) : -1, pR = nd ? in.add(ref_kf, 4 * (size_t)npts) : -1, pL = nd ? in.add(ref_level, 4 * (size_t)npts) : -1;
-  const int pF = nd ? in.add(obs_kf, 4 * (size_t)nobs) : -1, pC = nd ? in.add(kf_center, 24 * (size_t)nkf) : -1, pS = nd ? in.add(scale_factors, 4 * (size_t)n_levels) : -1;
-  // outputs in one block: [best_obs | desc_out | normal | min_max | nd_written]
-  Carve out;
-  const size_t oB = out.take(4 * (size_t)npts), oD = out.take(32 * (size_t)npts), oN = out.take(24 * (size_t)npts), oM = out.take(8 * (size_t)npts), oW = out.take((size_t)npts);
-  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
-  void* dws = W.d<uint8_t>(mp_workspace_bytes(npts), &rc);
-  if (rc || (rc = W.commit(in))) return rc;
-  if ((rc = orbl_update_map_points_device(npts, in.dev<int32_t>(pO), in.dev<double>(pX), in.dev<int32_t>(pR), in.dev<int32_t>(pL), in.dev<uint8_t>(pG), nobs,
-                                          in.dev<int32_t>(pF), in.dev<uint8_t>(pD), in.dev<uint8_t>(pK), nkf, in.dev<double>(pC), in.dev<float>(pS), n_levels, what,
-                                          (int32_t*)(dblk + oB), dblk + oD, (double*)(dblk + oN), (float*)(dblk + oM), dblk + oW, dws, W.s))) return rc;
-  const uint8_t* hb = W.down(dblk, out.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
+  const size_t np = (size_t)npts, no = (size_t)nobs;
+  RoundTrip R(W);
+  const HostIn<int32_t> d_off = R.csr(obs_off, np), d_ref = R.in(nd ? ref_kf : nullptr, np), d_lvl = R.in(nd ? ref_level : nullptr, np), d_kf = R.in(nd ? obs_kf : nullptr, no);
+  const HostIn<uint8_t> d_good = R.in(pt_good, np), d_desc = R.in(desc ? obs_desc : nullptr, 32 * no), d_kf_good = R.in(desc ? obs_kf_good : nullptr, no);
+  const HostIn<double> d_X = R.in(nd ? X : nullptr, 3 * np), d_ctr = R.in(nd ? kf_center : nullptr, 3 * (size_t)nkf);
+  const HostIn<float> d_sf = R.in(nd ? scale_factors : nullptr, (size_t)n_levels);
+  const HostOut<int32_t> o_best = R.out<int32_t>(np);
+  const HostOut<uint8_t> o_desc = R.out<uint8_t>(32 * np), o_wrote = R.out<uint8_t>(np);
+  const HostOut<double> o_normal = R.out<double>(3 * np);
+  const HostOut<float> o_mm = R.out<float>(2 * np);
+  R.scratch(mp_workspace_bytes(npts));
+  if ((rc = R.commit())) return rc;
+  if ((rc = orbl_update_map_points_device(npts, d_off.dev(), d_X.dev(), d_ref.dev(), d_lvl.dev(), d_good.dev(), nobs, d_kf.dev(), d_desc.dev(), d_kf_good.dev(), nkf,
+                                          d_ctr.dev(), d_sf.dev(), n_levels, what, o_best.dev(), o_desc.dev(), o_normal.dev(), o_mm.dev(), o_wrote.dev(),
+                                          R.scratch_dev(), R.stream()))) return rc;
+  if ((rc = R.finish())) return rc;
   // only what the call wrote reaches the caller's buffers: unchanged points keep their bytes
-  const int32_t* hbest = (const int32_t*)(hb + oB);
-  const uint8_t* hwrote = hb + oW;
   if (desc) {
-    std::memcpy(best_obs, hbest, 4 * (size_t)npts);
-    for (int p = 0; p < npts; p++)
-      if (hbest[p] >= 0) std::memcpy(desc_out + 32 * (size_t)p, hb + oD + 32 * (size_t)p, 32);
+    R.copy_out(o_best, best_obs, np);
+    for (size_t p = 0; p < np; p++)
+      if (o_best[p] >= 0) std::copy_n(&o_desc[32 * p], 32, desc_out + 32 * p);
   }
   if (nd) {
-    std::memcpy(nd_written, hwrote, (size_t)npts);
-    for (int p = 0; p < npts; p++)
-      if (hwrote[p]) { std::memcpy(normal + 3 * (size_t)p, hb + oN + 24 * (size_t)p, 24); std::memcpy(min_max + 2 * (size_t)p, hb + oM + 8 * (size_t)p, 8); }
+    R.copy_out(o_wrote, nd_written, np);
+    for (size_t p = 0; p < np; p++)
+      if (o_wrote[p]) { std::copy_n(&o_normal[3 * p], 3, normal + 3 * p); std::copy_n(&o_mm[2 * p], 2, min_max + 2 * p); }
   }
   return 0;
 }

@@ -503,83 +503,61 @@ int orbl_update_connections(int ntgt, const int32_t* tgt_kf, const uint8_t* tgt_
   ORBHIP_REQUIRE(link_off || !link_kf, ORBHIP_EINVAL, "orbl_update_connections: link_kf without link_off");
   ORBHIP_REQUIRE((cap_aff == 0 || aff_kf) && (cap_conn == 0 || (oconn_kf && oconn_w)) && (cap_ord == 0 || (oord_kf && oord_w)) && (!link_off || cap_link == 0 || link_kf),
                  ORBHIP_EINVAL, "orbl_update_connections: NULL list output");
+  static const char E[] = "orbl_update_connections";
   int nslots = 0, nobs = 0, nconn = 0, nprev = 0;
-  struct { const int32_t* off; int rows; int* total; const char* what; } csr[] = {{slot_off, ntgt, &nslots, "slot_off"}, {obs_off, npts, &nobs, "obs_off"},
-                                                                                 {conn_off, nkf, &nconn, "conn_off"}, {prev_off, prev_off ? ntgt : 0, &nprev, "prev_off"}};
-  for (const auto& c : csr) {
-    if (c.rows == 0) continue;
-    ORBHIP_REQUIRE(c.off[0] == 0, ORBHIP_EINVAL, "orbl_update_connections: CSR offsets must start at 0");
-    for (int r = 0; r < c.rows; r++) ORBHIP_REQUIRE(c.off[r] <= c.off[r + 1], ORBHIP_EINVAL, "orbl_update_connections: CSR offsets decrease");
-    *c.total = c.off[c.rows];
-  }
+  ORBHIP_ARG(check_csr(E, "slot_off", slot_off, ntgt, &nslots));
+  ORBHIP_ARG(check_csr(E, "obs_off", obs_off, npts, &nobs));
+  ORBHIP_ARG(check_csr(E, "conn_off", conn_off, nkf, &nconn));
+  ORBHIP_ARG(check_csr(E, "prev_off", prev_off, prev_off ? ntgt : 0, &nprev));
   ORBHIP_REQUIRE((nslots == 0 || slot_pt) && (nobs == 0 || obs_kf) && (nconn == 0 || (conn_kf && conn_w)), ORBHIP_EINVAL, "orbl_update_connections: NULL CSR entries");
-  std::vector<int32_t> seen((size_t)nkf, -1);
-  for (int t = 0; t < ntgt; t++) {
-    ORBHIP_REQUIRE(tgt_kf[t] >= 0 && tgt_kf[t] < nkf, ORBHIP_EINVAL, "orbl_update_connections: target keyframe index out of range");
-    ORBHIP_REQUIRE(seen[tgt_kf[t]] < 0, ORBHIP_EINVAL, "orbl_update_connections: a keyframe is listed twice among the targets");
-    seen[tgt_kf[t]] = t;
-  }
-  for (int s = 0; s < nslots; s++) ORBHIP_REQUIRE(slot_pt[s] >= -1 && slot_pt[s] < npts, ORBHIP_EINVAL, "orbl_update_connections: slot point index out of range");
-  for (int e = 0; e < nobs; e++) ORBHIP_REQUIRE(obs_kf[e] >= 0 && obs_kf[e] < nkf, ORBHIP_EINVAL, "orbl_update_connections: observation keyframe index out of range");
-  for (int e = 0; e < nprev; e++) ORBHIP_REQUIRE(prev_kf[e] >= 0 && prev_kf[e] < nkf, ORBHIP_EINVAL, "orbl_update_connections: previous neighbour out of range");
-  if (kf_rank) {
-    std::fill(seen.begin(), seen.end(), -1);
-    for (int k = 0; k < nkf; k++) {
-      ORBHIP_REQUIRE(kf_rank[k] >= 0 && kf_rank[k] < nkf && seen[kf_rank[k]] < 0, ORBHIP_EINVAL, "orbl_update_connections: kf_rank is not a permutation");
-      seen[kf_rank[k]] = k;
-    }
-  }
-  std::fill(seen.begin(), seen.end(), -1);
+  ORBHIP_ARG(check_listed_once(E, "tgt_kf", tgt_kf, ntgt, nkf));
+  ORBHIP_ARG(check_index(E, "slot_pt", slot_pt, nslots, npts, true));
+  ORBHIP_ARG(check_index(E, "obs_kf", obs_kf, nobs, nkf));
+  ORBHIP_ARG(check_index(E, "prev_kf", prev_kf, nprev, nkf));
+  if (kf_rank) ORBHIP_ARG(check_permutation(E, "kf_rank", kf_rank, nkf));
+  ORBHIP_ARG(check_index(E, "conn_kf", conn_kf, nconn, nkf));
+  std::vector<int32_t> seen((size_t)nkf, -1);                       // (per ROW of the table: the last row that named the keyframe)
   for (int k = 0; k < nkf; k++)
     for (int e = conn_off[k]; e < conn_off[k + 1]; e++) {
-      ORBHIP_REQUIRE(conn_kf[e] >= 0 && conn_kf[e] < nkf, ORBHIP_EINVAL, "orbl_update_connections: table keyframe index out of range");
-      ORBHIP_REQUIRE(conn_kf[e] != k && seen[conn_kf[e]] != k, ORBHIP_EINVAL, "orbl_update_connections: a table row names itself or a keyframe twice");
+      ORBHIP_REQUIRE(conn_kf[e] != k && seen[conn_kf[e]] != k, ORBHIP_EINVAL, "orbl_update_connections: a row of conn_kf names itself or a keyframe twice");
       seen[conn_kf[e]] = k;
     }
   ThreadWs& W = thread_ws();
   int rc = W.begin();
   if (rc) return rc;
-  ThreadWs::Pack in;
-  const int pT = ntgt ? in.add(tgt_kf, 4 * (size_t)ntgt) : -1, pF = ntgt && tgt_flags ? in.add(tgt_flags, (size_t)ntgt) : -1;
-  const int pSO = ntgt ? in.add(slot_off, 4 * ((size_t)ntgt + 1)) : -1, pSP = nslots ? in.add(slot_pt, 4 * (size_t)nslots) : -1;
-  const int pOO = npts ? in.add(obs_off, 4 * ((size_t)npts + 1)) : -1, pOK = nobs ? in.add(obs_kf, 4 * (size_t)nobs) : -1;
-  const int pB = npts && pt_bad ? in.add(pt_bad, (size_t)npts) : -1, pR = nkf && kf_rank ? in.add(kf_rank, 4 * (size_t)nkf) : -1;
-  const int pCO = nkf ? in.add(conn_off, 4 * ((size_t)nkf + 1)) : -1, pCK = nconn ? in.add(conn_kf, 4 * (size_t)nconn) : -1, pCW = nconn ? in.add(conn_w, 4 * (size_t)nconn) : -1;
-  const int32_t zero_off[1] = {0};
-  const int pPO = prev_off ? in.add(ntgt ? prev_off : zero_off, 4 * ((size_t)ntgt + 1)) : -1, pPK = prev_off ? in.add(prev_kf, 4 * (size_t)nprev) : -1;
-  // outputs in one block: [counts, status | tgt_status | tgt_parent | aff_kf | oconn_off | oord_off | link_off | oconn_kf | oconn_w | oord_kf | oord_w | link_kf]
   const bool links = link_off != nullptr;
-  Carve out;
-  const size_t oC = out.take(32), oS = out.take(4 * (size_t)ntgt), oP = out.take(4 * (size_t)ntgt), oA = out.take(4 * (size_t)cap_aff);
-  const size_t oCO = out.take(4 * ((size_t)cap_aff + 1)), oOO = out.take(4 * ((size_t)cap_aff + 1)), oLO = out.take(links ? 4 * ((size_t)ntgt + 1) : 0);
-  const size_t oCK = out.take(4 * (size_t)cap_conn), oCW = out.take(4 * (size_t)cap_conn), oOK = out.take(4 * (size_t)cap_ord), oOW = out.take(4 * (size_t)cap_ord);
-  const size_t oLK = out.take(links ? 4 * (size_t)cap_link : 0);
-  uint8_t* dblk = W.d<uint8_t>(out.total, &rc);
-  void* dws = W.d<uint8_t>(uc_workspace(ntgt, nkf, nconn).total, &rc);
-  if (rc || (rc = W.commit(in))) return rc;
-  auto at = [&](size_t o) { return (int32_t*)(dblk + o); };
-  if ((rc = orbl_update_connections_device(ntgt, in.dev<int32_t>(pT), in.dev<uint8_t>(pF), nslots, in.dev<int32_t>(pSO), in.dev<int32_t>(pSP), nkf, npts, nobs,
-                                           in.dev<int32_t>(pOO), in.dev<int32_t>(pOK), in.dev<uint8_t>(pB), in.dev<int32_t>(pR), nconn, in.dev<int32_t>(pCO),
-                                           in.dev<int32_t>(pCK), in.dev<int32_t>(pCW), nprev, in.dev<int32_t>(pPO), prev_off ? in.dev<int32_t>(pPK) : nullptr, th,
-                                           cap_aff, cap_conn, cap_ord, links ? cap_link : 0, at(oS), at(oP), at(oA), at(oCO), at(oCK), at(oCW), at(oOO),
-                                           at(oOK), at(oOW), links ? at(oLO) : nullptr, links ? at(oLK) : nullptr, at(oC), (uint32_t*)(dblk + oC + 16), dws, W.s)))
+  const size_t nt = (size_t)ntgt, nk = (size_t)nkf, np = (size_t)npts;
+  RoundTrip R(W);
+  const HostIn<int32_t> d_tgt = R.in(tgt_kf, nt), d_slot_off = R.csr(slot_off, nt), d_slot_pt = R.in(slot_pt, (size_t)nslots), d_rank = R.in(kf_rank, nk);
+  const HostIn<int32_t> d_obs_off = R.csr(obs_off, np), d_obs_kf = R.in(obs_kf, (size_t)nobs), d_prev_off = R.csr(prev_off, nt), d_prev_kf = R.in(prev_kf, (size_t)nprev);
+  const HostIn<int32_t> d_conn_off = R.csr(conn_off, nk), d_conn_kf = R.in(conn_kf, (size_t)nconn), d_conn_w = R.in(conn_w, (size_t)nconn);
+  const HostIn<uint8_t> d_flags = R.in(tgt_flags, nt), d_bad = R.in(pt_bad, np);
+  const HostOut<int32_t> o_counts = R.out<int32_t>(4), o_tgt_status = R.out<int32_t>(nt), o_parent = R.out<int32_t>(nt), o_aff = R.out<int32_t>((size_t)cap_aff);
+  const HostOut<int32_t> o_conn_off = R.out<int32_t>((size_t)cap_aff + 1), o_conn_kf = R.out<int32_t>((size_t)cap_conn), o_conn_w = R.out<int32_t>((size_t)cap_conn);
+  const HostOut<int32_t> o_ord_off = R.out<int32_t>((size_t)cap_aff + 1), o_ord_kf = R.out<int32_t>((size_t)cap_ord), o_ord_w = R.out<int32_t>((size_t)cap_ord);
+  const HostOut<int32_t> o_link_off = R.out<int32_t>(nt + 1, links), o_link_kf = R.out<int32_t>((size_t)cap_link, links);
+  const HostOut<uint32_t> o_status = R.out<uint32_t>(1);
+  R.scratch(uc_workspace(ntgt, nkf, nconn).total);
+  if ((rc = R.commit())) return rc;
+  if ((rc = orbl_update_connections_device(ntgt, d_tgt.dev(), d_flags.dev(), nslots, d_slot_off.dev(), d_slot_pt.dev(), nkf, npts, nobs, d_obs_off.dev(), d_obs_kf.dev(),
+                                           d_bad.dev(), d_rank.dev(), nconn, d_conn_off.dev(), d_conn_kf.dev(), d_conn_w.dev(), nprev, d_prev_off.dev(), d_prev_kf.dev(),
+                                           th, cap_aff, cap_conn, cap_ord, links ? cap_link : 0, o_tgt_status.dev(), o_parent.dev(), o_aff.dev(), o_conn_off.dev(),
+                                           o_conn_kf.dev(), o_conn_w.dev(), o_ord_off.dev(), o_ord_kf.dev(), o_ord_w.dev(), o_link_off.dev(), o_link_kf.dev(),
+                                           o_counts.dev(), o_status.dev(), R.scratch_dev(), R.stream())))
     return rc;
-  const uint8_t* hb = W.down(dblk, out.total, &rc);
-  if (rc || (rc = W.sync())) return rc;
-  const int32_t* hc = (const int32_t*)(hb + oC);
-  std::memcpy(counts, hc, 16);
-  if (hc[0] > cap_aff || hc[1] > cap_conn || hc[2] > cap_ord || (links && hc[3] > cap_link)) {
-    set_error("orbl_update_connections: wanted %d affected keyframes, %d map entries, %d list entries, %d links; capacities %d, %d, %d, %d", hc[0], hc[1], hc[2], hc[3],
-              cap_aff, cap_conn, cap_ord, links ? cap_link : 0);
+  if ((rc = R.finish())) return rc;
+  R.copy_out(o_counts, counts, 4);
+  const size_t n_aff = (size_t)o_counts[0], n_conn = (size_t)o_counts[1], n_ord = (size_t)o_counts[2], n_link = (size_t)o_counts[3];
+  if (n_aff > (size_t)cap_aff || n_conn > (size_t)cap_conn || n_ord > (size_t)cap_ord || (links && n_link > (size_t)cap_link)) {
+    set_error("orbl_update_connections: wanted %d affected keyframes, %d map entries, %d list entries, %d links; capacities %d, %d, %d, %d", o_counts[0], o_counts[1],
+              o_counts[2], o_counts[3], cap_aff, cap_conn, cap_ord, links ? cap_link : 0);
     return ORBHIP_ECAP;
   }
-  const size_t w = 4;
-  if (ntgt) { std::memcpy(tgt_status, hb + oS, w * ntgt); std::memcpy(tgt_parent, hb + oP, w * ntgt); }
-  if (hc[0]) std::memcpy(aff_kf, hb + oA, w * hc[0]);
-  std::memcpy(oconn_off, hb + oCO, w * ((size_t)hc[0] + 1)); std::memcpy(oord_off, hb + oOO, w * ((size_t)hc[0] + 1));
-  if (hc[1]) { std::memcpy(oconn_kf, hb + oCK, w * hc[1]); std::memcpy(oconn_w, hb + oCW, w * hc[1]); }
-  if (hc[2]) { std::memcpy(oord_kf, hb + oOK, w * hc[2]); std::memcpy(oord_w, hb + oOW, w * hc[2]); }
-  if (links) { std::memcpy(link_off, hb + oLO, w * ((size_t)ntgt + 1)); if (hc[3]) std::memcpy(link_kf, hb + oLK, w * hc[3]); }
+  // the lists up to their counts: what lies behind them in the caller's arrays is not touched
+  R.copy_out(o_tgt_status, tgt_status, nt); R.copy_out(o_parent, tgt_parent, nt); R.copy_out(o_aff, aff_kf, n_aff);
+  R.copy_out(o_conn_off, oconn_off, n_aff + 1); R.copy_out(o_ord_off, oord_off, n_aff + 1);
+  R.copy_out(o_conn_kf, oconn_kf, n_conn); R.copy_out(o_conn_w, oconn_w, n_conn); R.copy_out(o_ord_kf, oord_kf, n_ord); R.copy_out(o_ord_w, oord_w, n_ord);
+  R.copy_out(o_link_off, link_off, nt + 1); R.copy_out(o_link_kf, link_kf, n_link);
   return 0;
 }
 
