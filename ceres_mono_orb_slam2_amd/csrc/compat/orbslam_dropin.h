@@ -1908,6 +1908,213 @@ struct FrameOpsT {
     return counts[2];
   }
 
+  // CeresOptimizer::LocalBundleAdjustment, src/CeresOptimizer.cc:344-599, with BOTH halves around the optimisation in the library
+  // (orbl_local_ba_assemble, orbl_local_ba_apply): `FrameOpsHip::LocalBundleAdjustment(current_keyframe_, &is_abort_BA_, map_);` at
+  // src/LocalMapping.cc:89.  AssembleLocalBA flattens the current keyframe, its covisible keyframes, the points in their slots and the
+  // observers of those points (kf_rank / pt_rank = their orders under std::less), and keeps the tables beside the assembled problem;
+  // ApplyLocalBA runs the write-back on those tables and carries the changes into the objects: EraseMapPointMatch on every emptied slot,
+  // the observations, Observations(), the reference keyframe and the bad flag of every point that lost an observation (under
+  // mutex_features_ when the type has it; map_->EraseMapPoint of a point that turned bad stays with the caller), SetPose, SetWorldPos,
+  // normal_vector_ / min_distance_ / max_distance_.  Both return -1, with the map untouched, when the flattened part of the map is not
+  // consistent: keyframe k holds p in slot i iff p's observations contain (k, i).
+  template <class KF, class MP> struct LocalBAProblemT {
+    std::vector<KF*> kfs; std::vector<MP*> pts; KF* current = nullptr;
+    std::vector<double> kf_Tcw, kf_center, X; std::vector<int32_t> slot_off, slot_pt, pt_nobs, pt_ref, obs_off, obs_kf, obs_slot, obs_level, kf_level0;
+    std::vector<uint8_t> pt_bad; std::vector<float> scale_factors;
+    int32_t counts[4] = {0, 0, 0, 0};                                // {ncam, n_local_cam, npts_local, nobs_local}
+    std::vector<int32_t> cam_kf, lpt_pt, lobs_cam, lobs_pt, lobs_src; std::vector<double> K4, poses7, pts3, lobs_uv; std::vector<float> lobs_inv_sigma2;
+    std::vector<uint8_t> cam_fixed, cam_local, kf_role, pt_local;
+  };
+
+  template <class KF, class MP> static int AssembleLocalBA(KF* keyframe, LocalBAProblemT<KF, MP>* P) {
+    typedef typename std::decay<decltype(keyframe->GetPose())>::type M4;
+    *P = LocalBAProblemT<KF, MP>();
+    P->current = keyframe;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*>& kfs = P->kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    kf_index(keyframe);
+    const std::vector<KF*> neighbor_keyframes = keyframe->GetVectorCovisibleKeyFrames();
+    std::vector<int32_t> nbr_kf;
+    for (KF* nb : neighbor_keyframes) nbr_kf.push_back(kf_index(nb));
+    const int n_stamped = (int)kfs.size();
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*>& pts = P->pts;
+    std::vector<float> obs_uv;
+    for (int k = 0; k < n_stamped; k++) {                             // the points in the slots of the local keyframes (":366-384")
+      if (k > 0 && kfs[k]->isBad()) continue;
+      const std::vector<MP*> matches = kfs[k]->GetMapPointMatches();
+      for (MP* mp : matches) {
+        if (!mp || pt_at.count(mp)) continue;
+        pt_at.emplace(mp, (int)pts.size()); pts.push_back(mp);
+        const bool bad = mp->isBad();
+        P->pt_bad.push_back(bad ? 1 : 0);
+        const Vector3d X = mp->GetWorldPos();
+        for (int c = 0; c < 3; c++) P->X.push_back(X[c]);
+        if (!bad) {
+          const auto observations = mp->GetObservations();
+          for (const auto& o : observations) {
+            const auto& kp = o.first->undistort_keypoints_[o.second];
+            P->obs_kf.push_back(kf_index(o.first)); P->obs_slot.push_back((int32_t)o.second); P->obs_level.push_back(kp.octave);
+            obs_uv.push_back(kp.pt.x); obs_uv.push_back(kp.pt.y);
+          }
+        }
+        P->obs_off.push_back((int32_t)P->obs_kf.size());
+        P->pt_nobs.push_back(mp->Observations());
+        KF* rk = mp->GetReferenceKeyFrame();
+        P->pt_ref.push_back(rk ? kf_index(rk) : -1);              // (-1: no reference keyframe; it is compared and never dereferenced)
+      }
+    }
+    P->obs_off.insert(P->obs_off.begin(), 0);
+    const int nkf = (int)kfs.size(), npts = (int)pts.size(), nobs = (int)P->obs_kf.size();
+    std::vector<int32_t> kf_id(nkf), kf_rank(nkf), pt_rank(std::max(npts, 1)), by(nkf);
+    std::vector<uint8_t> kf_bad(nkf);
+    std::vector<double> kf_K4(4 * (size_t)nkf);
+    P->kf_Tcw.resize(12 * (size_t)nkf); P->kf_center.resize(3 * (size_t)nkf); P->kf_level0.resize(nkf); P->slot_off.assign(1, 0);
+    for (int k = 0; k < nkf; k++) {
+      KF* kf = kfs[k];
+      const M4 T = kf->GetPose();
+      const Vector3d O = kf->GetCameraCenter();
+      for (int r = 0; r < 3; r++) { for (int c = 0; c < 4; c++) P->kf_Tcw[12 * (size_t)k + 4 * r + c] = T(r, c); P->kf_center[3 * (size_t)k + r] = O[r]; }
+      kf_id[k] = (int32_t)kf->id_; kf_bad[k] = kf->isBad() ? 1 : 0;
+      kf_K4[4 * (size_t)k] = kf->fx_; kf_K4[4 * (size_t)k + 1] = kf->fy_; kf_K4[4 * (size_t)k + 2] = kf->cx_; kf_K4[4 * (size_t)k + 3] = kf->cy_;
+      P->kf_level0[k] = kf->undistort_keypoints_.empty() ? 0 : kf->undistort_keypoints_[0].octave;
+      const std::vector<MP*> matches = kf->GetMapPointMatches();      // a point the flattening does not know is an empty slot: nothing writes it
+      for (MP* mp : matches) { auto it = mp ? pt_at.find(mp) : pt_at.end(); P->slot_pt.push_back(it == pt_at.end() ? -1 : it->second); }
+      P->slot_off.push_back((int32_t)P->slot_pt.size());
+      by[k] = k;
+    }
+    // consistency of what was flattened: every observation's slot holds its point, every slot's point lists that slot.  A BAD point in
+    // a slot is exempt: between `is_bad_ = true` and the EraseMapPointMatch loop of SetBadFlag (src/MapPoint.cc:179-188) it sits there with
+    // its observations cleared, and the reference, which collects without mutex_map_update_, skips it (":376") and runs.
+    for (int p = 0; p < npts; p++)
+      for (int e = P->obs_off[p]; e < P->obs_off[p + 1]; e++) {
+        const int k = P->obs_kf[e], s = P->obs_slot[e];
+        if (s < 0 || s >= P->slot_off[k + 1] - P->slot_off[k] || P->slot_pt[P->slot_off[k] + s] != p) return -1;
+      }
+    for (int k = 0; k < nkf; k++)
+      for (int s = P->slot_off[k]; s < P->slot_off[k + 1]; s++) {
+        const int p = P->slot_pt[s];
+        if (p < 0 || P->pt_bad[p]) continue;
+        bool listed = false;
+        for (int e = P->obs_off[p]; e < P->obs_off[p + 1] && !listed; e++) listed = P->obs_kf[e] == k && P->obs_slot[e] == s - P->slot_off[k];
+        if (!listed) return -1;
+      }
+    std::sort(by.begin(), by.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nkf; r++) kf_rank[by[r]] = r;
+    std::vector<int32_t> byp(npts);
+    for (int p = 0; p < npts; p++) byp[p] = p;
+    std::sort(byp.begin(), byp.end(), [&](int a, int b) { return std::less<MP*>()(pts[a], pts[b]); });
+    for (int r = 0; r < npts; r++) pt_rank[byp[r]] = r;
+    const int n_levels = keyframe->n_scale_levels_;
+    const std::vector<float> isg(keyframe->inv_level_sigma2s_.begin(), keyframe->inv_level_sigma2s_.begin() + n_levels);
+    P->scale_factors.assign(keyframe->scale_factors_.begin(), keyframe->scale_factors_.begin() + n_levels);
+    const size_t cc = (size_t)nkf, cp = (size_t)std::max(npts, 1), co = (size_t)std::max(nobs, 1);
+    P->cam_kf.resize(cc); P->K4.resize(4 * cc); P->poses7.resize(7 * cc); P->cam_fixed.resize(cc); P->cam_local.resize(cc); P->lpt_pt.resize(cp); P->pts3.resize(3 * cp);
+    P->lobs_cam.resize(co); P->lobs_pt.resize(co); P->lobs_uv.resize(2 * co); P->lobs_inv_sigma2.resize(co); P->lobs_src.resize(co); P->kf_role.resize(cc); P->pt_local.resize(cp);
+    P->X.resize(3 * cp); P->pt_bad.resize(cp); P->pt_nobs.resize(cp); P->pt_ref.resize(cp);
+    P->obs_kf.resize(co); P->obs_slot.resize(co); P->obs_level.resize(co); obs_uv.resize(2 * co);
+    if (P->slot_pt.empty()) P->slot_pt.push_back(-1);
+    if (nbr_kf.empty()) nbr_kf.push_back(0);
+    dropin::check(orbl_local_ba_assemble(0, (int)neighbor_keyframes.size(), nbr_kf.data(), nkf, kf_id.data(), kf_bad.data(), kf_rank.data(), P->kf_Tcw.data(), kf_K4.data(),
+                                         P->slot_off.data(), P->slot_pt.data(), npts, P->X.data(), P->pt_bad.data(), pt_rank.data(), P->obs_off.data(), P->obs_kf.data(),
+                                         obs_uv.data(), P->obs_level.data(), isg.data(), n_levels, nkf, npts, nobs, P->counts, P->cam_kf.data(), P->K4.data(),
+                                         P->poses7.data(), P->cam_fixed.data(), P->cam_local.data(), P->lpt_pt.data(), P->pts3.data(), P->lobs_cam.data(), P->lobs_pt.data(),
+                                         P->lobs_uv.data(), P->lobs_inv_sigma2.data(), P->lobs_src.data(), P->kf_role.data(), P->pt_local.data()),
+                  "orbl_local_ba_assemble");
+    const size_t ncam = (size_t)P->counts[0], npl = (size_t)P->counts[2], nol = (size_t)P->counts[3];
+    P->cam_kf.resize(ncam); P->K4.resize(4 * ncam); P->poses7.resize(7 * ncam); P->cam_fixed.resize(ncam); P->cam_local.resize(ncam); P->lpt_pt.resize(npl); P->pts3.resize(3 * npl);
+    P->lobs_cam.resize(nol); P->lobs_pt.resize(nol); P->lobs_uv.resize(2 * nol); P->lobs_inv_sigma2.resize(nol); P->lobs_src.resize(nol);
+    // the reference's stamps (":351", ":358", ":379", ":399")
+    for (int k = 0; k < nkf; k++) if (P->kf_role[k] == 1 || P->kf_role[k] == 3) kfs[k]->n_BA_local_for_keyframe_ = keyframe->id_;
+    for (size_t j = 0; j < npl; j++) {
+      const int p = P->lpt_pt[j];
+      pts[p]->n_BA_local_for_keyframe_ = keyframe->id_;
+      for (int e = P->obs_off[p]; e < P->obs_off[p + 1]; e++) { const int r = P->kf_role[P->obs_kf[e]]; if (r == 0 || r == 2) kfs[P->obs_kf[e]]->n_BA_fixed_for_keyframe_ = keyframe->id_; }
+    }
+    return (int)nol;
+  }
+
+  // poses7[ncam][7], pts3[npts_local][3], obs_erase[nobs_local]: what ba_local_bundle_adjustment left.  Returns the number of observations erased.
+  // turned_bad (optional): the points this call turned bad, for the caller's map_->EraseMapPoint.
+  template <class KF, class MP> static int ApplyLocalBA(LocalBAProblemT<KF, MP>* P, const double* poses7, const double* pts3, const uint8_t* obs_erase,
+                                                        std::vector<MP*>* turned_bad = nullptr) {
+    typedef typename std::decay<decltype(P->current->GetPose())>::type M4;
+    const int nkf = (int)P->kfs.size(), npts = (int)P->pts.size(), nobs = P->obs_off.back();
+    const int ncam = P->counts[0], npl = P->counts[2], nol = P->counts[3];
+    std::vector<int32_t> slots = P->slot_pt, nobs_after = P->pt_nobs, ref = P->pt_ref;
+    std::vector<uint8_t> bad = P->pt_bad, erased((size_t)std::max(nobs, 1), 0), wrote((size_t)std::max(npts, 1), 0);
+    std::vector<double> Tcw = P->kf_Tcw, center = P->kf_center, X = P->X, normal(3 * (size_t)std::max(npts, 1));
+    std::vector<float> mm(2 * (size_t)std::max(npts, 1));
+    const uint8_t none = 0;
+    int32_t counts[4] = {0, 0, 0, 0};
+    dropin::check(orbl_local_ba_apply(ncam, P->cam_kf.data(), P->cam_local.data(), poses7, npl, P->lpt_pt.data(), pts3, nol, P->lobs_src.data(), nol ? obs_erase : &none, nkf,
+                                      Tcw.data(), center.data(), P->slot_off.data(), slots.data(), npts, X.data(), bad.data(), nobs_after.data(), ref.data(), P->obs_off.data(),
+                                      P->obs_kf.data(), P->obs_slot.data(), P->obs_level.data(), P->kf_level0.data(), P->scale_factors.data(), (int)P->scale_factors.size(),
+                                      erased.data(), normal.data(), mm.data(), wrote.data(), counts),
+                  "orbl_local_ba_apply");
+    for (int k = 0; k < nkf; k++)                                     // (":578", src/MapPoint.cc:187)
+      for (int s = P->slot_off[k]; s < P->slot_off[k + 1]; s++)
+        if (slots[s] < 0 && P->slot_pt[s] >= 0) { const size_t index = (size_t)(s - P->slot_off[k]); P->kfs[k]->EraseMapPointMatch(index); }
+    for (int p = 0; p < npts; p++) {                                  // (":579", src/MapPoint.cc:140-188)
+      bool lost = false;
+      for (int e = P->obs_off[p]; e < P->obs_off[p + 1]; e++) lost = lost || erased[e];
+      if (!lost) continue;
+      MP* mp = P->pts[p];
+      std::unique_lock<std::mutex> lock = lock_features(mp, 0);
+      for (int e = P->obs_off[p]; e < P->obs_off[p + 1]; e++) if (erased[e]) mp->observations_.erase(P->kfs[P->obs_kf[e]]);
+      mp->n_observations_ = nobs_after[p];
+      if (ref[p] >= 0 && ref[p] != P->pt_ref[p]) mp->reference_keyframe_ = P->kfs[ref[p]];
+      if (bad[p] && !P->pt_bad[p]) { mp->is_bad_ = true; if (turned_bad) turned_bad->push_back(mp); }
+    }
+    for (int c = 0; c < ncam; c++) {                                  // (":585-591")
+      if (!P->cam_local[c]) continue;
+      const int k = P->cam_kf[c];
+      M4 T = P->kfs[k]->GetPose();
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = Tcw[12 * (size_t)k + 4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      P->kfs[k]->SetPose(T);
+    }
+    for (int j = 0; j < npl; j++) {                                   // (":593-598")
+      const int p = P->lpt_pt[j];
+      MP* mp = P->pts[p];
+      Vector3d Q, v;
+      for (int c = 0; c < 3; c++) { Q[c] = X[3 * (size_t)p + c]; v[c] = normal[3 * (size_t)p + c]; }
+      mp->SetWorldPos(Q);
+      if (wrote[p]) {
+        std::unique_lock<std::mutex> lock = lock_pose(mp, 0);
+        mp->max_distance_ = mm[2 * (size_t)p + 1]; mp->min_distance_ = mm[2 * (size_t)p]; mp->normal_vector_ = v;
+      }
+    }
+    return counts[0];
+  }
+
+  // 0 when the map was optimised or the stop flag ended the call first (":509-512": the reference returns without writing back), -1 when
+  // the map is not consistent (it is left untouched).  turned_bad (optional): the points the write-back turned bad - SetBadFlag's
+  // map_->EraseMapPoint(this) (src/MapPoint.cc:190) is the caller's: `for (MapPoint* mp : turned_bad) map_->EraseMapPoint(mp);`
+  template <class KF, class MapT, class MP = typename std::remove_pointer<typename std::decay<decltype(std::declval<KF*>()->GetMapPointMatches()[0])>::type>::type>
+  static int LocalBundleAdjustment(KF* keyframe, bool* stop_flag, MapT* map, std::vector<MP*>* turned_bad = nullptr) {
+    LocalBAProblemT<KF, MP> P;
+    if (AssembleLocalBA(keyframe, &P) < 0) return -1;
+    if (stop_flag && *stop_flag) return 0;
+    std::vector<uint8_t> erase(P.lobs_cam.size() ? P.lobs_cam.size() : 1, 0);
+    std::vector<double> poses7 = P.poses7, pts3 = P.pts3;
+    if (pts3.empty()) pts3.resize(3);
+    int aborted = 0;
+    dropin::check(ba_local_bundle_adjustment(P.K4.data(), poses7.data(), P.cam_fixed.data(), P.cam_local.data(), P.counts[0], pts3.data(), P.counts[2], P.lobs_cam.data(),
+                                             P.lobs_pt.data(), P.lobs_uv.data(), P.lobs_inv_sigma2.data(), P.counts[3], reinterpret_cast<const volatile uint8_t*>(stop_flag),
+                                             1, erase.data(), &aborted, nullptr, nullptr),
+                  "ba_local_bundle_adjustment");
+    if (aborted) return 0;
+    std::unique_lock<std::mutex> lock(map->mutex_map_update_);        // (":573")
+    ApplyLocalBA(&P, poses7.data(), pts3.data(), erase.data(), turned_bad);
+    return 0;
+  }
+
  private:
   // the reference's KeyFrame::mutex_connections_ when the type has it
   template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {

@@ -394,3 +394,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_updateconn.inc"
 // LoopClosing::CorrectLoop's pose / point correction and the global-BA write-back (orbl_correct_loop*, orbl_propagate_global_ba*)
 #include "orb_mapcorrect.inc"
+// CeresOptimizer::LocalBundleAdjustment's problem from the map tables and its write-back (orbl_local_ba_assemble*, orbl_local_ba_apply*)
+#include "orb_localba.inc"

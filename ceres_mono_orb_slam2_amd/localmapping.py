@@ -344,3 +344,230 @@ def update_connections_device(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, c
     r.setdefault("link_off", None); r.setdefault("link_kf", None)
     r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
     return r
+
+
+# *d_status bits of orbl_local_ba_assemble_device and orbl_local_ba_apply_device
+LA_OFFSETS, LA_KF, LA_PT, LA_RANK, LA_LEVEL, LA_CAP_CAM, LA_CAP_PTS, LA_CAP_OBS, LA_OBS = 1, 2, 4, 8, 16, 32, 64, 128, 256
+
+_LA_IN = (("kf_id", np.int32), ("kf_bad", np.uint8), ("kf_rank", np.int32), ("kf_Tcw", np.float64), ("kf_K4", np.float64), ("kf_slot_off", np.int32),
+          ("kf_slot_pt", np.int32), ("X", np.float64), ("pt_bad", np.uint8), ("pt_rank", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32),
+          ("obs_uv", np.float32), ("obs_level", np.int32), ("inv_level_sigma2", np.float32))
+# (name, dtype, entries per element, which capacity)
+_LA_OUT = (("cam_kf", np.int32, 1, 0), ("K4", np.float64, 4, 0), ("poses7", np.float64, 7, 0), ("cam_fixed", np.uint8, 1, 0), ("cam_local", np.uint8, 1, 0),
+           ("lpt_pt", np.int32, 1, 1), ("pts3", np.float64, 3, 1), ("lobs_cam", np.int32, 1, 2), ("lobs_pt", np.int32, 1, 2), ("lobs_uv", np.float64, 2, 2),
+           ("lobs_inv_sigma2", np.float32, 1, 2), ("lobs_src", np.int32, 1, 2))
+_LA_SHAPE = dict(K4=(-1, 4), poses7=(-1, 7), pts3=(-1, 3), lobs_uv=(-1, 2))
+_AP_INOUT = (("kf_Tcw", np.float64), ("kf_center", np.float64), ("kf_slot_pt", np.int32), ("X", np.float64), ("pt_bad", np.uint8), ("pt_nobs", np.int32),
+             ("pt_ref_kf", np.int32))
+_AP_IN = (("kf_slot_off", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32), ("obs_slot", np.int32), ("obs_level", np.int32), ("kf_level0", np.int32),
+          ("scale_factors", np.float32))
+
+
+def _flat(a, dt):
+    return None if a is None else _c(a, dt).reshape(-1)
+
+
+def local_ba_assemble(cur_kf, nbr_kf, tab, caps=None, out=None, check=True, device=False, **kw):
+    """The problem of CeresOptimizer::LocalBundleAdjustment from the map tables (orbl_local_ba_assemble; include/orbslam_hip.h states the
+    inputs and the semantics).  tab: dict of the tables kf_id, kf_bad, kf_rank, kf_Tcw [nkf, 12], kf_K4 [nkf, 4], kf_slot_off, kf_slot_pt,
+    X [npts, 3], pt_bad, pt_rank, obs_off, obs_kf, obs_uv [nobs, 2], obs_level, inv_level_sigma2 (kf_bad, kf_rank, pt_bad, pt_rank may be
+    None or missing).  caps = (cap_cam, cap_pts, cap_obs), default (nkf, npts, nobs): bounds no call exceeds.  out: optional dict of preset
+    output arrays of those capacities.  Returns a dict trimmed to the written counts: cam_kf, K4 [ncam, 4], poses7 [ncam, 7], cam_fixed,
+    cam_local, lpt_pt, pts3, lobs_cam, lobs_pt, lobs_uv, lobs_inv_sigma2, lobs_src, kf_role [nkf], pt_local [npts], counts = {ncam,
+    n_local_cam, npts_local, nobs_local} and rc; check=False returns rc = ORBHIP_ECAP with only counts filled instead of raising.
+    device=True: local_ba_assemble_device on torch CUDA tensors."""
+    if device:
+        return local_ba_assemble_device(cur_kf, nbr_kf, tab, caps=caps, out=out, **kw)
+    L = _lib.load()
+    t = {k: _flat(tab.get(k), dt) for k, dt in _LA_IN}
+    nb = _c(nbr_kf, np.int32).reshape(-1)
+    nkf, npts, nobs = len(t["kf_id"]), len(t["X"]) // 3, len(t["obs_kf"])
+    assert len(t["kf_Tcw"]) == 12 * nkf and len(t["kf_K4"]) == 4 * nkf and len(t["kf_slot_off"]) == nkf + 1 and len(t["obs_off"]) == npts + 1
+    assert len(t["obs_uv"]) == 2 * nobs and len(t["obs_level"]) == nobs and nobs >= (t["obs_off"][-1] if npts else 0)
+    assert len(t["kf_slot_pt"]) >= (t["kf_slot_off"][-1] if nkf else 0)                      # (the library checks the rest)
+    for k, n in (("kf_bad", nkf), ("kf_rank", nkf), ("pt_bad", npts), ("pt_rank", npts)):
+        assert t[k] is None or len(t[k]) == n, k
+    cap = (nkf, npts, nobs) if caps is None else tuple(int(c) for c in caps)
+    o = {} if out is None else out
+    for k, dt, w, c in _LA_OUT:
+        o.setdefault(k, np.zeros(w * cap[c], dt))
+        assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * cap[c], k
+    o.setdefault("kf_role", np.zeros(nkf, np.uint8)); o.setdefault("pt_local", np.zeros(npts, np.uint8)); o.setdefault("counts", np.zeros(4, np.int32))
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    rc = L.orbl_local_ba_assemble(int(cur_kf), len(nb), a(nb), nkf, *[a(t[k]) for k in ("kf_id", "kf_bad", "kf_rank", "kf_Tcw", "kf_K4")], _addr(t["kf_slot_off"]),
+                                  a(t["kf_slot_pt"]), npts, a(t["X"]), a(t["pt_bad"]), a(t["pt_rank"]), _addr(t["obs_off"]), a(t["obs_kf"]), a(t["obs_uv"]),
+                                  a(t["obs_level"]), a(t["inv_level_sigma2"]), len(t["inv_level_sigma2"]), cap[0], cap[1], cap[2], _addr(o["counts"]),
+                                  *[a(o[k]) for k, _, _, _ in _LA_OUT], a(o["kf_role"]), a(o["pt_local"]))
+    if rc == ECAP and not check:
+        return dict(rc=rc, counts=o["counts"])
+    _lib.check(rc, "orbl_local_ba_assemble")
+    n = (int(o["counts"][0]), int(o["counts"][2]), int(o["counts"][3]))
+    r = dict(rc=0, counts=o["counts"], kf_role=o["kf_role"], pt_local=o["pt_local"])
+    for k, _, w, c in _LA_OUT:
+        r[k] = o[k][:w * n[c]].reshape(_LA_SHAPE.get(k, (-1,)))
+    return r
+
+
+def local_ba_assemble_device(cur_kf, nbr_kf, tab, caps=None, out=None, workspace=None):
+    """orbl_local_ba_assemble_device on torch CUDA tensors (dtypes as in local_ba_assemble; None where a pointer may be NULL), enqueued on
+    the current stream, nothing synchronised.  Returns a dict of device tensors of FULL capacity - counts[4] holds the wanted sizes,
+    status (uint32 as int32[1]) the LA_* bits - with kf_role, pt_local and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_id"].device
+    n_nbr = nbr_kf.numel() if nbr_kf is not None else 0
+    nkf, npts, nobs, nslots = tab["kf_id"].numel(), tab["X"].numel() // 3, tab["obs_kf"].numel(), tab["kf_slot_pt"].numel()
+    cap = (nkf, npts, nobs) if caps is None else tuple(int(c) for c in caps)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_local_ba_assemble_workspace(nkf, npts, C.byref(nbytes)), "orbl_local_ba_assemble_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    tdt = {np.int32: torch.int32, np.float64: torch.float64, np.float32: torch.float32, np.uint8: torch.uint8}
+    sizes = [(k, tdt[dt], w * cap[c]) for k, dt, w, c in _LA_OUT] + [("kf_role", torch.uint8, nkf), ("pt_local", torch.uint8, npts), ("counts", torch.int32, 4),
+                                                                     ("status", torch.int32, 1)]
+    for k, dt, n in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_local_ba_assemble_device(int(cur_kf), n_nbr, p(nbr_kf), nkf, p(g("kf_id")), p(g("kf_bad")), p(g("kf_rank")), p(g("kf_Tcw")), p(g("kf_K4")), nslots,
+                                               C.c_void_p(tab["kf_slot_off"].data_ptr()), p(g("kf_slot_pt")), npts, p(g("X")), p(g("pt_bad")), p(g("pt_rank")), nobs,
+                                               C.c_void_p(tab["obs_off"].data_ptr()), p(g("obs_kf")), p(g("obs_uv")), p(g("obs_level")), p(g("inv_level_sigma2")),
+                                               tab["inv_level_sigma2"].numel(), cap[0], cap[1], cap[2], p(o["counts"]), *[p(o[k]) for k, _, _, _ in _LA_OUT],
+                                               p(o["kf_role"]), p(o["pt_local"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               "orbl_local_ba_assemble_device")
+    r = dict(o)
+    r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
+    return r
+
+
+def local_ba_apply(asm, poses7, pts3, obs_erase, tab, normals=True, out=None, device=False, **kw):
+    """The write-back of CeresOptimizer::LocalBundleAdjustment on the map tables (orbl_local_ba_apply; include/orbslam_hip.h states the
+    inputs and the semantics).  asm: what local_ba_assemble returned (cam_kf, cam_local, lpt_pt, lobs_src are read); poses7 [ncam, 7],
+    pts3 [npts_local, 3], obs_erase [nobs_local] from optimizer.local_bundle_adjustment.  tab: dict of the tables kf_Tcw, kf_center, kf_slot_off,
+    kf_slot_pt, X, pt_bad, pt_nobs, pt_ref_kf, obs_off, obs_kf, obs_slot, obs_level, kf_level0 (may be None), scale_factors.  normals=False
+    leaves step 4 out.  out: optional dict of preset normal [npts, 3], min_max [npts, 2], nd_written [npts] arrays, of which only the rows of
+    points with a new normal are rewritten (nd_written wholly).  Returns a dict: new copies of kf_Tcw, kf_center, kf_slot_pt, X, pt_bad,
+    pt_nobs, pt_ref_kf; obs_erased [nobs], normal, min_max, nd_written, counts = {n_erased, n_points_turned_bad, n_observations_dead,
+    n_normals_written}.  device=True: local_ba_apply_device on torch CUDA tensors, in place."""
+    if device:
+        return local_ba_apply_device(asm, poses7, pts3, obs_erase, tab, normals=normals, out=out, **kw)
+    L = _lib.load()
+    io = {k: (None if tab.get(k) is None else np.array(tab[k], dtype=dt, order="C").reshape(-1)) for k, dt in _AP_INOUT}       # (always copies)
+    t = {k: _flat(tab.get(k), dt) for k, dt in _AP_IN}
+    ck = _flat(asm["cam_kf"], np.int32); cl = _flat(asm["cam_local"], np.uint8); lp = _flat(asm["lpt_pt"], np.int32); ls = _flat(asm["lobs_src"], np.int32)
+    p7 = _flat(poses7, np.float64); p3 = _flat(pts3, np.float64); er = _flat(obs_erase, np.uint8)
+    ncam, npl, nol = len(ck), len(lp), len(ls)
+    nkf, npts, nobs = len(io["kf_Tcw"]) // 12, len(io["X"]) // 3, len(t["obs_kf"])
+    assert len(cl) == ncam and len(p7) == 7 * ncam and len(p3) == 3 * npl and len(er) >= nol
+    assert len(t["kf_slot_off"]) == nkf + 1 and len(t["obs_off"]) == npts + 1 and len(t["obs_slot"]) == nobs and nobs >= (t["obs_off"][-1] if npts else 0)
+    assert len(io["pt_bad"]) == npts and len(io["pt_nobs"]) == npts and len(io["pt_ref_kf"]) == npts and (io["kf_center"] is None or len(io["kf_center"]) == 3 * nkf)
+    assert len(io["kf_slot_pt"]) >= (t["kf_slot_off"][-1] if nkf else 0)
+    o = {} if out is None else out
+    o["obs_erased"] = np.zeros(nobs, np.uint8); o["counts"] = np.zeros(4, np.int32)
+    if normals:
+        o.setdefault("normal", np.zeros((npts, 3))); o.setdefault("min_max", np.zeros((npts, 2), np.float32)); o.setdefault("nd_written", np.zeros(npts, np.uint8))
+        for k, dt, n in (("normal", np.float64, 3 * npts), ("min_max", np.float32, 2 * npts), ("nd_written", np.uint8, npts)):
+            assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == n, k
+        assert len(t["obs_level"]) == nobs
+    else:
+        o.update(normal=None, min_max=None, nd_written=None)
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    sf = t["scale_factors"] if normals else None
+    _lib.check(L.orbl_local_ba_apply(ncam, a(ck), a(cl), a(p7), npl, a(lp), a(p3), nol, a(ls), a(er), nkf, a(io["kf_Tcw"]), a(io["kf_center"]), _addr(t["kf_slot_off"]),
+                                     a(io["kf_slot_pt"]), npts, a(io["X"]), a(io["pt_bad"]), a(io["pt_nobs"]), a(io["pt_ref_kf"]), _addr(t["obs_off"]), a(t["obs_kf"]),
+                                     a(t["obs_slot"]), a(t["obs_level"]), a(t["kf_level0"]), _addr(sf), len(sf) if sf is not None else 0, a(o["obs_erased"]),
+                                     _addr(o["normal"]), _addr(o["min_max"]), _addr(o["nd_written"]), _addr(o["counts"])), "orbl_local_ba_apply")
+    r = dict(o)
+    r.update(io)
+    r["kf_Tcw"] = io["kf_Tcw"].reshape(-1, 12); r["X"] = io["X"].reshape(-1, 3)
+    if io["kf_center"] is not None:
+        r["kf_center"] = io["kf_center"].reshape(-1, 3)
+    return r
+
+
+def local_ba_apply_device(asm, poses7, pts3, obs_erase, tab, normals=True, out=None, n=None, workspace=None):
+    """orbl_local_ba_apply_device on torch CUDA tensors, enqueued on the current stream, nothing synchronised.  The tables kf_Tcw,
+    kf_center, kf_slot_pt, X, pt_bad, pt_nobs, pt_ref_kf change IN PLACE.  n = (ncam, npts_local, nobs_local) as host integers; default:
+    read from asm["counts"], which waits for the stream.  Returns a dict of device tensors: those tables, obs_erased, normal, min_max,
+    nd_written, counts[4], status (the LA_* bits), and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_Tcw"].device
+    if n is None:
+        c = asm["counts"].cpu().tolist()
+        n = (c[0], c[2], c[3])
+    ncam, npl, nol = (int(v) for v in n)
+    nkf, npts, nobs, nslots = tab["kf_Tcw"].numel() // 12, tab["X"].numel() // 3, tab["obs_kf"].numel(), tab["kf_slot_pt"].numel()
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_local_ba_apply_workspace(nobs, C.byref(nbytes)), "orbl_local_ba_apply_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    sizes = [("obs_erased", torch.uint8, nobs), ("counts", torch.int32, 4), ("status", torch.int32, 1)]
+    if normals:
+        sizes += [("normal", torch.float64, 3 * npts), ("min_max", torch.float32, 2 * npts), ("nd_written", torch.uint8, npts)]
+    for k, dt, m in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    for k, _ in _AP_INOUT:
+        assert g(k) is None or g(k).is_contiguous(), k
+    sf = g("scale_factors") if normals else None
+    _lib.check(L.orbl_local_ba_apply_device(ncam, p(asm["cam_kf"]), p(asm["cam_local"]), p(poses7), npl, p(asm["lpt_pt"]), p(pts3), nol, p(asm["lobs_src"]), p(obs_erase),
+                                            nkf, p(g("kf_Tcw")), p(g("kf_center")), nslots, C.c_void_p(tab["kf_slot_off"].data_ptr()), p(g("kf_slot_pt")), npts, p(g("X")),
+                                            p(g("pt_bad")), p(g("pt_nobs")), p(g("pt_ref_kf")), nobs, C.c_void_p(tab["obs_off"].data_ptr()), p(g("obs_kf")), p(g("obs_slot")),
+                                            p(g("obs_level")), p(g("kf_level0")), None if sf is None else C.c_void_p(sf.data_ptr()), sf.numel() if sf is not None else 0,
+                                            p(o["obs_erased"]), *[None if o.get(k) is None else C.c_void_p(o[k].data_ptr()) for k in ("normal", "min_max", "nd_written")],
+                                            p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_local_ba_apply_device")
+    r = dict(o)
+    for k in ("normal", "min_max", "nd_written"):
+        r.setdefault(k, None)
+    r.update({k: g(k) for k, _ in _AP_INOUT})
+    r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
+    return r
+
+
+def local_bundle_adjustment_on_tables(cur_kf, nbr_kf, tab, stop_flag=None, normals=True, device=False, out=None):
+    """CeresOptimizer::LocalBundleAdjustment on the map tables: local_ba_assemble, optimizer.local_bundle_adjustment on the compact problem
+    (its structure pass is host code: the problem crosses to the host between the two calls), local_ba_apply - which is skipped when the
+    stop flag aborted the solve (src/CeresOptimizer.cc:509-512), so that the tables stay as they are.  tab holds the tables of both calls.
+    Returns dict(aborted, assembled, solved = (poses7, pts3, obs_erase) or None, applied = what local_ba_apply returned or None,
+    summaries)."""
+    from . import optimizer
+    asm = local_ba_assemble(cur_kf, nbr_kf, tab, device=device)
+    if device:
+        c = asm["counts"].cpu().tolist()                         # (waits for the stream: the solver's structure pass reads the problem on the host)
+        n = (c[0], c[2], c[3])
+        w = dict(K4=4, poses7=7, cam_fixed=1, cam_local=1, pts3=3, lobs_cam=1, lobs_pt=1, lobs_uv=2, lobs_inv_sigma2=1)
+        cap = dict(K4=0, poses7=0, cam_fixed=0, cam_local=0, pts3=1, lobs_cam=2, lobs_pt=2, lobs_uv=2, lobs_inv_sigma2=2)
+        h = {k: asm[k][:w[k] * n[cap[k]]].cpu().numpy() for k in w}
+    else:
+        h = asm
+    if stop_flag is not None and stop_flag.reshape(-1)[0]:       # (:509-512)
+        return dict(aborted=1, assembled=asm, solved=None, applied=None, summaries=None)
+    aborted, poses7, pts3, erase, s1, s2 = optimizer.local_bundle_adjustment(h["K4"], np.asarray(h["poses7"]).reshape(-1, 7), h["cam_fixed"], h["cam_local"], h["pts3"],
+                                                                             h["lobs_cam"], h["lobs_pt"], h["lobs_uv"], h["lobs_inv_sigma2"], stop_flag=stop_flag)
+    if aborted:
+        return dict(aborted=aborted, assembled=asm, solved=(poses7, pts3, erase), applied=None, summaries=(s1, s2))
+    if device:
+        import torch
+        dev = tab["kf_Tcw"].device
+        up = [torch.as_tensor(np.ascontiguousarray(v)).to(dev) for v in (poses7, pts3, erase)]
+        applied = local_ba_apply_device(asm, up[0], up[1], up[2], tab, normals=normals, out=out, n=n)
+        applied["_uploads"] = up
+    else:
+        applied = local_ba_apply(asm, poses7, pts3, erase, tab, normals=normals, out=out)
+    return dict(aborted=0, assembled=asm, solved=(poses7, pts3, erase), applied=applied, summaries=(s1, s2))

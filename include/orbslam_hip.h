@@ -699,6 +699,97 @@ int orbl_propagate_global_ba_device(int nkf, double* d_kf_Tcw, double* d_kf_gba_
 /* *bytes = the workspace orbl_propagate_global_ba_device needs (host arithmetic): nkf bytes rounded up to 256, at least 256. */
 int orbl_propagate_global_ba_workspace(int nkf, int npts, size_t* bytes);
 
+/* ---- CeresOptimizer::LocalBundleAdjustment on the map tables, first half (src/CeresOptimizer.cc:346-406 and the flattening :423-506):
+ * the local keyframes, the local map points, the fixed keyframes, and one row per (local point, observing keyframe with a camera), as the
+ * arguments of ba_local_bundle_adjustment.  Keyframes are 0..nkf-1, points 0..npts-1, nkf >= 1.
+ *   cur_kf; nbr_kf[n_nbr] = GetVectorCovisibleKeyFrames() of it (bad ones, repeats and cur_kf itself allowed).
+ *   kf_id[nkf]; kf_bad[nkf] (nullable); kf_rank[nkf] (nullable = index order): a permutation, the position under std::less<KeyFrame*>.
+ *   kf_Tcw[nkf][12]; kf_K4[nkf][4] {fx, fy, cx, cy}, double.   kf_slot_off[nkf + 1] / kf_slot_pt[]: GetMapPointMatches() of EVERY
+ *   keyframe, a point index or -1.   X[npts][3]; pt_bad (nullable); pt_rank[npts] (nullable = index order): std::less<MapPoint*>.
+ *   obs_off[npts + 1] / obs_kf[] in each point's std::map order; obs_uv[nobs][2] (float, the undistorted keypoint); obs_level[nobs];
+ *   inv_level_sigma2[n_levels].
+ * Local keyframes: cur_kf and every nbr_kf that is not bad, each once.  A bad neighbour is still STAMPED local (:358) and so never becomes
+ * fixed.  Local points: not bad, in a slot of a local keyframe.  Fixed keyframes: the observers of a local point that are neither stamped
+ * nor bad.  Cameras: the local keyframes by ascending kf_id (ties: the current one, then nbr_kf order), then the fixed ones by ascending
+ * kf_rank; cam_fixed[c] = fixed || kf_id == 0; cam_local[c]; poses7[c] = ba_matrix4d_to_pose7 of the pose; K4[c].  Points by ascending
+ * pt_rank: lpt_pt[j], pts3[j].  Rows: per local point in that order its list in list order, without the observers that are bad or have no
+ * camera: lobs_cam, lobs_pt, lobs_uv (double, the float widened), lobs_inv_sigma2 = inv_level_sigma2[obs_level], lobs_src = the index e in
+ * the obs_* arrays.  A local point without rows stays in pts3.  kf_role[nkf] (0 none, 1 local, 2 fixed, 3 stamped local but bad) and
+ * pt_local[npts] are written for every element.  counts[4] = {ncam, n_local_cam, npts_local, nobs_local}.
+ * The output lists have the capacities cap_cam, cap_pts, cap_obs (an array may be NULL when its capacity is 0): when a list does not fit
+ * the call returns ORBHIP_ECAP with only counts[] written.  Every place in a list comes from an ordered scan: the outputs are the same
+ * bytes on every run.  Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts,
+ * NULLs, cur_kf, offsets that do not ascend from 0, indices or levels out of range, ranks that are no permutations, n_levels outside
+ * [1, 64]; ORBHIP_ENODEV without a GPU.                                                                                              */
+int orbl_local_ba_assemble(int cur_kf, int n_nbr, const int32_t* nbr_kf, int nkf, const int32_t* kf_id, const uint8_t* kf_bad, const int32_t* kf_rank, const double* kf_Tcw,
+                           const double* kf_K4, const int32_t* kf_slot_off, const int32_t* kf_slot_pt, int npts, const double* X, const uint8_t* pt_bad,
+                           const int32_t* pt_rank, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv, const int32_t* obs_level,
+                           const float* inv_level_sigma2, int n_levels, int cap_cam, int cap_pts, int cap_obs, int32_t* counts, int32_t* cam_kf, double* K4,
+                           double* poses7, uint8_t* cam_fixed, uint8_t* cam_local, int32_t* lpt_pt, double* pts3, int32_t* lobs_cam, int32_t* lobs_pt, double* lobs_uv,
+                           float* lobs_inv_sigma2, int32_t* lobs_src, uint8_t* kf_role, uint8_t* pt_local);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nslots = kf_slot_off[nkf], nobs = obs_off[npts] given by
+ * the caller; cur_kf is a host value and checked on the host).  Counts, NULL pointers and alignment (8 bytes for the 64-bit arrays and the
+ * workspace, 4 for the 32-bit ones) are checked on the host; the data is bounds-checked on the device: an entry out of range counts as
+ * ABSENT - a neighbour that is not there, an empty slot, a keyframe without slots, a point without a list, an observation that gives no
+ * row - and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = a keyframe index, 4 = a point index, 8 = a rank is not a
+ * permutation (of two holders of a place the higher index counts), 16 = a level; a list that does not fit is written up to its capacity,
+ * counts[] holds the wanted sizes and 32 = cameras, 64 = points, 128 = rows is set.
+ * `d_workspace`: at least orbl_local_ba_assemble_workspace(...) bytes, not shared with concurrent calls, reusable by the next.        */
+int orbl_local_ba_assemble_device(int cur_kf, int n_nbr, const int32_t* d_nbr_kf, int nkf, const int32_t* d_kf_id, const uint8_t* d_kf_bad, const int32_t* d_kf_rank,
+                                  const double* d_kf_Tcw, const double* d_kf_K4, int nslots, const int32_t* d_kf_slot_off, const int32_t* d_kf_slot_pt, int npts,
+                                  const double* d_X, const uint8_t* d_pt_bad, const int32_t* d_pt_rank, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                  const float* d_obs_uv, const int32_t* d_obs_level, const float* d_inv_level_sigma2, int n_levels, int cap_cam, int cap_pts,
+                                  int cap_obs, int32_t* d_counts, int32_t* d_cam_kf, double* d_K4, double* d_poses7, uint8_t* d_cam_fixed, uint8_t* d_cam_local,
+                                  int32_t* d_lpt_pt, double* d_pts3, int32_t* d_lobs_cam, int32_t* d_lobs_pt, double* d_lobs_uv, float* d_lobs_inv_sigma2,
+                                  int32_t* d_lobs_src, uint8_t* d_kf_role, uint8_t* d_pt_local, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_local_ba_assemble_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nkf, 4 * nkf,
+ * 4 * npts, 4 * nkf, nkf, 8 * nkf, 8 * (ceil(nkf / 256) + 1), 8 * npts, 8 * (ceil(npts / 256) + 1), 16. */
+int orbl_local_ba_assemble_workspace(int nkf, int npts, size_t* bytes);
+
+/* ---- CeresOptimizer::LocalBundleAdjustment on the map tables, second half (src/CeresOptimizer.cc:573-598), in place on the tables.
+ *   cam_kf[ncam], cam_local[ncam], lpt_pt[npts_local], lobs_src[nobs_local] as assembled; poses7[ncam][7], pts3[npts_local][3] and
+ *   obs_erase[nobs_local] from ba_local_bundle_adjustment.
+ *   IN/OUT: kf_Tcw[nkf][12], kf_center[nkf][3] (nullable unless normals are asked for), kf_slot_pt[], X[npts][3], pt_bad[npts],
+ *   pt_nobs[npts] (= Observations()), pt_ref_kf[npts] (-1 = none: it is compared, and read only for a point that gets a normal).
+ *   IN: kf_slot_off[nkf + 1], obs_off[npts + 1] / obs_kf[], obs_slot[nobs] (the observation's index in its keyframe), obs_level[nobs],
+ *   kf_level0[nkf] (nullable = 0: the octave of keypoint 0), scale_factors[n_levels].
+ * In this order:
+ *  1. for every row i with obs_erase[i], in row order, e = lobs_src[i], k = obs_kf[e], p the point whose list holds e: nothing when e is no
+ *     longer alive (GetIndexInKeyFrame == -1 / count() == 0 after a SetBadFlag); else slot obs_slot[e] of k becomes -1 whatever it held,
+ *     the observation dies, pt_nobs[p]--; if pt_ref_kf[p] == k it becomes the observer of the first alive entry of the list (it stays when
+ *     none is left: the ONE departure, the reference dereferences end() there); if pt_nobs[p] <= 2 the point turns bad and every alive
+ *     observation of it dies with its slot set to -1 (pt_nobs is not reset).  Every observation listed at entry is alive.
+ *  2. every camera with cam_local (kf_id == 0 included): Tcw = [R(q / |q|) | t] with the arithmetic of ba_pose7_to_matrix4d, the centre as
+ *     orbl_correct_loop computes it.
+ *  3. X[lpt_pt[j]] = pts3[j], bad points included.
+ *  4. every local point that is not bad and has an alive observation: normal, min_max, nd_written = 1 as orbl_update_map_points computes
+ *     them from the alive observations in list order, the NEW centres, pt_ref_kf[p] after step 1 and the level of the reference keyframe's
+ *     alive observation - kf_level0[ref] when it has none (std::map::operator[], src/MapPoint.cc:366).  Rows of other points untouched.
+ *   OUT: obs_erased[nobs] (every death of this call; every element written), nd_written[npts] (every element written), counts[4] =
+ *   {n_erased (rows that found their observation alive), n_points_turned_bad, n_observations_dead, n_normals_written}.
+ *   normal, min_max, nd_written and scale_factors are nullable AS A SET: then step 4 is left out (with npts = 0 the three arrays have no
+ *   rows and may be NULL beside a given scale_factors).
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, NULLs, offsets,
+ * indices, slots or levels out of range, a local camera's pose that is not finite or has |q| = 0; ORBHIP_ENODEV without a GPU.        */
+int orbl_local_ba_apply(int ncam, const int32_t* cam_kf, const uint8_t* cam_local, const double* poses7, int npts_local, const int32_t* lpt_pt, const double* pts3,
+                        int nobs_local, const int32_t* lobs_src, const uint8_t* obs_erase, int nkf, double* kf_Tcw, double* kf_center, const int32_t* kf_slot_off,
+                        int32_t* kf_slot_pt, int npts, double* X, uint8_t* pt_bad, int32_t* pt_nobs, int32_t* pt_ref_kf, const int32_t* obs_off, const int32_t* obs_kf,
+                        const int32_t* obs_slot, const int32_t* obs_level, const int32_t* kf_level0, const float* scale_factors, int n_levels, uint8_t* obs_erased,
+                        double* normal, float* min_max, uint8_t* nd_written, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside.  Counts, NULL pointers and alignment are checked on the
+ * host, the data on the device: an entry out of range counts as absent (a row that erases nothing, a slot that is not written, a camera or
+ * point that is not moved, a normal that is not written) and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = a keyframe
+ * index, 4 = a point index, 16 = a level, 256 = lobs_src or obs_slot.
+ * `d_workspace`: at least orbl_local_ba_apply_workspace(...) bytes, not shared with concurrent calls, reusable by the next.            */
+int orbl_local_ba_apply_device(int ncam, const int32_t* d_cam_kf, const uint8_t* d_cam_local, const double* d_poses7, int npts_local, const int32_t* d_lpt_pt,
+                               const double* d_pts3, int nobs_local, const int32_t* d_lobs_src, const uint8_t* d_obs_erase, int nkf, double* d_kf_Tcw,
+                               double* d_kf_center, int nslots, const int32_t* d_kf_slot_off, int32_t* d_kf_slot_pt, int npts, double* d_X, uint8_t* d_pt_bad,
+                               int32_t* d_pt_nobs, int32_t* d_pt_ref_kf, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf, const int32_t* d_obs_slot,
+                               const int32_t* d_obs_level, const int32_t* d_kf_level0, const float* d_scale_factors, int n_levels, uint8_t* d_obs_erased,
+                               double* d_normal, float* d_min_max, uint8_t* d_nd_written, int32_t* d_counts, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_local_ba_apply_device needs (host arithmetic): 4 * nobs bytes rounded up to 256, at least 256. */
+int orbl_local_ba_apply_workspace(int nobs, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
