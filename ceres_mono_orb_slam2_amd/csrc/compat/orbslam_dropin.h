@@ -2115,6 +2115,193 @@ struct FrameOpsT {
     return 0;
   }
 
+  // CeresOptimizer::OptimizeEssentialGraph, src/CeresOptimizer.cc:737-957, with BOTH halves around the optimisation in the library
+  // (orbl_essential_graph_assemble, orbl_essential_graph_apply): `FrameOpsHip::OptimizeEssentialGraph(map_, matched_keyframe_,
+  // current_keyframe_, sophus_non_corrected_sim3, sophus_corrected_sim3, loop_connections);` at src/LoopClosing.cc:573.
+  // AssembleEssentialGraph flattens GetAllKeyFrames() - isBad(), id_, GetPose(), GetParent(), GetChilds(), GetLoopEdges(), and under
+  // mutex_connections_ connected_keyframe_weights_ with the two ordered lists (the friend declaration of INTEGRATION.md section 4) - the
+  // two Sim3 maps and loop_connections; kf_rank is the pointer order.  A keyframe the map does not list (a parent, a child, a link) is
+  // left out, as a keyframe without a parameter block is in CeresOptimizerT::OptimizeEssentialGraph.  ApplyEssentialGraph flattens
+  // GetAllMapPoints() - isBad(), corrected_by_keyframe_, corrected_reference_, GetReferenceKeyFrame(), GetObservations(), the reference
+  // level - runs the write-back on the tables and carries SetPose, SetWorldPos and normal_vector_ / min_distance_ / max_distance_ into
+  // the objects; the caller holds map->mutex_map_update_ (":914"), as OptimizeEssentialGraph below does.  kf_id must be distinct among
+  // the keyframes that are not bad (the library refuses a map where it is not).
+  template <class KF> struct EssentialGraphProblemT {
+    std::vector<KF*> kfs; KF* current = nullptr;
+    int32_t counts[4] = {0, 0, 0, 0};                                // {n_vtx, n_edges, n_loop_connection_edges, n_dropped}
+    std::vector<int32_t> vtx_kf, kf_vtx, edge_j, edge_i; std::vector<double> lie7, edge_Sji; std::vector<uint8_t> vtx_fixed, edge_kind;
+  };
+
+  template <class MapT, class KF, class Sim3T>
+  static int AssembleEssentialGraph(MapT* map, KF* loop_keyframe, KF* current_keyframe, const std::map<KF*, Sim3T>& non_corrected_sim3,
+                                    const std::map<KF*, Sim3T>& corrected_sim3, const std::map<KF*, std::set<KF*> >& loop_connections,
+                                    EssentialGraphProblemT<KF>* P, int min_weight = 100) {
+    typedef typename std::decay<decltype(current_keyframe->GetPose())>::type M4;
+    *P = EssentialGraphProblemT<KF>();
+    P->current = current_keyframe;
+    P->kfs = map->GetAllKeyFrames();
+    const std::vector<KF*>& kfs = P->kfs;
+    const int nkf = (int)kfs.size();
+    if (nkf == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    for (int k = 0; k < nkf; k++) kf_at.emplace(kfs[k], k);
+    auto index_of = [&](KF* kf) { auto it = kf ? kf_at.find(kf) : kf_at.end(); return it == kf_at.end() ? -1 : it->second; };
+    const int loop_index = index_of(loop_keyframe), cur_index = index_of(current_keyframe);
+    if (loop_index < 0 || cur_index < 0) throw std::runtime_error("FrameOpsT::AssembleEssentialGraph: the loop or the current keyframe is not in the map");
+    std::vector<int32_t> kf_id(nkf), kf_rank(nkf), kf_parent(nkf), by(nkf), child_off(1, 0), child_kf, loop_off(1, 0), loop_kf, conn_off(1, 0), conn_kf, conn_w, ord_off(1, 0), ord_kf,
+        ord_w;
+    std::vector<uint8_t> kf_bad(nkf);
+    std::vector<double> Tcw(12 * (size_t)nkf);
+    for (int k = 0; k < nkf; k++) {
+      KF* kf = kfs[k];
+      const M4 T = kf->GetPose();
+      for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c);
+      kf_id[k] = (int32_t)kf->id_; kf_bad[k] = kf->isBad() ? 1 : 0; kf_parent[k] = index_of(kf->GetParent()); by[k] = k;
+      const auto childs = kf->GetChilds();
+      for (KF* c : childs) { const int ci = index_of(c); if (ci >= 0) child_kf.push_back(ci); }
+      child_off.push_back((int32_t)child_kf.size());
+      const auto loop_edges = kf->GetLoopEdges();
+      for (KF* l : loop_edges) { const int li = index_of(l); if (li >= 0) loop_kf.push_back(li); }
+      loop_off.push_back((int32_t)loop_kf.size());
+      {
+        std::unique_lock<std::mutex> lock = lock_connections(kf, 0);
+        for (const auto& w : kf->connected_keyframe_weights_) { const int wi = index_of(w.first); if (wi >= 0) { conn_kf.push_back(wi); conn_w.push_back((int32_t)w.second); } }
+        auto wt = kf->ordered_weights_.begin();
+        for (auto it = kf->ordered_connected_keyframes_.begin(); it != kf->ordered_connected_keyframes_.end(); ++it, ++wt) {
+          ord_kf.push_back(index_of(*it)); ord_w.push_back((int32_t)*wt);                   // (-1 must not leave the list: the prefix rule reads every weight)
+        }
+      }
+      conn_off.push_back((int32_t)conn_kf.size()); ord_off.push_back((int32_t)ord_kf.size());
+    }
+    // an ordered entry the map does not list is a keyframe without a parameter block: the library has no such index, so it is given the
+    // index of a bad keyframe's stand-in - the entry's own keyframe, which no rule admits (a keyframe is never its own covisible)
+    for (int k = 0; k < nkf; k++) for (int e = ord_off[k]; e < ord_off[k + 1]; e++) if (ord_kf[e] < 0) ord_kf[e] = k;
+    std::sort(by.begin(), by.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nkf; r++) kf_rank[by[r]] = r;
+    std::vector<int32_t> group_kf, tgt_kf, link_off(1, 0), link_kf;
+    std::vector<double> corrected, non_corrected;
+    for (const auto& c : corrected_sim3) {
+      const int k = index_of(c.first);
+      auto n = non_corrected_sim3.find(c.first);
+      if (k < 0) continue;
+      if (n == non_corrected_sim3.end()) throw std::runtime_error("FrameOpsT::AssembleEssentialGraph: the two Sim3 maps name different keyframes");
+      group_kf.push_back(k);
+      for (int q = 0; q < 7; q++) { corrected.push_back(c.second.data()[q]); non_corrected.push_back(n->second.data()[q]); }
+    }
+    for (const auto& t : loop_connections) {
+      const int k = index_of(t.first);
+      if (k < 0) continue;
+      tgt_kf.push_back(k);
+      for (KF* l : t.second) { const int li = index_of(l); if (li >= 0) link_kf.push_back(li); }
+      link_off.push_back((int32_t)link_kf.size());
+    }
+    const int nconn = (int)group_kf.size(), ntgt = (int)tgt_kf.size();
+    const size_t cv = (size_t)nkf, ce = link_kf.size() + (size_t)nkf + loop_kf.size() + ord_kf.size() + 1;
+    P->vtx_kf.resize(cv); P->kf_vtx.resize(cv); P->lie7.resize(7 * cv); P->vtx_fixed.resize(cv); P->edge_j.resize(ce); P->edge_i.resize(ce); P->edge_Sji.resize(7 * ce);
+    P->edge_kind.resize(ce);
+    dropin::check(orbl_essential_graph_assemble(nkf, kf_id.data(), kf_bad.data(), kf_rank.data(), Tcw.data(), kf_parent.data(), child_off.data(), child_kf.data(), loop_off.data(),
+                                                loop_kf.data(), conn_off.data(), conn_kf.data(), conn_w.data(), ord_off.data(), ord_kf.data(), ord_w.data(), nconn, group_kf.data(),
+                                                corrected.data(), non_corrected.data(), ntgt, tgt_kf.data(), link_off.data(), link_kf.data(), loop_index, cur_index, min_weight,
+                                                (int)cv, (int)ce, P->counts, P->vtx_kf.data(), P->kf_vtx.data(), P->lie7.data(), P->vtx_fixed.data(), P->edge_j.data(),
+                                                P->edge_i.data(), P->edge_Sji.data(), P->edge_kind.data()),
+                  "orbl_essential_graph_assemble");
+    const size_t nv = (size_t)P->counts[0], ne = (size_t)P->counts[1];
+    P->vtx_kf.resize(nv); P->lie7.resize(7 * nv); P->vtx_fixed.resize(nv); P->edge_j.resize(ne); P->edge_i.resize(ne); P->edge_Sji.resize(7 * ne); P->edge_kind.resize(ne);
+    return (int)ne;
+  }
+
+  // lie_opt[n_vtx][7]: what ba_optimize_essential_graph left.  Returns the number of points moved.
+  template <class MapT, class KF> static int ApplyEssentialGraph(MapT* map, EssentialGraphProblemT<KF>* P, const double* lie_opt) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(map->GetAllMapPoints()[0])>::type>::type MP;
+    typedef typename std::decay<decltype(P->current->GetPose())>::type M4;
+    const int nkf = (int)P->kfs.size(), n_vtx = P->counts[0];
+    if (nkf == 0 || n_vtx == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    std::unordered_map<unsigned long, int> kf_by_id;                   // (corrected_reference_ is a keyframe id: the non-bad keyframe that holds it)
+    for (int k = 0; k < nkf; k++) { kf_at.emplace(P->kfs[k], k); if (P->kf_vtx[k] >= 0) kf_by_id.emplace((unsigned long)P->kfs[k]->id_, k); }
+    const std::vector<MP*> points = map->GetAllMapPoints();
+    const int npts = (int)points.size();
+    const size_t np1 = (size_t)std::max(npts, 1);
+    std::vector<int32_t> pt_ref(np1, -1), pt_corr(np1, -1), ref_level(np1, 0), obs_off(1, 0), obs_kf;
+    std::vector<uint8_t> pt_bad(np1, 0), pt_done(np1, 0), moved(np1, 0), wrote(np1, 0), on_host(np1, 0);
+    std::vector<double> X(3 * np1, 0.0), normal(3 * np1, 0.0);
+    std::vector<float> mm(2 * np1, 0.f);
+    for (int p = 0; p < npts; p++) {
+      MP* mp = points[p];
+      pt_bad[p] = mp->isBad() ? 1 : 0;
+      if (!pt_bad[p]) {
+        const Vector3d Q = mp->GetWorldPos();
+        for (int c = 0; c < 3; c++) X[3 * (size_t)p + c] = Q[c];
+        KF* rk = mp->GetReferenceKeyFrame();
+        auto rit = rk ? kf_at.find(rk) : kf_at.end();
+        pt_ref[p] = rit == kf_at.end() ? -1 : rit->second;
+        if (mp->corrected_by_keyframe_ == P->current->id_) {           // (":942-943")
+          pt_done[p] = 1;
+          auto cit = kf_by_id.find((unsigned long)mp->corrected_reference_);
+          pt_corr[p] = cit == kf_by_id.end() ? -1 : cit->second;
+        }
+        bool all_known = pt_ref[p] >= 0;                               // (what UpdateNormalAndDepth snapshots, src/MapPoint.cc:339-371)
+        const auto observations = mp->GetObservations();
+        size_t kp = 0;
+        const size_t first = obs_kf.size();
+        for (const auto& o : observations) { auto oit = kf_at.find(o.first); if (oit == kf_at.end()) { all_known = false; break; } obs_kf.push_back(oit->second); if (o.first == rk) kp = o.second; }
+        if (!all_known) { obs_kf.resize(first); on_host[p] = 1; }      // (an observer outside the map: the object's own UpdateNormalAndDepth below)
+        else if (!observations.empty()) ref_level[p] = rk->undistort_keypoints_[kp].octave;
+      }
+      obs_off.push_back((int32_t)obs_kf.size());
+    }
+    std::vector<double> Tcw(12 * (size_t)nkf), center(3 * (size_t)nkf);
+    for (int k = 0; k < nkf; k++) {
+      const M4 T = P->kfs[k]->GetPose();
+      const Vector3d O = P->kfs[k]->GetCameraCenter();
+      for (int r = 0; r < 3; r++) { for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c); center[3 * (size_t)k + r] = O[r]; }
+    }
+    const std::vector<float> table(P->current->scale_factors_.begin(), P->current->scale_factors_.begin() + P->current->n_scale_levels_);
+    if (obs_kf.empty()) obs_kf.push_back(0);
+    int32_t counts[2] = {0, 0};
+    dropin::check(orbl_essential_graph_apply(n_vtx, P->vtx_kf.data(), P->lie7.data(), lie_opt, nkf, Tcw.data(), center.data(), npts, X.data(), pt_bad.data(), pt_done.data(),
+                                             pt_corr.data(), pt_ref.data(), obs_off.data(), obs_kf.data(), ref_level.data(), table.data(), (int)table.size(), normal.data(),
+                                             mm.data(), wrote.data(), moved.data(), counts),
+                  "orbl_essential_graph_apply");
+    for (int v = 0; v < n_vtx; v++) {                                 // (":917-933")
+      const int k = P->vtx_kf[v];
+      M4 T = P->kfs[k]->GetPose();
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = Tcw[12 * (size_t)k + 4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      P->kfs[k]->SetPose(T);
+    }
+    for (int p = 0; p < npts; p++) {                                  // (":936-956")
+      if (!moved[p]) continue;
+      MP* mp = points[p];
+      Vector3d Q, v;
+      for (int c = 0; c < 3; c++) { Q[c] = X[3 * (size_t)p + c]; v[c] = normal[3 * (size_t)p + c]; }
+      mp->SetWorldPos(Q);
+      if (wrote[p]) {
+        std::unique_lock<std::mutex> lock = lock_pose(mp, 0);
+        mp->max_distance_ = mm[2 * (size_t)p + 1]; mp->min_distance_ = mm[2 * (size_t)p]; mp->normal_vector_ = v;
+      } else if (on_host[p]) mp->UpdateNormalAndDepth();
+    }
+    return counts[1];
+  }
+
+  // Returns the number of edges of the problem.  summary (optional): the solver's.
+  template <class MapT, class KF, class Sim3T>
+  static int OptimizeEssentialGraph(MapT* map, KF* loop_keyframe, KF* current_keyframe, const std::map<KF*, Sim3T>& non_corrected_sim3,
+                                    const std::map<KF*, Sim3T>& corrected_sim3, const std::map<KF*, std::set<KF*> >& loop_connections) {
+    EssentialGraphProblemT<KF> P;
+    const int n_edges = AssembleEssentialGraph(map, loop_keyframe, current_keyframe, non_corrected_sim3, corrected_sim3, loop_connections, &P);
+    const int n_vtx = P.counts[0];
+    if (n_vtx == 0) return 0;
+    std::vector<double> lie = P.lie7;
+    const int32_t idummy[1] = {0}; const double ddummy[7] = {0, 0, 0, 1, 0, 0, 0};
+    dropin::check(ba_optimize_essential_graph(lie.data(), P.vtx_fixed.data(), n_vtx, n_edges ? P.edge_j.data() : idummy, n_edges ? P.edge_i.data() : idummy,
+                                              n_edges ? P.edge_Sji.data() : ddummy, n_edges, 100, nullptr, nullptr),
+                  "ba_optimize_essential_graph");
+    std::unique_lock<std::mutex> lock(map->mutex_map_update_);        // (":914")
+    ApplyEssentialGraph(map, &P, lie.data());
+    return n_edges;
+  }
+
  private:
   // the reference's KeyFrame::mutex_connections_ when the type has it
   template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {

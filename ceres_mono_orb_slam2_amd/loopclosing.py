@@ -178,3 +178,233 @@ def propagate_global_ba_device(kf_Tcw, kf_gba_Tcw, kf_in_gba, kf_parent, origin_
     r = dict(o)
     r.update(kf_Tcw=kf_Tcw, kf_gba_Tcw=kf_gba_Tcw, kf_in_gba=kf_in_gba, kf_center=kf_center, X=X, _workspace=ws)
     return r
+
+
+# ---------------------------------------------------------------------------------------------- OptimizeEssentialGraph on the tables
+EG_OFFSETS, EG_KF, EG_RANK, EG_LEVEL, EG_CAP_VTX, EG_CAP_EDGES, EG_SIM3 = 1, 2, 8, 16, 32, 64, 512     # *d_status bits of orbl_essential_graph_*_device
+ECAP = -4                            # ORBHIP_ECAP
+_EG_KF = (("kf_id", np.int32), ("kf_bad", np.uint8), ("kf_rank", np.int32), ("kf_Tcw", np.float64), ("kf_parent", np.int32))
+_EG_CSR = (("child_off", "child_kf"), ("loop_off", "loop_kf"), ("conn_off", "conn_kf", "conn_w"), ("ord_off", "ord_kf", "ord_w"))
+_EG_OUT = (("vtx_kf", np.int32, 1, 0), ("lie7", np.float64, 7, 0), ("vtx_fixed", np.uint8, 1, 0), ("edge_j", np.int32, 1, 1), ("edge_i", np.int32, 1, 1),
+           ("edge_Sji", np.float64, 7, 1), ("edge_kind", np.uint8, 1, 1))                                # (name, dtype, width, which capacity)
+_EG_ORDER = ("vtx_kf", "kf_vtx", "lie7", "vtx_fixed", "edge_j", "edge_i", "edge_Sji", "edge_kind")        # (the order of the C arguments)
+_EA_ND = ("obs_off", "obs_kf", "ref_level", "scale_factors")
+
+
+def _flat(a, dt):
+    return None if a is None else _c(a, dt).reshape(-1)
+
+
+def _eg_caps(t, nkf, caps):
+    """(cap_vtx, cap_edges): by default bounds no call exceeds - every keyframe, and every link, parent, loop edge and ordered entry"""
+    if caps is not None:
+        return tuple(int(c) for c in caps)
+    n = lambda k: 0 if t.get(k) is None else (t[k].numel() if hasattr(t[k], "numel") else np.asarray(t[k]).size)
+    return nkf, n("link_kf") + nkf + n("loop_kf") + n("ord_kf")
+
+
+def essential_graph_assemble(loop_kf, cur_kf, tab, min_weight=100, caps=None, out=None, check=True, device=False, **kw):
+    """The problem of CeresOptimizer::OptimizeEssentialGraph from the map tables (orbl_essential_graph_assemble; include/orbslam_hip.h
+    states the inputs and the semantics).  loop_kf, cur_kf: keyframe indices.  tab: dict of the tables kf_id, kf_bad, kf_rank, kf_Tcw
+    [nkf, 12], kf_parent, child_off / child_kf, loop_off / loop_kf, conn_off / conn_kf / conn_w, ord_off / ord_kf / ord_w, the two Sim3 maps
+    conn_group_kf, corrected [nconn, 7], non_corrected [nconn, 7], and loop_connections tgt_kf, link_off / link_kf (kf_bad, kf_rank may be
+    None or missing; so may the group and the targets, as empty).  caps = (cap_vtx, cap_edges), by default bounds no call exceeds.  out:
+    optional dict of preset output arrays of those capacities.  Returns a dict trimmed to the written counts: vtx_kf, kf_vtx [nkf], lie7
+    [n_vtx, 7], vtx_fixed, edge_j, edge_i, edge_Sji [n_edges, 7], edge_kind, counts = {n_vtx, n_edges, n_loop_connection_edges, n_dropped}
+    and rc; check=False returns rc = ORBHIP_ECAP with only counts filled instead of raising.  device=True: essential_graph_assemble_device
+    on torch CUDA tensors."""
+    if device:
+        return essential_graph_assemble_device(loop_kf, cur_kf, tab, min_weight=min_weight, caps=caps, out=out, **kw)
+    L = _lib.load()
+    t = {k: _flat(tab.get(k), dt) for k, dt in _EG_KF}
+    for row in _EG_CSR + (("link_off", "link_kf"),):
+        t.update({k: _flat(tab.get(k), np.int32) for k in row})
+    t.update(conn_group_kf=_flat(tab.get("conn_group_kf"), np.int32), tgt_kf=_flat(tab.get("tgt_kf"), np.int32), corrected=_flat(tab.get("corrected"), np.float64),
+             non_corrected=_flat(tab.get("non_corrected"), np.float64))
+    nkf = len(t["kf_id"])
+    nconn = 0 if t["conn_group_kf"] is None else len(t["conn_group_kf"])
+    ntgt = 0 if t["tgt_kf"] is None else len(t["tgt_kf"])
+    assert len(t["kf_Tcw"]) == 12 * nkf and len(t["kf_parent"]) == nkf and (t["kf_bad"] is None or len(t["kf_bad"]) == nkf) and (t["kf_rank"] is None or len(t["kf_rank"]) == nkf)
+    for row in _EG_CSR:
+        assert len(t[row[0]]) == nkf + 1 and all(len(t[k]) >= (t[row[0]][-1] if nkf else 0) for k in row[1:]), row     # (the library checks the rest)
+    assert nconn == 0 or (len(t["corrected"]) == 7 * nconn and len(t["non_corrected"]) == 7 * nconn)
+    assert ntgt == 0 or (len(t["link_off"]) == ntgt + 1 and (t["link_off"][-1] == 0 or len(t["link_kf"]) >= t["link_off"][-1]))
+    cap = _eg_caps(t, nkf, caps)
+    o = {} if out is None else out
+    for k, dt, w, c in _EG_OUT:
+        o.setdefault(k, np.zeros(w * cap[c], dt))
+        assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * cap[c], k
+    o.setdefault("kf_vtx", np.zeros(nkf, np.int32)); o.setdefault("counts", np.zeros(4, np.int32))
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    rc = L.orbl_essential_graph_assemble(nkf, *[a(t[k]) for k, _ in _EG_KF], *[_addr(t[k]) if k.endswith("_off") else a(t[k]) for row in _EG_CSR for k in row], nconn,
+                                         a(t["conn_group_kf"]), a(t["corrected"]), a(t["non_corrected"]), ntgt, a(t["tgt_kf"]), _addr(t["link_off"]) if ntgt else None,
+                                         a(t["link_kf"]), int(loop_kf), int(cur_kf), int(min_weight), cap[0], cap[1], _addr(o["counts"]), *[a(o[k]) for k in _EG_ORDER])
+    if rc == ECAP and not check:
+        return dict(rc=rc, counts=o["counts"])
+    _lib.check(rc, "orbl_essential_graph_assemble")
+    n = (int(o["counts"][0]), int(o["counts"][1]))
+    r = dict(rc=0, counts=o["counts"], kf_vtx=o["kf_vtx"])
+    for k, _, w, c in _EG_OUT:
+        r[k] = o[k][:w * n[c]].reshape((-1, 7) if w == 7 else (-1,))
+    return r
+
+
+def essential_graph_assemble_device(loop_kf, cur_kf, tab, min_weight=100, caps=None, out=None, workspace=None):
+    """orbl_essential_graph_assemble_device on torch CUDA tensors (dtypes as in essential_graph_assemble; None where a pointer may be NULL),
+    enqueued on the current stream, nothing synchronised.  Returns a dict of device tensors of FULL capacity - counts[4] holds the wanted
+    sizes, status (uint32 as int32[1]) the EG_* bits - with kf_vtx and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_id"].device
+    nkf = tab["kf_id"].numel()
+    n = lambda k: 0 if g(k) is None else g(k).numel()
+    cap = _eg_caps(tab, nkf, caps)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_essential_graph_assemble_workspace(nkf, C.byref(nbytes)), "orbl_essential_graph_assemble_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    tdt = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}
+    sizes = [(k, tdt[dt], w * cap[c]) for k, dt, w, c in _EG_OUT] + [("kf_vtx", torch.int32, nkf), ("counts", torch.int32, 4), ("status", torch.int32, 1)]
+    for k, dt, m in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    csr = []
+    for row in _EG_CSR:
+        csr += [n(row[1]), C.c_void_p(tab[row[0]].data_ptr())] + [p(g(k)) for k in row[1:]]
+    ntgt = n("tgt_kf")
+    _lib.check(L.orbl_essential_graph_assemble_device(nkf, *[p(g(k)) for k, _ in _EG_KF], *csr, n("conn_group_kf"), p(g("conn_group_kf")), p(g("corrected")), p(g("non_corrected")),
+                                                      ntgt, p(g("tgt_kf")), n("link_kf"), C.c_void_p(tab["link_off"].data_ptr()) if ntgt else None, p(g("link_kf")), int(loop_kf),
+                                                      int(cur_kf), int(min_weight), cap[0], cap[1], p(o["counts"]), *[p(o[k]) for k in _EG_ORDER], p(o["status"]), p(ws),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_essential_graph_assemble_device")
+    r = dict(o)
+    r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
+    return r
+
+
+def essential_graph_apply(vtx_kf, lie_orig, lie_opt, tab, normals=True, out=None, device=False, **kw):
+    """The write-back of CeresOptimizer::OptimizeEssentialGraph on the map tables (orbl_essential_graph_apply; include/orbslam_hip.h states
+    the inputs and the semantics).  vtx_kf, lie_orig = lie7 as essential_graph_assemble returned them, lie_opt [n_vtx, 7] from
+    optimizer.optimize_essential_graph.  tab: dict of the tables kf_Tcw, kf_center, X, pt_bad, pt_done, pt_corr_ref, pt_ref_kf and, for the
+    normals, obs_off, obs_kf, ref_level, scale_factors (pt_bad, pt_done / pt_corr_ref may be None or missing).  normals=False leaves step 3
+    out.  out: optional dict of preset normal [npts, 3], min_max [npts, 2], nd_written [npts] arrays, of which only the rows of points with
+    a new normal are rewritten (nd_written wholly).  Returns a dict: new copies of kf_Tcw, kf_center, X; pt_moved [npts], normal, min_max,
+    nd_written, counts = {n_poses_written, n_points_moved}.  device=True: essential_graph_apply_device on torch CUDA tensors, in place."""
+    if device:
+        return essential_graph_apply_device(vtx_kf, lie_orig, lie_opt, tab, normals=normals, out=out, **kw)
+    L = _lib.load()
+    T = _copy(tab["kf_Tcw"], np.float64, (-1, 12)); nkf = len(T)
+    Cn = None if tab.get("kf_center") is None else _copy(tab["kf_center"], np.float64, (-1, 3))
+    Xn = _copy(tab["X"], np.float64, (-1, 3)); npts = len(Xn)
+    vk = _flat(vtx_kf, np.int32); lo = _flat(lie_orig, np.float64); ln = _flat(lie_opt, np.float64); nv = len(vk)
+    pb = _flat(tab.get("pt_bad"), np.uint8); pd = _flat(tab.get("pt_done"), np.uint8); pc = _flat(tab.get("pt_corr_ref"), np.int32); pr = _flat(tab.get("pt_ref_kf"), np.int32)
+    assert len(lo) == 7 * nv and len(ln) == 7 * nv and len(pr) == npts and (Cn is None or len(Cn) == nkf)
+    assert all(v is None or len(v) == npts for v in (pb, pd, pc))
+    o = {} if out is None else out
+    o["pt_moved"] = np.zeros(npts, np.uint8); o["counts"] = np.zeros(2, np.int32)
+    nd = [None] * 4
+    n_levels = 0
+    if normals:
+        nd = [_flat(tab[k], np.float32 if k == "scale_factors" else np.int32) for k in _EA_ND]
+        n_levels = len(nd[3])
+        assert len(nd[0]) == npts + 1 and len(nd[2]) == npts and len(nd[1]) >= (nd[0][-1] if npts else 0)
+        if nd[1].size == 0:
+            nd[1] = np.zeros(1, np.int32)
+        o.setdefault("normal", np.zeros((npts, 3))); o.setdefault("min_max", np.zeros((npts, 2), np.float32)); o.setdefault("nd_written", np.zeros(npts, np.uint8))
+        for k, dt, m in (("normal", np.float64, 3 * npts), ("min_max", np.float32, 2 * npts), ("nd_written", np.uint8, npts)):
+            assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == m, k
+    else:
+        o.update(normal=None, min_max=None, nd_written=None)
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    nda = (lambda x: None if x is None else _addr(x)) if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
+    _lib.check(L.orbl_essential_graph_apply(nv, a(vk), a(lo), a(ln), nkf, a(T), a(Cn), npts, a(Xn), a(pb), a(pd), a(pc), a(pr), *[nda(v) for v in nd], n_levels,
+                                            nda(o["normal"]), nda(o["min_max"]), nda(o["nd_written"]), a(o["pt_moved"]), _addr(o["counts"])), "orbl_essential_graph_apply")
+    r = dict(o)
+    r.update(kf_Tcw=T, kf_center=Cn, X=Xn)
+    return r
+
+
+def essential_graph_apply_device(vtx_kf, lie_orig, lie_opt, tab, normals=True, out=None, workspace=None, n_vtx=None):
+    """orbl_essential_graph_apply_device on torch CUDA tensors, enqueued on the current stream, nothing synchronised.  kf_Tcw, kf_center and
+    X of tab change IN PLACE.  n_vtx: the number of vertices when vtx_kf / lie_orig are the full-capacity tensors of
+    essential_graph_assemble_device.  Returns a dict of device tensors: the three tables, pt_moved, normal / min_max / nd_written,
+    counts[2], status (the EG_* bits), and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_Tcw"].device
+    nkf, npts = tab["kf_Tcw"].numel() // 12, tab["X"].numel() // 3
+    nv = vtx_kf.numel() if n_vtx is None else int(n_vtx)
+    assert vtx_kf.numel() >= nv and lie_orig.numel() >= 7 * nv and lie_opt.numel() >= 7 * nv
+    nobs = g("obs_kf").numel() if (normals and g("obs_kf") is not None) else 0
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_essential_graph_apply_workspace(nkf, nv, C.byref(nbytes)), "orbl_essential_graph_apply_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    sizes = [("pt_moved", torch.uint8, npts), ("counts", torch.int32, 2), ("status", torch.int32, 1)]
+    if normals:
+        sizes += [("normal", torch.float64, 3 * npts), ("min_max", torch.float32, 2 * npts), ("nd_written", torch.uint8, npts)]
+    for k, dt, m in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+    def q(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    for k in ("kf_Tcw", "kf_center", "X"):
+        assert g(k) is None or (g(k).is_contiguous() and g(k).dtype == torch.float64), k
+    nd = [q(g(k)) if (normals and npts) else None for k in _EA_ND]
+    sf = g("scale_factors")
+    _lib.check(L.orbl_essential_graph_apply_device(nv, p(vtx_kf), p(lie_orig), p(lie_opt), nkf, p(g("kf_Tcw")), p(g("kf_center")), npts, p(g("X")), p(g("pt_bad")), p(g("pt_done")),
+                                                   p(g("pt_corr_ref")), p(g("pt_ref_kf")), nobs, nd[0], nd[1] if nobs else None, nd[2], nd[3],
+                                                   sf.numel() if (normals and sf is not None) else 0,
+                                                   *[q(o.get(k)) if (normals and npts) else None for k in ("normal", "min_max", "nd_written")], p(o["pt_moved"]), p(o["counts"]),
+                                                   p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_essential_graph_apply_device")
+    r = dict(o)
+    for k in ("normal", "min_max", "nd_written"):
+        r.setdefault(k, None)
+    r.update(kf_Tcw=g("kf_Tcw"), kf_center=g("kf_center"), X=g("X"), _workspace=ws)
+    return r
+
+
+def optimize_essential_graph_on_tables(loop_kf, cur_kf, tab, min_weight=100, max_iters=100, normals=True, device=False, out=None):
+    """CeresOptimizer::OptimizeEssentialGraph on the map tables: essential_graph_assemble, optimizer.optimize_essential_graph on the
+    compact problem (its structure pass is host code: 7 doubles per vertex and the edge list cross to the host between the two calls),
+    essential_graph_apply.  tab holds the tables of both calls.  Returns dict(assembled, lie_opt [n_vtx, 7], summary, applied)."""
+    from . import optimizer
+    asm = essential_graph_assemble(loop_kf, cur_kf, tab, min_weight=min_weight, device=device)
+    if device:
+        c = asm["counts"].cpu().tolist()                         # (waits for the stream: the solver reads the problem on the host)
+        st = int(asm["status"].item()) & 0xFFFFFFFF
+        if st & (EG_CAP_VTX | EG_CAP_EDGES):
+            raise _lib.OrbHipError("essential_graph_assemble_device: a list did not fit (status %d)" % st)
+        nv, ne = c[0], c[1]
+        h = dict(lie7=asm["lie7"][:7 * nv].cpu().numpy().reshape(-1, 7), vtx_fixed=asm["vtx_fixed"][:nv].cpu().numpy(), edge_j=asm["edge_j"][:ne].cpu().numpy(),
+                 edge_i=asm["edge_i"][:ne].cpu().numpy(), edge_Sji=asm["edge_Sji"][:7 * ne].cpu().numpy().reshape(-1, 7))
+    else:
+        h = asm
+        nv = int(asm["counts"][0])
+    if nv == 0:                                                  # (:795: nothing to optimise, nothing to write back)
+        return dict(assembled=asm, lie_opt=np.zeros((0, 7)), summary=None, applied=None)
+    lie_opt, summary = optimizer.optimize_essential_graph(h["lie7"], h["vtx_fixed"], h["edge_j"], h["edge_i"], h["edge_Sji"], max_iters)
+    if device:
+        import torch
+        up = torch.as_tensor(np.ascontiguousarray(lie_opt)).to(tab["kf_Tcw"].device)
+        applied = essential_graph_apply_device(asm["vtx_kf"], asm["lie7"], up, tab, normals=normals, out=out, n_vtx=nv)
+        applied["_uploads"] = [up]
+    else:
+        applied = essential_graph_apply(asm["vtx_kf"], asm["lie7"], lie_opt, tab, normals=normals, out=out)
+    return dict(assembled=asm, lie_opt=lie_opt, summary=summary, applied=applied)

@@ -790,6 +790,102 @@ int orbl_local_ba_apply_device(int ncam, const int32_t* d_cam_kf, const uint8_t*
 /* *bytes = the workspace orbl_local_ba_apply_device needs (host arithmetic): 4 * nobs bytes rounded up to 256, at least 256. */
 int orbl_local_ba_apply_workspace(int nobs, size_t* bytes);
 
+/* ---- CeresOptimizer::OptimizeEssentialGraph on the map tables, first half (src/CeresOptimizer.cc:769-905; LoopClosing.cc:573): the
+ * vertices with the logarithms of their Sim(3)s and the edge list, as the arguments of ba_optimize_essential_graph.  Keyframes are
+ * 0..nkf-1, nkf >= 1; map points do not enter.
+ *   kf_id[nkf]; kf_bad[nkf] (nullable); kf_rank[nkf] (nullable = index order): a permutation, the position under std::less<KeyFrame*> -
+ *   the order of Map::GetAllKeyFrames(), of loop_connections and of both std::set<KeyFrame*>.   kf_Tcw[nkf][12]; kf_parent[nkf]:
+ *   GetParent() or -1.   child_off[nkf + 1] / child_kf[]: childrens_, read for hasChild only.   loop_off[nkf + 1] / loop_kf[]:
+ *   GetLoopEdges(), rows in any order.   conn_off / conn_kf / conn_w: connected_keyframe_weights_, for GetWeight (0 when absent).
+ *   ord_off[nkf + 1] / ord_kf / ord_w: ordered_connected_keyframes_ / ordered_weights_ (the layouts orbl_update_connections writes).
+ *   nconn (>= 0), conn_group_kf[nconn], corrected[nconn][7], non_corrected[nconn][7]: the two KeyFrameAndSim3 maps as orbl_correct_loop
+ *   returns them.   ntgt, tgt_kf[ntgt], link_off[ntgt + 1] / link_kf[]: loop_connections as orbl_update_connections returns it, rows in
+ *   any order.   loop_keyframe, cur_keyframe: indices;   min_weight (100 at the call site, >= 1).
+ * PRECONDITION: kf_id is distinct among the keyframes that are not bad (inserted_edges is keyed by id pairs; index pairs then say the same).
+ *  1. Vertices: the keyframes that are not bad, numbered densely in ascending kf_rank: vtx_kf[v]; kf_vtx[k] (-1 = none, every element
+ *     written); lie7[v] = log(corrected) for a keyframe of the group, else log(Sim3(RxSO3(1, Rcw), tcw)) with the matrix -> quaternion
+ *     branches of ba_matrix4d_to_pose7; vtx_fixed[v] = (k == loop_keyframe).
+ *  2. Loop-connection edges (:797-821): the targets in ascending kf_rank, each row in ascending kf_rank (a keyframe named twice counts
+ *     once).  Entry (i, j) is skipped when (kf_id[i] != kf_id[cur] || kf_id[j] != kf_id[loop]) && GetWeight(i, j) < min_weight, and when an
+ *     end has no vertex; else Sji = exp(lie[j]) * exp(lie[i])^-1 and the pair joins inserted_edges.
+ *  3. Per keyframe i with a vertex, in ascending kf_rank, W(k) = non_corrected when k is in the group, else exp(lie[k]): the parent
+ *     (:836-854); every loop edge l with kf_id[l] < kf_id[i], in ascending kf_rank (:857-876); of the prefix of the ordered list with
+ *     ord_w >= min_weight - EMPTY when every weight of the list passes (KeyFrame::GetCovisiblesByWeight, src/KeyFrame.cc:218-235) - in list
+ *     order the entries that are not the parent, not a child, not a loop edge, not bad, of smaller kf_id and not in inserted_edges
+ *     (:879-905).  Every edge is Sji = W(j) * W(i)^-1 on (vertex j, vertex i); an edge to a keyframe without a vertex is not added.
+ *   OUT: edge_j, edge_i (vertex numbers), edge_Sji[n_edges][7], edge_kind (0 loop connection, 1 parent, 2 loop edge, 3 covisibility);
+ *   counts[4] = {n_vtx, n_edges, n_loop_connection_edges, n_dropped: entries every other rule admits of which an end has no vertex}.
+ * Capacities cap_vtx, cap_edges (an array may be NULL when its capacity is 0): when a list does not fit the call returns ORBHIP_ECAP with
+ * only counts[] written.  Every place comes from an ordered scan: the outputs are the same bytes on every run.  Host pointers,
+ * synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, NULLs, loop_keyframe /
+ * cur_keyframe, min_weight, offsets that do not ascend from 0, indices out of range, a rank that is no permutation, a keyframe twice in
+ * conn_group_kf or tgt_kf, a corrected / non_corrected row that is not finite or has |q|^2 = 0, kf_id not distinct among the keyframes
+ * that are not bad; ORBHIP_ENODEV without a GPU.                                                                                      */
+int orbl_essential_graph_assemble(int nkf, const int32_t* kf_id, const uint8_t* kf_bad, const int32_t* kf_rank, const double* kf_Tcw, const int32_t* kf_parent,
+                                  const int32_t* child_off, const int32_t* child_kf, const int32_t* loop_off, const int32_t* loop_kf, const int32_t* conn_off,
+                                  const int32_t* conn_kf, const int32_t* conn_w, const int32_t* ord_off, const int32_t* ord_kf, const int32_t* ord_w, int nconn,
+                                  const int32_t* conn_group_kf, const double* corrected, const double* non_corrected, int ntgt, const int32_t* tgt_kf,
+                                  const int32_t* link_off, const int32_t* link_kf, int loop_keyframe, int cur_keyframe, int min_weight, int cap_vtx, int cap_edges,
+                                  int32_t* counts, int32_t* vtx_kf, int32_t* kf_vtx, double* lie7, uint8_t* vtx_fixed, int32_t* edge_j, int32_t* edge_i,
+                                  double* edge_Sji, uint8_t* edge_kind);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (n_child = child_off[nkf], n_loop, n_connw, n_ord, n_link
+ * likewise, given by the caller; loop_keyframe, cur_keyframe and min_weight are host values and checked on the host).  Counts, NULL
+ * pointers and alignment (8 bytes for the 64-bit arrays and the workspace, 4 for the 32-bit ones) are checked on the host; the data is
+ * bounds-checked on the device: an entry out of range counts as ABSENT - a parent, child, loop edge, connection, group member, target or
+ * link that is not there, a row without entries - and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = a keyframe index
+ * (or a keyframe twice in conn_group_kf / tgt_kf: its last instance counts), 8 = kf_rank is not a permutation (of two holders of a place
+ * the higher index counts), 512 = a corrected / non_corrected row that is not finite or has |q|^2 = 0 (the keyframe counts as outside the
+ * group); a list that does not fit is written up to its capacity and not beyond, d_counts holds the wanted sizes and 32 = vertices,
+ * 64 = edges is set.
+ * `d_workspace`: at least orbl_essential_graph_assemble_workspace(...) bytes, not shared with concurrent calls, reusable by the next. */
+int orbl_essential_graph_assemble_device(int nkf, const int32_t* d_kf_id, const uint8_t* d_kf_bad, const int32_t* d_kf_rank, const double* d_kf_Tcw,
+                                         const int32_t* d_kf_parent, int n_child, const int32_t* d_child_off, const int32_t* d_child_kf, int n_loop,
+                                         const int32_t* d_loop_off, const int32_t* d_loop_kf, int n_connw, const int32_t* d_conn_off, const int32_t* d_conn_kf,
+                                         const int32_t* d_conn_w, int n_ord, const int32_t* d_ord_off, const int32_t* d_ord_kf, const int32_t* d_ord_w, int nconn,
+                                         const int32_t* d_conn_group_kf, const double* d_corrected, const double* d_non_corrected, int ntgt, const int32_t* d_tgt_kf,
+                                         int n_link, const int32_t* d_link_off, const int32_t* d_link_kf, int loop_keyframe, int cur_keyframe, int min_weight,
+                                         int cap_vtx, int cap_edges, int32_t* d_counts, int32_t* d_vtx_kf, int32_t* d_kf_vtx, double* d_lie7, uint8_t* d_vtx_fixed,
+                                         int32_t* d_edge_j, int32_t* d_edge_i, double* d_edge_Sji, uint8_t* d_edge_kind, uint32_t* d_status, void* d_workspace,
+                                         void* stream);
+/* *bytes = the workspace orbl_essential_graph_assemble_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nkf,
+ * 4 * nkf, 4 * nkf, 8 * nkf, 8 * (ceil(nkf / 256) + 1), 8 * nkf, 8 * (ceil(nkf / 256) + 1), 56 * nkf, 56 * nkf. */
+int orbl_essential_graph_assemble_workspace(int nkf, size_t* bytes);
+
+/* ---- CeresOptimizer::OptimizeEssentialGraph on the map tables, second half (src/CeresOptimizer.cc:916-956), in place on the tables.
+ *   vtx_kf[n_vtx] as assembled, lie_orig[n_vtx][7] = the assembled lie7, lie_opt[n_vtx][7] from ba_optimize_essential_graph.
+ *   IN/OUT: kf_Tcw[nkf][12], kf_center[nkf][3] (nullable unless normals are asked for), X[npts][3].
+ *   IN: pt_bad (nullable), pt_done[npts] (nullable: corrected_by_keyframe_ == the current keyframe's id), pt_corr_ref[npts] (needed with
+ *   pt_done: the keyframe index orbl_correct_loop returned as pt_owner), pt_ref_kf[npts] (-1 = none); for the normals, nullable AS A SET:
+ *   obs_off[npts + 1] / obs_kf[], ref_level[npts], scale_factors[n_levels], normal, min_max, nd_written.
+ *  1. every vertex keyframe: Tcw = [R | t / s] of exp(lie_opt) (the arithmetic of ba_essential_graph_correct), the centre as
+ *     orbl_correct_loop computes it.
+ *  2. every point that is not bad, r = pt_done ? pt_corr_ref : pt_ref_kf, r holding a vertex v: X <- exp(lie_opt[v])^-1 * (exp(lie_orig[v])
+ *     * X), pt_moved = 1.  A point whose r is -1 or has no vertex stays and gets no normal (the reference would read an uninitialised
+ *     block there).
+ *  3. every moved point with observations: normal, min_max, nd_written = 1 as orbl_update_map_points computes them from the new position,
+ *     pt_ref_kf, ref_level and the NEW centres (every SetPose precedes the point loop).  Rows of other points are untouched.
+ *   OUT: pt_moved[npts] and nd_written[npts] (every element written), counts[2] = {n_poses_written, n_points_moved}.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, NULLs, a keyframe
+ * out of range or twice in vtx_kf, a tangent that is not finite, reference keyframes, observers or levels out of range, n_levels
+ * outside [1, 64]; ORBHIP_ENODEV without a GPU.                                                                                      */
+int orbl_essential_graph_apply(int n_vtx, const int32_t* vtx_kf, const double* lie_orig, const double* lie_opt, int nkf, double* kf_Tcw, double* kf_center, int npts, double* X,
+                               const uint8_t* pt_bad, const uint8_t* pt_done, const int32_t* pt_corr_ref, const int32_t* pt_ref_kf, const int32_t* obs_off,
+                               const int32_t* obs_kf, const int32_t* ref_level, const float* scale_factors, int n_levels, double* normal, float* min_max,
+                               uint8_t* nd_written, uint8_t* pt_moved, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nobs = obs_off[npts]).  Counts, NULL pointers and
+ * alignment are checked on the host, the data on the device: an entry out of range counts as absent (a vertex that writes no pose, a
+ * point that stays, a normal that is not written) and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = a keyframe index
+ * (or a keyframe twice in vtx_kf: its last vertex counts), 16 = a level, 512 = a tangent that is not finite.
+ * `d_workspace`: at least orbl_essential_graph_apply_workspace(...) bytes, not shared with concurrent calls, reusable by the next.    */
+int orbl_essential_graph_apply_device(int n_vtx, const int32_t* d_vtx_kf, const double* d_lie_orig, const double* d_lie_opt, int nkf, double* d_kf_Tcw, double* d_kf_center,
+                                      int npts, double* d_X, const uint8_t* d_pt_bad, const uint8_t* d_pt_done, const int32_t* d_pt_corr_ref, const int32_t* d_pt_ref_kf,
+                                      int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf, const int32_t* d_ref_level, const float* d_scale_factors, int n_levels,
+                                      double* d_normal, float* d_min_max, uint8_t* d_nd_written, uint8_t* d_pt_moved, int32_t* d_counts, uint32_t* d_status,
+                                      void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_essential_graph_apply_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nkf,
+ * 56 * n_vtx, 56 * n_vtx; at least 256. */
+int orbl_essential_graph_apply_workspace(int nkf, int n_vtx, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
