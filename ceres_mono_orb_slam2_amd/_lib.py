@@ -18,6 +18,8 @@ SYMBOLS = [
     "orbl_local_ba_apply", "orbl_local_ba_apply_device", "orbl_local_ba_apply_workspace",
     "orbl_essential_graph_assemble", "orbl_essential_graph_assemble_device", "orbl_essential_graph_assemble_workspace",
     "orbl_essential_graph_apply", "orbl_essential_graph_apply_device", "orbl_essential_graph_apply_workspace",
+    "orbl_global_ba_assemble", "orbl_global_ba_assemble_device", "orbl_global_ba_assemble_workspace",
+    "orbl_global_ba_apply", "orbl_global_ba_apply_device", "orbl_global_ba_apply_workspace",
     "orbt_relocalization_search_by_bow",
     "orbt_initialize", "orbt_initialize_batch_device", "orbt_initialize_workspace",
     "orbt_pnp_ransac_params", "orbt_pnp_iterate", "orbt_pnp_iterate_batch_device", "orbt_pnp_iterate_workspace",
@@ -250,6 +252,12 @@ def load():
     L.orbl_essential_graph_apply.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32] + [vp] * 9 + [i32] + [vp] * 5
     L.orbl_essential_graph_apply_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32] + [vp] * 8
     L.orbl_essential_graph_apply_workspace.argtypes = [i32, i32, C.POINTER(sz)]
+    L.orbl_global_ba_assemble.argtypes = [i32, vp, i32, vp, i32] + [vp] * 4 + [i32] + [vp] * 7 + [i32] * 5 + [vp] * 15
+    L.orbl_global_ba_assemble_device.argtypes = [i32, vp, i32, vp, i32] + [vp] * 4 + [i32, vp, vp, i32] + [vp] * 5 + [i32] * 5 + [vp] * 18
+    L.orbl_global_ba_assemble_workspace.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
+    L.orbl_global_ba_apply.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32] + [vp] * 3 + [i32] + [vp] * 11 + [i32] + [vp] * 4
+    L.orbl_global_ba_apply_device.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32] + [vp] * 3 + [i32] + [vp] * 7 + [i32] + [vp] * 4 + [i32] + [vp] * 7
+    L.orbl_global_ba_apply_workspace.argtypes = [i32, i32, C.POINTER(sz)]
     L.orbt_initialize.argtypes = [vp, i32, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, C.POINTER(InitReport), C.POINTER(InitTrace)]
     L.orbt_initialize_batch_device.argtypes = [i32, vp, vp, i32, vp, vp, i32, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbt_initialize_workspace.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_size_t)]

@@ -2302,6 +2302,180 @@ struct FrameOpsT {
     return n_edges;
   }
 
+  // CeresOptimizer::GlobalBundleAdjustemnt -> BundleAdjustment, src/CeresOptimizer.cc:49-225, with BOTH halves around the optimisation in
+  // the library (orbl_global_ba_assemble, orbl_global_ba_apply): `FrameOpsHip::GlobalBundleAdjustemnt(map_, 10, &is_stop_global_BA_,
+  // n_loop_keyframe, false);` at src/LoopClosing.cc:656 and `FrameOpsHip::GlobalBundleAdjustemnt(map_, 20);` at src/Tracking.cc:502.
+  // AssembleGlobalBA flattens the two lists - isBad(), id_, GetPose(), the intrinsics, GetWorldPos(), GetObservations() in their std::map
+  // order with the undistorted keypoint of each; an observer outside `keyframes` becomes a table row that the list does not name - and
+  // makes the problem CeresOptimizerT::BundleAdjustment makes.  ApplyGlobalBA reads isBad() again, runs the write-back on the tables and
+  // carries it into the objects: SetPose, SetWorldPos, normal_vector_ / min_distance_ / max_distance_ (n_loop_keyframe == 0), or
+  // global_BA_Tcw_ / global_BA_pose_ with n_BA_global_for_keyframe_ (n_loop_keyframe != 0).  As in the reference, no map mutex is taken.
+  template <class KF, class MP> struct GlobalBAProblemT {
+    std::vector<KF*> kfs; std::vector<MP*> pts; std::unordered_map<KF*, int> kf_at;
+    int32_t counts[3] = {0, 0, 0};                                   // {ncam, npts_ba, nobs_ba}
+    std::vector<int32_t> cam_kf, kf_cam, gpt_pt, pt_idx, gobs_cam, gobs_pt, gobs_src; std::vector<double> K4, poses7, pts3, gobs_uv, gobs_weight;
+    std::vector<uint8_t> cam_fixed, gobs_robust; std::vector<float> scale_factors;
+  };
+
+  // Returns the number of rows of the problem.
+  template <class KF, class MP>
+  static int AssembleGlobalBA(const std::vector<KF*>& keyframes, const std::vector<MP*>& map_points, bool is_robust, GlobalBAProblemT<KF, MP>* P) {
+    typedef typename std::decay<decltype(keyframes[0]->GetPose())>::type M4;
+    *P = GlobalBAProblemT<KF, MP>();
+    if (keyframes.empty()) return 0;                                  // (":67-70")
+    std::vector<KF*>& kfs = P->kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = P->kf_at.find(kf);
+      if (it == P->kf_at.end()) { it = P->kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::vector<int32_t> ba_kf, obs_off(1, 0), obs_kf, obs_level;
+    for (KF* kf : keyframes) ba_kf.push_back(kf_index(kf));
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*>& pts = P->pts;
+    std::vector<double> X; std::vector<uint8_t> pt_bad; std::vector<float> obs_uv;
+    for (MP* mp : map_points) {
+      if (!mp || pt_at.count(mp)) continue;                           // (Map hands over a std::set: distinct)
+      pt_at.emplace(mp, (int)pts.size()); pts.push_back(mp);
+      const bool bad = mp->isBad();
+      pt_bad.push_back(bad ? 1 : 0);
+      const Vector3d Q = mp->GetWorldPos();
+      for (int c = 0; c < 3; c++) X.push_back(Q[c]);
+      if (!bad) {
+        const auto observations = mp->GetObservations();
+        for (const auto& o : observations) {
+          const auto& kp = o.first->undistort_keypoints_[o.second];
+          obs_kf.push_back(kf_index(o.first)); obs_level.push_back(kp.octave);
+          obs_uv.push_back(kp.pt.x); obs_uv.push_back(kp.pt.y);
+        }
+      }
+      obs_off.push_back((int32_t)obs_kf.size());
+    }
+    const int nkf = (int)kfs.size(), npts = (int)pts.size(), nobs = (int)obs_kf.size();
+    std::vector<int32_t> kf_id(nkf); std::vector<uint8_t> kf_bad(nkf); std::vector<double> kf_Tcw(12 * (size_t)nkf), kf_K4(4 * (size_t)nkf);
+    for (int k = 0; k < nkf; k++) {
+      KF* kf = kfs[k];
+      const M4 T = kf->GetPose();
+      for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) kf_Tcw[12 * (size_t)k + 4 * r + c] = T(r, c);
+      kf_id[k] = (int32_t)kf->id_; kf_bad[k] = kf->isBad() ? 1 : 0;
+      kf_K4[4 * (size_t)k] = kf->fx_; kf_K4[4 * (size_t)k + 1] = kf->fy_; kf_K4[4 * (size_t)k + 2] = kf->cx_; kf_K4[4 * (size_t)k + 3] = kf->cy_;
+    }
+    KF* first = keyframes[0];
+    const int n_levels = first->n_scale_levels_;
+    const std::vector<float> isg(first->inv_level_sigma2s_.begin(), first->inv_level_sigma2s_.begin() + n_levels);
+    P->scale_factors.assign(first->scale_factors_.begin(), first->scale_factors_.begin() + n_levels);
+    const size_t cc = (size_t)std::min(nkf, (int)ba_kf.size()), cp = (size_t)std::max(npts, 1), co = (size_t)std::max(nobs, 1);
+    P->cam_kf.resize(cc); P->kf_cam.resize(nkf); P->K4.resize(4 * cc); P->poses7.resize(7 * cc); P->cam_fixed.resize(cc); P->gpt_pt.resize(cp); P->pt_idx.resize(cp);
+    P->pts3.resize(3 * cp); P->gobs_cam.resize(co); P->gobs_pt.resize(co); P->gobs_uv.resize(2 * co); P->gobs_weight.resize(co); P->gobs_robust.resize(co); P->gobs_src.resize(co);
+    X.resize(3 * cp); pt_bad.resize(cp); obs_kf.resize(co); obs_level.resize(co); obs_uv.resize(2 * co);
+    dropin::check(orbl_global_ba_assemble((int)ba_kf.size(), ba_kf.data(), npts, nullptr, nkf, kf_id.data(), kf_bad.data(), kf_Tcw.data(), kf_K4.data(), npts, X.data(),
+                                          pt_bad.data(), obs_off.data(), obs_kf.data(), obs_uv.data(), obs_level.data(), isg.data(), n_levels, is_robust ? 1 : 0, (int)cc, npts,
+                                          nobs, P->counts, P->cam_kf.data(), P->kf_cam.data(), P->K4.data(), P->poses7.data(), P->cam_fixed.data(), P->gpt_pt.data(),
+                                          P->pt_idx.data(), P->pts3.data(), P->gobs_cam.data(), P->gobs_pt.data(), P->gobs_uv.data(), P->gobs_weight.data(),
+                                          P->gobs_robust.data(), P->gobs_src.data()),
+                  "orbl_global_ba_assemble");
+    const size_t ncam = (size_t)P->counts[0], npb = (size_t)P->counts[1], nob = (size_t)P->counts[2];
+    P->cam_kf.resize(ncam); P->K4.resize(4 * ncam); P->poses7.resize(7 * ncam); P->cam_fixed.resize(ncam); P->gpt_pt.resize(npb); P->pts3.resize(3 * npb);
+    P->gobs_cam.resize(nob); P->gobs_pt.resize(nob); P->gobs_uv.resize(2 * nob); P->gobs_weight.resize(nob); P->gobs_robust.resize(nob); P->gobs_src.resize(nob);
+    return (int)nob;
+  }
+
+  // poses7[ncam][7], pts3[npts_ba][3]: what ba_solve left.  Returns the number of points written.
+  template <class KF, class MP>
+  static int ApplyGlobalBA(GlobalBAProblemT<KF, MP>* P, const double* poses7, const double* pts3, const unsigned long n_loop_keyframe) {
+    const int nkf = (int)P->kfs.size(), npts = (int)P->pts.size(), ncam = P->counts[0], npb = P->counts[1];
+    if (ncam == 0) return 0;
+    typedef typename std::decay<decltype(P->kfs[0]->GetPose())>::type M4;
+    const int stage = n_loop_keyframe == 0 ? 0 : 1;
+    const size_t np1 = (size_t)std::max(npts, 1);
+    std::vector<uint8_t> kf_bad(nkf), pt_bad(np1, 0), wrote(np1, 0), on_host(np1, 0), kin(nkf, 0), pin(np1, 0);
+    std::vector<double> Tcw(12 * (size_t)nkf), center(3 * (size_t)nkf), X(3 * np1, 0.0), normal(3 * np1, 0.0), gT(12 * (size_t)nkf, 0.0), gX(3 * np1, 0.0);
+    std::vector<int32_t> pt_ref(np1, -1), ref_level(np1, 0), obs_off(1, 0), obs_kf;
+    std::vector<float> mm(2 * np1, 0.f);
+    for (int k = 0; k < nkf; k++) {
+      kf_bad[k] = P->kfs[k]->isBad() ? 1 : 0;                         // (":193": read again)
+      const M4 T = P->kfs[k]->GetPose();
+      const Vector3d O = P->kfs[k]->GetCameraCenter();
+      for (int r = 0; r < 3; r++) { for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c); center[3 * (size_t)k + r] = O[r]; }
+    }
+    for (int p = 0; p < npts; p++) {
+      MP* mp = P->pts[p];
+      pt_bad[p] = mp->isBad() ? 1 : 0;                                // (":214")
+      if (stage == 0 && !pt_bad[p] && P->pt_idx[p] >= 0) {             // (what UpdateNormalAndDepth snapshots, src/MapPoint.cc:339-371)
+        const Vector3d Q = mp->GetWorldPos();
+        for (int c = 0; c < 3; c++) X[3 * (size_t)p + c] = Q[c];
+        KF* rk = mp->GetReferenceKeyFrame();
+        auto rit = rk ? P->kf_at.find(rk) : P->kf_at.end();
+        pt_ref[p] = rit == P->kf_at.end() ? -1 : rit->second;
+        bool all_known = pt_ref[p] >= 0;
+        const auto observations = mp->GetObservations();
+        size_t kp = 0;
+        const size_t first = obs_kf.size();
+        for (const auto& o : observations) { auto oit = P->kf_at.find(o.first); if (oit == P->kf_at.end()) { all_known = false; break; } obs_kf.push_back(oit->second); if (o.first == rk) kp = o.second; }
+        if (!all_known) { obs_kf.resize(first); pt_ref[p] = -1; on_host[p] = rk ? 1 : 0; }      // (an observer the flattening does not know: the object's own UpdateNormalAndDepth below)
+        else if (!observations.empty()) ref_level[p] = rk->undistort_keypoints_[kp].octave;
+      }
+      obs_off.push_back((int32_t)obs_kf.size());
+    }
+    if (obs_kf.empty()) obs_kf.push_back(0);
+    int32_t counts[3] = {0, 0, 0};
+    const bool s0 = stage == 0;
+    dropin::check(orbl_global_ba_apply(ncam, P->cam_kf.data(), poses7, npb, P->gpt_pt.data(), pts3, stage, nkf, kf_bad.data(), s0 ? Tcw.data() : nullptr,
+                                       s0 ? center.data() : nullptr, npts, s0 ? X.data() : nullptr, pt_bad.data(), s0 ? nullptr : gT.data(), s0 ? nullptr : kin.data(),
+                                       s0 ? nullptr : gX.data(), s0 ? nullptr : pin.data(), s0 ? pt_ref.data() : nullptr, s0 ? obs_off.data() : nullptr,
+                                       s0 ? obs_kf.data() : nullptr, s0 ? ref_level.data() : nullptr, s0 ? P->scale_factors.data() : nullptr, (int)P->scale_factors.size(),
+                                       s0 ? normal.data() : nullptr, s0 ? mm.data() : nullptr, s0 ? wrote.data() : nullptr, counts),
+                  "orbl_global_ba_apply");
+    for (int c = 0; c < ncam; c++) {                                  // (":190-205")
+      const int k = P->cam_kf[c];
+      if (kf_bad[k]) continue;
+      M4 T = P->kfs[k]->GetPose();
+      const double* src = (s0 ? Tcw.data() : gT.data()) + 12 * (size_t)k;
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = src[4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      if (s0) P->kfs[k]->SetPose(T);
+      else { P->kfs[k]->global_BA_Tcw_ = T; P->kfs[k]->n_BA_global_for_keyframe_ = n_loop_keyframe; }
+    }
+    for (int j = 0; j < npb; j++) {                                   // (":208-224")
+      const int p = P->gpt_pt[j];
+      if (pt_bad[p]) continue;
+      MP* mp = P->pts[p];
+      Vector3d Q, v;
+      const double* src = (s0 ? X.data() : gX.data()) + 3 * (size_t)p;
+      for (int c = 0; c < 3; c++) { Q[c] = src[c]; v[c] = normal[3 * (size_t)p + c]; }
+      if (!s0) { mp->global_BA_pose_ = Q; mp->n_BA_global_for_keyframe_ = n_loop_keyframe; continue; }
+      mp->SetWorldPos(Q);
+      if (wrote[p]) {
+        std::unique_lock<std::mutex> lock = lock_pose(mp, 0);
+        mp->max_distance_ = mm[2 * (size_t)p + 1]; mp->min_distance_ = mm[2 * (size_t)p]; mp->normal_vector_ = v;
+      } else if (on_host[p]) mp->UpdateNormalAndDepth();
+    }
+    return counts[1];
+  }
+
+  // Returns the number of rows of the problem (0: nothing to optimise, nothing written).  The write-back also runs after a raised stop
+  // flag, as in the reference; RunGlobalBundleAdjustment decides afterwards whether to propagate.
+  template <class MapT>
+  static int GlobalBundleAdjustemnt(MapT* map, int n_iterations = 200, bool* stop_flag = nullptr, const unsigned long n_loop_keyframe = 0, const bool is_robust = true) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(map->GetAllKeyFrames()[0])>::type>::type KF;
+    typedef typename std::remove_pointer<typename std::decay<decltype(map->GetAllMapPoints()[0])>::type>::type MP;
+    const std::vector<KF*> keyframes = map->GetAllKeyFrames();
+    const std::vector<MP*> map_points = map->GetAllMapPoints();
+    GlobalBAProblemT<KF, MP> P;
+    const int nob = AssembleGlobalBA(keyframes, map_points, is_robust, &P);
+    if (P.counts[0] == 0) return 0;
+    std::vector<double> poses7 = P.poses7, pts3 = P.pts3;
+    if (nob > 0) {
+      ba_options o; o.max_iterations = n_iterations; o.huber_delta = std::sqrt(5.991); o.fix_points = 0;
+      o.stop_flag = reinterpret_cast<const volatile uint8_t*>(stop_flag);
+      dropin::check(ba_solve(P.K4.data(), poses7.data(), P.cam_fixed.data(), P.counts[0], pts3.data(), P.counts[1], P.gobs_cam.data(), P.gobs_pt.data(), P.gobs_uv.data(),
+                             P.gobs_weight.data(), P.gobs_robust.data(), nob, &o, nullptr),
+                    "ba_solve");
+    }
+    ApplyGlobalBA(&P, poses7.data(), pts3.data(), n_loop_keyframe);
+    return nob;
+  }
+
  private:
   // the reference's KeyFrame::mutex_connections_ when the type has it
   template <class P> static auto lock_connections(P* p, int) -> decltype((void)p->mutex_connections_, std::unique_lock<std::mutex>()) {

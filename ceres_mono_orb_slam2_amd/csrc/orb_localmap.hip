@@ -398,3 +398,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_localba.inc"
 // CeresOptimizer::OptimizeEssentialGraph's problem from the map tables and its write-back (orbl_essential_graph_assemble*, orbl_essential_graph_apply*)
 #include "orb_essgraph.inc"
+// CeresOptimizer::BundleAdjustment's (GlobalBundleAdjustemnt) problem from the map tables and its write-back (orbl_global_ba_assemble*, orbl_global_ba_apply*)
+#include "orb_globalba.inc"

@@ -408,3 +408,246 @@ def optimize_essential_graph_on_tables(loop_kf, cur_kf, tab, min_weight=100, max
     else:
         applied = essential_graph_apply(asm["vtx_kf"], asm["lie7"], lie_opt, tab, normals=normals, out=out)
     return dict(assembled=asm, lie_opt=lie_opt, summary=summary, applied=applied)
+
+
+# ---- CeresOptimizer::GlobalBundleAdjustemnt on the map tables (orbl_global_ba_assemble*, orbl_global_ba_apply*) ------------------------
+GA_OFFSETS, GA_KF, GA_PT, GA_LEVEL, GA_CAP_CAM, GA_CAP_PTS, GA_CAP_OBS, GA_REPEAT, GA_POSE = 1, 2, 4, 16, 32, 64, 128, 1024, 2048    # *d_status bits
+_GA_KF = (("kf_id", np.int32), ("kf_bad", np.uint8), ("kf_Tcw", np.float64), ("kf_K4", np.float64))
+_GA_PT = (("X", np.float64), ("pt_bad", np.uint8), ("obs_off", np.int32), ("obs_kf", np.int32), ("obs_uv", np.float32), ("obs_level", np.int32),
+          ("inv_level_sigma2", np.float32))
+# (name, dtype, entries per place, which capacity) in the order of the C arguments; kf_cam [nkf] and pt_idx [npts] stand between them
+_GA_OUT = (("cam_kf", np.int32, 1, 0), ("kf_cam", np.int32, 1, -1), ("K4", np.float64, 4, 0), ("poses7", np.float64, 7, 0), ("cam_fixed", np.uint8, 1, 0),
+           ("gpt_pt", np.int32, 1, 1), ("pt_idx", np.int32, 1, -2), ("pts3", np.float64, 3, 1), ("gobs_cam", np.int32, 1, 2), ("gobs_pt", np.int32, 1, 2),
+           ("gobs_uv", np.float64, 2, 2), ("gobs_weight", np.float64, 1, 2), ("gobs_robust", np.uint8, 1, 2), ("gobs_src", np.int32, 1, 2))
+_GP_ND = ("pt_ref_kf", "obs_off", "obs_kf", "ref_level", "scale_factors")
+_GP_ND_DT = (np.int32, np.int32, np.int32, np.int32, np.float32)
+
+
+def _numel(a):
+    return 0 if a is None else (a.numel() if hasattr(a, "numel") else np.asarray(a).size)
+
+
+def _ga_sizes(tab, ba_kf, ba_pt, caps):
+    nkf, npts, nobs = _numel(tab["kf_id"]), _numel(tab["X"]) // 3, _numel(tab.get("obs_kf"))
+    nbk, nbp = (nkf if ba_kf is None else _numel(ba_kf)), (npts if ba_pt is None else _numel(ba_pt))
+    # by default bounds no call exceeds: every list entry a camera, every listed point, every observation
+    cap = (min(nbk, nkf), min(nbp, npts), nobs) if caps is None else tuple(int(c) for c in caps)
+    return nkf, npts, nobs, nbk, nbp, cap
+
+
+def global_ba_assemble(tab, ba_kf=None, ba_pt=None, is_robust=True, caps=None, out=None, check=True, device=False, **kw):
+    """The arguments of ba_solve for CeresOptimizer::GlobalBundleAdjustemnt from the map tables (orbl_global_ba_assemble;
+    include/orbslam_hip.h states the inputs and the semantics).  ba_kf, ba_pt: the keyframe and point lists, None = all.  tab: dict of the
+    tables kf_id, kf_bad, kf_Tcw [nkf, 12], kf_K4 [nkf, 4], X [npts, 3], pt_bad, obs_off / obs_kf / obs_uv / obs_level, inv_level_sigma2
+    (kf_bad, pt_bad may be None or missing).  caps = (cap_cam, cap_pts, cap_obs), by default bounds no call exceeds.  out: optional dict of
+    preset output arrays of those capacities.  Returns a dict trimmed to the written counts: cam_kf, kf_cam [nkf], K4, poses7, cam_fixed,
+    gpt_pt, pt_idx [npts], pts3, gobs_cam, gobs_pt, gobs_uv, gobs_weight, gobs_robust, gobs_src, counts = {ncam, npts_ba, nobs_ba} and rc;
+    check=False returns rc = ORBHIP_ECAP with only counts filled instead of raising.  device=True: global_ba_assemble_device."""
+    if device:
+        return global_ba_assemble_device(tab, ba_kf=ba_kf, ba_pt=ba_pt, is_robust=is_robust, caps=caps, out=out, **kw)
+    L = _lib.load()
+    t = {k: _flat(tab.get(k), dt) for k, dt in _GA_KF + _GA_PT}
+    bk, bp = _flat(ba_kf, np.int32), _flat(ba_pt, np.int32)
+    nkf, npts, nobs, nbk, nbp, cap = _ga_sizes(t, bk, bp, caps)
+    assert len(t["kf_Tcw"]) == 12 * nkf and len(t["kf_K4"]) == 4 * nkf and len(t["obs_off"]) == npts + 1
+    assert all(t[k] is None or len(t[k]) == n for k, n in (("kf_bad", nkf), ("pt_bad", npts)))
+    assert nobs >= (t["obs_off"][-1] if npts else 0) and len(t["obs_uv"]) == 2 * nobs and len(t["obs_level"]) == nobs
+    o = {} if out is None else out
+    dims = {-1: nkf, -2: npts, 0: cap[0], 1: cap[1], 2: cap[2]}
+    for k, dt, w, c in _GA_OUT:
+        o.setdefault(k, np.zeros(w * dims[c], dt))
+        assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * dims[c], k
+    o.setdefault("counts", np.zeros(3, np.int32))
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    rc = L.orbl_global_ba_assemble(nbk, a(bk), nbp, a(bp), nkf, *[a(t[k]) for k, _ in _GA_KF], npts, *[a(t[k]) for k, _ in _GA_PT], len(t["inv_level_sigma2"]),
+                                   int(bool(is_robust)), cap[0], cap[1], cap[2], _addr(o["counts"]), *[a(o[k]) for k, _, _, _ in _GA_OUT])
+    if rc == ECAP and not check:
+        return dict(rc=rc, counts=o["counts"])
+    _lib.check(rc, "orbl_global_ba_assemble")
+    n = {-1: nkf, -2: npts, 0: int(o["counts"][0]), 1: int(o["counts"][1]), 2: int(o["counts"][2])}
+    r = dict(rc=0, counts=o["counts"])
+    for k, _, w, c in _GA_OUT:
+        r[k] = o[k][:w * n[c]].reshape((-1, w) if w > 1 else (-1,))
+    return r
+
+
+def global_ba_assemble_device(tab, ba_kf=None, ba_pt=None, is_robust=True, caps=None, out=None, workspace=None):
+    """orbl_global_ba_assemble_device on torch CUDA tensors (dtypes as in global_ba_assemble; None where a pointer may be NULL), enqueued on
+    the current stream, nothing synchronised.  Returns a dict of device tensors of FULL capacity - counts[3] holds the wanted sizes, status
+    (uint32 as int32[1]) the GA_* bits - with kf_cam, pt_idx and the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_id"].device
+    nkf, npts, nobs, nbk, nbp, cap = _ga_sizes(tab, ba_kf, ba_pt, caps)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_global_ba_assemble_workspace(nkf, npts, nbk, nbp, C.byref(nbytes)), "orbl_global_ba_assemble_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    tdt = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}
+    dims = {-1: nkf, -2: npts, 0: cap[0], 1: cap[1], 2: cap[2]}
+    sizes = [(k, tdt[dt], w * dims[c]) for k, dt, w, c in _GA_OUT] + [("counts", torch.int32, 3), ("status", torch.int32, 1)]
+    for k, dt, m in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_global_ba_assemble_device(nbk, p(ba_kf), nbp, p(ba_pt), nkf, *[p(g(k)) for k, _ in _GA_KF], npts, p(g("X")), p(g("pt_bad")), nobs,
+                                                *[p(g(k)) for k, _ in _GA_PT[2:]], g("inv_level_sigma2").numel(), int(bool(is_robust)), cap[0], cap[1], cap[2],
+                                                p(o["counts"]), *[p(o[k]) for k, _, _, _ in _GA_OUT], p(o["status"]), p(ws),
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_global_ba_assemble_device")
+    r = dict(o)
+    r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
+    return r
+
+
+def global_ba_apply(cam_kf, gpt_pt, poses7, pts3, tab, stage=0, normals=True, out=None, device=False, **kw):
+    """The write-back of CeresOptimizer::BundleAdjustment on the map tables (orbl_global_ba_apply; include/orbslam_hip.h states the inputs
+    and the semantics).  cam_kf, gpt_pt as global_ba_assemble returned them, poses7 [ncam, 7] and pts3 [npts_ba, 3] from
+    optimizer.bundle_adjustment.  tab: kf_bad, pt_bad (None or missing allowed) and, stage 0: kf_Tcw, kf_center, X and for the normals
+    pt_ref_kf, obs_off, obs_kf, ref_level, scale_factors; stage 1: optional kf_gba_Tcw [nkf, 12], pt_gba_X [npts, 3] whose unwritten rows
+    are kept (zeros otherwise; nkf and npts are taken from kf_Tcw and X).  normals=False leaves step 3 out.  out: optional dict of preset
+    normal [npts, 3], min_max [npts, 2], nd_written [npts].  Returns a dict of new copies: stage 0 kf_Tcw, kf_center, X, normal, min_max,
+    nd_written; stage 1 kf_gba_Tcw, kf_in_gba, pt_gba_X, pt_in_gba; counts = {n_poses_written, n_points_written, n_normals_written}.
+    device=True: global_ba_apply_device on torch CUDA tensors, in place."""
+    if device:
+        return global_ba_apply_device(cam_kf, gpt_pt, poses7, pts3, tab, stage=stage, normals=normals, out=out, **kw)
+    L = _lib.load()
+    nkf, npts = np.asarray(tab["kf_Tcw"]).size // 12, np.asarray(tab["X"]).size // 3
+    ck, gp = _flat(cam_kf, np.int32), _flat(gpt_pt, np.int32)
+    p7, p3 = _flat(poses7, np.float64), _flat(pts3, np.float64)
+    assert len(p7) == 7 * len(ck) and len(p3) == 3 * len(gp)
+    kb, pb = _flat(tab.get("kf_bad"), np.uint8), _flat(tab.get("pt_bad"), np.uint8)
+    assert (kb is None or len(kb) == nkf) and (pb is None or len(pb) == npts)
+    o = {} if out is None else out
+    o["counts"] = np.zeros(3, np.int32)
+    T = Cn = Xn = gT = gX = kin = pin = None
+    nd, ndo, n_levels = [None] * 5, [None] * 3, 0
+    if stage == 0:
+        T = _copy(tab["kf_Tcw"], np.float64, (-1, 12)); Xn = _copy(tab["X"], np.float64, (-1, 3))
+        Cn = None if tab.get("kf_center") is None else _copy(tab["kf_center"], np.float64, (-1, 3))
+        if normals:
+            nd = [_flat(tab[k], dt) for k, dt in zip(_GP_ND, _GP_ND_DT)]
+            n_levels = len(nd[4])
+            assert len(nd[0]) == npts and len(nd[1]) == npts + 1 and len(nd[3]) == npts and len(nd[2]) >= (nd[1][-1] if npts else 0)
+            if nd[2].size == 0:
+                nd[2] = np.zeros(1, np.int32)
+            o.setdefault("normal", np.zeros((npts, 3))); o.setdefault("min_max", np.zeros((npts, 2), np.float32)); o.setdefault("nd_written", np.zeros(npts, np.uint8))
+            for k, dt, m in (("normal", np.float64, 3 * npts), ("min_max", np.float32, 2 * npts), ("nd_written", np.uint8, npts)):
+                assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == m, k
+            ndo = [o["normal"], o["min_max"], o["nd_written"]]
+        else:
+            o.update(normal=None, min_max=None, nd_written=None)
+    else:
+        gT = np.zeros((nkf, 12)) if tab.get("kf_gba_Tcw") is None else _copy(tab["kf_gba_Tcw"], np.float64, (-1, 12))
+        gX = np.zeros((npts, 3)) if tab.get("pt_gba_X") is None else _copy(tab["pt_gba_X"], np.float64, (-1, 3))
+        kin, pin = np.zeros(nkf, np.uint8), np.zeros(npts, np.uint8)
+        assert len(gT) == nkf and len(gX) == npts
+
+    def a(x):
+        return None if x is None or x.size == 0 else _addr(x)
+    nda = (lambda x: None if x is None else _addr(x)) if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
+    _lib.check(L.orbl_global_ba_apply(len(ck), a(ck), a(p7), len(gp), a(gp), a(p3), int(stage), nkf, a(kb), a(T), a(Cn), npts, a(Xn), a(pb), a(gT), a(kin), a(gX), a(pin),
+                                      *[nda(v) for v in nd], n_levels, *[nda(v) for v in ndo], _addr(o["counts"])), "orbl_global_ba_apply")
+    r = dict(o)
+    if stage == 0:
+        r.update(kf_Tcw=T, kf_center=Cn, X=Xn)
+    else:
+        r.update(kf_gba_Tcw=gT, kf_in_gba=kin, pt_gba_X=gX, pt_in_gba=pin)
+    return r
+
+
+def global_ba_apply_device(cam_kf, gpt_pt, poses7, pts3, tab, stage=0, normals=True, out=None, workspace=None, n=None):
+    """orbl_global_ba_apply_device on torch CUDA tensors, enqueued on the current stream, nothing synchronised.  Stage 0: kf_Tcw, kf_center
+    and X of tab change IN PLACE; stage 1: kf_gba_Tcw, kf_in_gba, pt_gba_X, pt_in_gba of tab (made when missing) are written.
+    n = (ncam, npts_ba) when cam_kf / gpt_pt are the full-capacity tensors of global_ba_assemble_device.  Returns a dict of device
+    tensors: the written tables, normal / min_max / nd_written, counts[3], status (the GA_* bits), the workspace under "_workspace"."""
+    import torch
+    L = _lib.load()
+    g = tab.get
+    dev = tab["kf_Tcw"].device
+    nkf, npts = tab["kf_Tcw"].numel() // 12, tab["X"].numel() // 3
+    ncam, npb = (cam_kf.numel(), gpt_pt.numel()) if n is None else (int(n[0]), int(n[1]))
+    assert cam_kf.numel() >= ncam and poses7.numel() >= 7 * ncam and gpt_pt.numel() >= npb and pts3.numel() >= 3 * npb
+    run_nd = bool(normals) and stage == 0 and npts > 0
+    nobs = g("obs_kf").numel() if (run_nd and g("obs_kf") is not None) else 0
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_global_ba_apply_workspace(nkf, npts, C.byref(nbytes)), "orbl_global_ba_apply_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else dict(out)
+    sizes = [("counts", torch.int32, 3), ("status", torch.int32, 1)]
+    if run_nd:
+        sizes += [("normal", torch.float64, 3 * npts), ("min_max", torch.float32, 2 * npts), ("nd_written", torch.uint8, npts)]
+    if stage:
+        for k in ("kf_gba_Tcw", "kf_in_gba", "pt_gba_X", "pt_in_gba"):
+            o.setdefault(k, g(k))
+        sizes += [("kf_gba_Tcw", torch.float64, 12 * nkf), ("kf_in_gba", torch.uint8, nkf), ("pt_gba_X", torch.float64, 3 * npts), ("pt_in_gba", torch.uint8, npts)]
+    for k, dt, m in sizes:
+        if o.get(k) is None:
+            o[k] = torch.zeros(max(m, 1), dtype=dt, device=dev)[:m]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
+
+    def p(t):
+        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+
+    def q(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    for k in ("kf_Tcw", "kf_center", "X"):
+        assert g(k) is None or (g(k).is_contiguous() and g(k).dtype == torch.float64), k
+    nd = [q(g(k)) if run_nd else None for k in _GP_ND]
+    if not nobs:
+        nd[2] = None
+    sf = g("scale_factors")
+    s0 = stage == 0
+    _lib.check(L.orbl_global_ba_apply_device(ncam, p(cam_kf), p(poses7), npb, p(gpt_pt), p(pts3), int(stage), nkf, p(g("kf_bad")), p(g("kf_Tcw")) if s0 else None,
+                                             p(g("kf_center")) if s0 else None, npts, p(g("X")) if s0 else None, p(g("pt_bad")),
+                                             *[p(o.get(k)) if stage else None for k in ("kf_gba_Tcw", "kf_in_gba", "pt_gba_X", "pt_in_gba")], nd[0], nobs, nd[1], nd[2], nd[3], nd[4],
+                                             sf.numel() if (run_nd and sf is not None) else 0, *[q(o.get(k)) if run_nd else None for k in ("normal", "min_max", "nd_written")],
+                                             p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_global_ba_apply_device")
+    r = dict(o)
+    for k in ("normal", "min_max", "nd_written"):
+        r.setdefault(k, None)
+    if s0:
+        r.update(kf_Tcw=g("kf_Tcw"), kf_center=g("kf_center"), X=g("X"))
+    r["_workspace"] = ws
+    return r
+
+
+def global_bundle_adjustment_on_tables(tab, ba_kf=None, ba_pt=None, n_iterations=200, stop_flag=None, stage=0, is_robust=True, normals=True, device=False, out=None):
+    """CeresOptimizer::GlobalBundleAdjustemnt on the map tables: global_ba_assemble, optimizer.bundle_adjustment on the compact problem (its
+    structure pass is host code: the problem crosses to the host between the two calls, the map does not), global_ba_apply.  The write-back
+    also runs after a raised stop flag: the reference writes back whatever the solve left, and RunGlobalBundleAdjustment decides afterwards
+    whether to propagate.  With no camera nothing is solved and nothing written (:67-70).  Returns dict(assembled, poses7, pts3, summary,
+    applied)."""
+    from . import optimizer
+    asm = global_ba_assemble(tab, ba_kf=ba_kf, ba_pt=ba_pt, is_robust=is_robust, device=device)
+    keys = ("K4", "poses7", "cam_fixed", "pts3", "gobs_cam", "gobs_pt", "gobs_uv", "gobs_weight", "gobs_robust")
+    if device:
+        c = asm["counts"].cpu().tolist()                         # (waits for the stream: the solver reads the problem on the host)
+        st = int(asm["status"].item()) & 0xFFFFFFFF
+        if st & (GA_CAP_CAM | GA_CAP_PTS | GA_CAP_OBS):
+            raise _lib.OrbHipError("global_ba_assemble_device: a list did not fit (status %d)" % st)
+        per = {k: (w, c[cc]) for k, _, w, cc in _GA_OUT if cc >= 0}
+        h = {k: asm[k][:per[k][0] * per[k][1]].cpu().numpy() for k in keys}
+    else:
+        h = asm
+        c = [int(v) for v in asm["counts"]]
+    if c[0] == 0:
+        return dict(assembled=asm, poses7=np.zeros((0, 7)), pts3=np.zeros((0, 3)), summary=None, applied=None)
+    poses7, pts3, summary = optimizer.bundle_adjustment(h["K4"].reshape(-1, 4), h["poses7"].reshape(-1, 7), h["cam_fixed"], h["pts3"].reshape(-1, 3), h["gobs_cam"], h["gobs_pt"],
+                                                        h["gobs_uv"].reshape(-1, 2), h["gobs_weight"], h["gobs_robust"], n_iterations, stop_flag=stop_flag)
+    if device:
+        import torch
+        dv = tab["kf_Tcw"].device
+        up = [torch.as_tensor(np.ascontiguousarray(poses7).reshape(-1)).to(dv), torch.as_tensor(np.ascontiguousarray(pts3).reshape(-1)).to(dv)]
+        applied = global_ba_apply_device(asm["cam_kf"], asm["gpt_pt"], up[0], up[1], tab, stage=stage, normals=normals, out=out, n=(c[0], c[1]))
+        applied["_uploads"] = up
+    else:
+        applied = global_ba_apply(asm["cam_kf"], asm["gpt_pt"], poses7, pts3, tab, stage=stage, normals=normals, out=out)
+    return dict(assembled=asm, poses7=poses7, pts3=pts3, summary=summary, applied=applied)

@@ -886,6 +886,94 @@ int orbl_essential_graph_apply_device(int n_vtx, const int32_t* d_vtx_kf, const 
  * 56 * n_vtx, 56 * n_vtx; at least 256. */
 int orbl_essential_graph_apply_workspace(int nkf, int n_vtx, size_t* bytes);
 
+/* ---- CeresOptimizer::GlobalBundleAdjustemnt -> BundleAdjustment on the map tables, first half (src/CeresOptimizer.cc:59-176; called at
+ * LoopClosing.cc:656 and Tracking.cc:502): the cameras, the points and one row per (point, observing keyframe with a camera), as the
+ * arguments of ba_solve.  Keyframes are 0..nkf-1, points 0..npts-1 (both may be 0).
+ *   ba_kf[n_ba_kf]: the `keyframes` argument (bad ones and repeats allowed); NULL = 0..nkf-1 (n_ba_kf is then nkf, or 0 for the empty list).
+ *   ba_pt[n_ba_pt]: the `map_points` argument, DISTINCT (Map holds a std::set); NULL = 0..npts-1 (n_ba_pt is then npts, or 0).
+ *   kf_id[nkf]; kf_bad[nkf] (nullable); kf_Tcw[nkf][12]; kf_K4[nkf][4] {fx, fy, cx, cy}, double.   X[npts][3]; pt_bad (nullable);
+ *   obs_off[npts + 1] / obs_kf[] in each point's std::map order; obs_uv[nobs][2] (float, the undistorted keypoint); obs_level[nobs];
+ *   inv_level_sigma2[n_levels]; is_robust.
+ * Cameras: every ba_kf entry that is not bad, once (its FIRST list position counts), by ascending kf_id, ties by that first position (the
+ * std::stable_sort of csrc/compat/orbslam_dropin.h); the ids need not be distinct, small or table indices.  cam_kf[c]; K4[c]; poses7[c] =
+ * ba_matrix4d_to_pose7 of the pose; cam_fixed[c] = (kf_id == 0); kf_cam[nkf] = the camera or -1, every element written.
+ * Points, in ba_pt order: a point that is not bad and has at least one row becomes problem point j: gpt_pt[j], pts3[j]; a point without
+ * rows is LEFT OUT (:170-172; orbl_local_ba_assemble keeps such a point); pt_idx[npts] = j or -1, every element written.
+ * Rows, per problem point in that order, its list in list order: one per observer that is not bad and has a camera - an observer outside
+ * ba_kf gives no row.  The reference's gate id_ > max_keyframe_id (:142) is implied by "the observer has a camera": the maximum is taken
+ * over the cameras, so no camera's id exceeds it; it is not tested a second time.  gobs_cam, gobs_pt, gobs_uv (double, the float widened),
+ * gobs_weight = (double)inv_level_sigma2[obs_level], gobs_robust = is_robust ? 1 : 0, gobs_src = the index e in the obs_* arrays.
+ * counts[3] = {ncam, npts_ba, nobs_ba}; all 0 when there is no camera (:67-70).
+ * The output lists have the capacities cap_cam, cap_pts, cap_obs (an array may be NULL when its capacity is 0): when a list does not fit
+ * the call returns ORBHIP_ECAP with only counts[] written.  Every place in a list comes from an ordered compaction: the outputs are the
+ * same bytes on every run.  Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for
+ * counts, NULLs, a NULL list whose count is neither 0 nor the table's, offsets that do not ascend from 0, indices or levels out of
+ * range, a point twice in ba_pt, n_levels outside [1, 64]; ORBHIP_ENODEV without a GPU.                                               */
+int orbl_global_ba_assemble(int n_ba_kf, const int32_t* ba_kf, int n_ba_pt, const int32_t* ba_pt, int nkf, const int32_t* kf_id, const uint8_t* kf_bad, const double* kf_Tcw,
+                            const double* kf_K4, int npts, const double* X, const uint8_t* pt_bad, const int32_t* obs_off, const int32_t* obs_kf, const float* obs_uv,
+                            const int32_t* obs_level, const float* inv_level_sigma2, int n_levels, int is_robust, int cap_cam, int cap_pts, int cap_obs, int32_t* counts,
+                            int32_t* cam_kf, int32_t* kf_cam, double* K4, double* poses7, uint8_t* cam_fixed, int32_t* gpt_pt, int32_t* pt_idx, double* pts3,
+                            int32_t* gobs_cam, int32_t* gobs_pt, double* gobs_uv, double* gobs_weight, uint8_t* gobs_robust, int32_t* gobs_src);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nobs = obs_off[npts] given by the caller).  Counts, NULL
+ * pointers and alignment (8 bytes for the 64-bit arrays and the workspace, 4 for the 32-bit ones) are checked on the host; the data is
+ * bounds-checked on the device exactly as in orbl_local_ba_assemble_device: an entry out of range counts as ABSENT - a list entry that is
+ * not there, a point without a list, an observation that gives no row - and sets a bit in *d_status (nullable; zeroed first):
+ * 1 = offsets, 2 = a keyframe index, 4 = a point index, 16 = a level; a list that does not fit is written up to its capacity, counts[]
+ * holds the wanted sizes (kf_cam and pt_idx the wanted places) and 32 = cameras, 64 = points, 128 = rows is set.  1024 = a point twice in
+ * ba_pt: its first position counts.
+ * `d_workspace`: at least orbl_global_ba_assemble_workspace(...) bytes, not shared with concurrent calls, reusable by the next.       */
+int orbl_global_ba_assemble_device(int n_ba_kf, const int32_t* d_ba_kf, int n_ba_pt, const int32_t* d_ba_pt, int nkf, const int32_t* d_kf_id, const uint8_t* d_kf_bad,
+                                   const double* d_kf_Tcw, const double* d_kf_K4, int npts, const double* d_X, const uint8_t* d_pt_bad, int nobs,
+                                   const int32_t* d_obs_off, const int32_t* d_obs_kf, const float* d_obs_uv, const int32_t* d_obs_level,
+                                   const float* d_inv_level_sigma2, int n_levels, int is_robust, int cap_cam, int cap_pts, int cap_obs, int32_t* d_counts,
+                                   int32_t* d_cam_kf, int32_t* d_kf_cam, double* d_K4, double* d_poses7, uint8_t* d_cam_fixed, int32_t* d_gpt_pt, int32_t* d_pt_idx,
+                                   double* d_pts3, int32_t* d_gobs_cam, int32_t* d_gobs_pt, double* d_gobs_uv, double* d_gobs_weight, uint8_t* d_gobs_robust,
+                                   int32_t* d_gobs_src, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_global_ba_assemble_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nkf, 4 * npts,
+ * 8 * n_ba_kf, 4 * n_ba_kf, 16, 8 * n_ba_pt, 8 * (ceil(n_ba_pt / 256) + 1). */
+int orbl_global_ba_assemble_workspace(int nkf, int npts, int n_ba_kf, int n_ba_pt, size_t* bytes);
+
+/* ---- CeresOptimizer::BundleAdjustment on the map tables, second half (src/CeresOptimizer.cc:190-224), in place on the tables.
+ *   cam_kf[ncam], gpt_pt[npts_ba] as assembled; poses7[ncam][7], pts3[npts_ba][3] from ba_solve.
+ *   stage: 0 = n_loop_keyframe == 0 (Tracking::CreateInitialMapMonocular), 1 = n_loop_keyframe != 0 (RunGlobalBundleAdjustment).
+ *   kf_bad[nkf], pt_bad[npts] (nullable) AT THE TIME OF THIS CALL: the reference tests isBad() again; a camera whose keyframe turned bad
+ *   and a point that turned bad are skipped.
+ * stage 0.  IN/OUT kf_Tcw[nkf][12], kf_center[nkf][3] (nullable unless normals are asked for), X[npts][3].
+ *  1. every camera (kf_id == 0 included: constant in the solve, it still goes through the quaternion): Tcw = [R(q / |q|) | t] with the
+ *     arithmetic of ba_pose7_to_matrix4d, the centre as orbl_correct_loop computes it.
+ *  2. X[gpt_pt[j]] = pts3[j].
+ *  3. every written point with observations: normal, min_max, nd_written = 1 as orbl_update_map_points computes them from the new
+ *     position, pt_ref_kf, ref_level and the NEW centres (every SetPose precedes the point loop).  Rows of other points are untouched;
+ *     nd_written[npts] is written for every element.  pt_ref_kf[npts] (-1 = none: no normal), obs_off[npts + 1] / obs_kf[],
+ *     ref_level[npts], scale_factors[n_levels], normal[npts][3], min_max[npts][2] (float), nd_written are nullable AS A SET: then step 3
+ *     is left out.  The stage-1 arrays are not read.
+ * stage 1.  OUT kf_gba_Tcw[nkf][12] (that matrix, for the written keyframes), pt_gba_X[npts][3] (= pts3[j], for the written points),
+ *  kf_in_gba[nkf] and pt_in_gba[npts]: EVERY element written, 1 where written and 0 elsewhere - the byte means
+ *  n_BA_global_for_keyframe_ == nLoopKF, and this call is what sets that stamp.  These four are what orbl_propagate_global_ba reads.
+ *  kf_Tcw, kf_center, X and the normal set are neither read nor written.
+ * counts[3] = {n_poses_written, n_points_written, n_normals_written}.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for counts, stage, NULLs, a
+ * keyframe out of range or twice in cam_kf, a point out of range or twice in gpt_pt, a pose that is not finite or has |q| = 0, reference
+ * keyframes, observers or levels out of range, n_levels outside [1, 64]; ORBHIP_ENODEV without a GPU.                                 */
+int orbl_global_ba_apply(int ncam, const int32_t* cam_kf, const double* poses7, int npts_ba, const int32_t* gpt_pt, const double* pts3, int stage, int nkf,
+                         const uint8_t* kf_bad, double* kf_Tcw, double* kf_center, int npts, double* X, const uint8_t* pt_bad, double* kf_gba_Tcw, uint8_t* kf_in_gba,
+                         double* pt_gba_X, uint8_t* pt_in_gba, const int32_t* pt_ref_kf, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* ref_level,
+                         const float* scale_factors, int n_levels, double* normal, float* min_max, uint8_t* nd_written, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation inside (nobs = obs_off[npts]).  Counts, stage, NULL pointers and
+ * alignment are checked on the host, the data on the device: an entry out of range counts as absent (a camera or a point that is not
+ * written, a normal that is not written) and sets a bit in *d_status (nullable; zeroed first): 1 = offsets, 2 = a keyframe index (or a
+ * keyframe twice in cam_kf: its LAST camera counts), 4 = a point index (or a point twice in gpt_pt: its last place counts), 16 = a level,
+ * 2048 = a pose that is not finite or has |q| = 0: that camera is not written.
+ * `d_workspace`: at least orbl_global_ba_apply_workspace(...) bytes, not shared with concurrent calls, reusable by the next.          */
+int orbl_global_ba_apply_device(int ncam, const int32_t* d_cam_kf, const double* d_poses7, int npts_ba, const int32_t* d_gpt_pt, const double* d_pts3, int stage, int nkf,
+                                const uint8_t* d_kf_bad, double* d_kf_Tcw, double* d_kf_center, int npts, double* d_X, const uint8_t* d_pt_bad, double* d_kf_gba_Tcw,
+                                uint8_t* d_kf_in_gba, double* d_pt_gba_X, uint8_t* d_pt_in_gba, const int32_t* d_pt_ref_kf, int nobs, const int32_t* d_obs_off,
+                                const int32_t* d_obs_kf, const int32_t* d_ref_level, const float* d_scale_factors, int n_levels, double* d_normal, float* d_min_max,
+                                uint8_t* d_nd_written, int32_t* d_counts, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_global_ba_apply_device needs (host arithmetic), each section rounded up to 256 bytes: 4 * nkf, 4 * npts; at
+ * least 256. */
+int orbl_global_ba_apply_workspace(int nkf, int npts, size_t* bytes);
+
 /* ---- Initializer::Initialize (src/Initializer.cc:54-889, monocular; called from src/Tracking.cc:432): the H / F RANSAC over
  * caller-given minimal sets, the model choice, ReconstructH / ReconstructF with CheckRT.  Frame 1 = the reference (initial) frame,
  * frame 2 = the current one.
