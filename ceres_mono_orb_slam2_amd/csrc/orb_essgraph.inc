@@ -6,7 +6,7 @@
 // tables").
 //
 // assemble: both lists are ORDERED compactions.  One lane per kf_rank position holds a flag (vertex) or a pair of counts (its
-// loop-connection edges, its per-keyframe edges); an exclusive scan (la_block_excl per workgroup, k_la_scan_sums across them) gives the
+// loop-connection edges, its per-keyframe edges); an exclusive scan (mt_block_excl per workgroup, k_mt_scan_sums across them) gives the
 // lane its places, and the lane writes them in the order the reference walks its keyframe.  Atomics only take order-free maxima, ors
 // and integer sums.
 //   k_eg_stamp     one lane per keyframe / group entry / target / table entry: the inverse of kf_rank, where the group and the targets
@@ -17,8 +17,11 @@
 // apply: keyframes and points are independent of each other once the vertex of every keyframe is known.
 //   k_ea_stamp     one lane per vertex: vtx_of[k] (atomicMax)
 //   k_ea_pose      one lane per vertex: exp(lie_orig), exp(lie_opt)^-1 (to the workspace), the new pose and centre
-//   k_ea_points    one lane per point: the new position, then k_mp_prep's normal / depth walk over the NEW centres
+//   k_ea_points    one lane per point: the new position, then the normal / depth walk (mt_normal_depth) over the NEW centres
 // Outputs are written with vector stores only.
+#include "orb_maptable.h"
+#include "sim3_math.h"
+
 namespace orbhip {
 
 #define EG_WG 256
@@ -39,17 +42,14 @@ struct EgArgs {
   int32_t *counts, *vtx_kf, *kf_vtx; double* lie7; uint8_t* vtx_fixed; int32_t *edge_j, *edge_i; double* edge_S; uint8_t* edge_kind; uint32_t* status;
   // workspace: inv_kf[nkf] | gpos[nkf] | tpos[nkf] (all set to all ones per call) | vscan[nkf] | vsums[nb + 1] | escan[nkf] | esums[nb + 1] |
   // wB[nkf][7] | wW[nkf][7]
-  int32_t *inv_kf, *gpos, *tpos; la_u64 *vscan, *vsums, *escan, *esums; double *wB, *wW;
+  int32_t *inv_kf, *gpos, *tpos; mt_u64 *vscan, *vsums, *escan, *esums; double *wB, *wW;
 };
 
 __device__ __forceinline__ bool eg_kf_bad(const EgArgs& a, int k) { return a.kf_bad && a.kf_bad[k]; }
 __device__ __forceinline__ bool eg_in(const EgArgs& a, int k) { return k >= 0 && k < a.nkf; }
 __device__ __forceinline__ long long eg_rank(const EgArgs& a, int k) { return a.kf_rank ? (long long)a.kf_rank[k] : (long long)k; }
 __device__ __forceinline__ int eg_kf_of_rank(const EgArgs& a, int r) { return a.kf_rank ? a.inv_kf[r] : r; }
-// row i of a CSR table with n entries; a row whose offsets are out of range is empty (k_eg_stamp flags it)
-__device__ __forceinline__ void eg_row(const int32_t* off, int i, int n, int* lo, int* hi) {
-  if (!la_range_ok(off, i, n, lo, hi)) { *lo = 0; *hi = 0; }
-}
+// (a CSR row whose offsets are out of range is empty wherever the walk meets it - mt_range - and k_eg_stamp flags it)
 __device__ __forceinline__ bool eg_sim3_ok(const double* S) {
   bool fin = true;
   for (int q = 0; q < 7; q++) fin = fin && isfinite(S[q]);
@@ -60,42 +60,42 @@ __global__ __launch_bounds__(EG_WG) void k_eg_stamp(EgArgs a) {
   const int i = blockIdx.x * EG_WG + threadIdx.x;
   if (i < a.nkf) {
     int lo, hi;
-    if (!la_range_ok(a.child_off, i, a.n_child, &lo, &hi) || !la_range_ok(a.loop_off, i, a.n_loop, &lo, &hi) || !la_range_ok(a.conn_off, i, a.n_cw, &lo, &hi) ||
-        !la_range_ok(a.ord_off, i, a.n_ord, &lo, &hi))
-      la_flag(a.status, EG_ST_OFFSETS);
+    if (!mt_range(a.child_off, i, a.n_child, &lo, &hi) || !mt_range(a.loop_off, i, a.n_loop, &lo, &hi) || !mt_range(a.conn_off, i, a.n_cw, &lo, &hi) ||
+        !mt_range(a.ord_off, i, a.n_ord, &lo, &hi))
+      mt_flag(a.status, EG_ST_OFFSETS);
     const int par = a.kf_parent[i];
-    if (par < -1 || par >= a.nkf) la_flag(a.status, EG_ST_KF);
+    if (par < -1 || par >= a.nkf) mt_flag(a.status, EG_ST_KF);
     if (a.kf_rank) {
       const int r = a.kf_rank[i];
-      if (r < 0 || r >= a.nkf) la_flag(a.status, EG_ST_RANK);
-      else if (atomicMax(&a.inv_kf[r], i) != -1) la_flag(a.status, EG_ST_RANK);  // (not a permutation: the highest index holds the place)
+      if (r < 0 || r >= a.nkf) mt_flag(a.status, EG_ST_RANK);
+      else if (atomicMax(&a.inv_kf[r], i) != -1) mt_flag(a.status, EG_ST_RANK);  // (not a permutation: the highest index holds the place)
     }
   }
   if (i < a.nconn) {
     const int k = a.group_kf[i];
-    if (!eg_in(a, k)) la_flag(a.status, EG_ST_KF);
-    else if (!eg_sim3_ok(a.corrected + 7 * (size_t)i) || !eg_sim3_ok(a.non_corrected + 7 * (size_t)i)) la_flag(a.status, EG_ST_SIM3);
-    else if (atomicMax(&a.gpos[k], i) != -1) la_flag(a.status, EG_ST_KF);        // (a keyframe listed twice: its last instance counts)
+    if (!eg_in(a, k)) mt_flag(a.status, EG_ST_KF);
+    else if (!eg_sim3_ok(a.corrected + 7 * (size_t)i) || !eg_sim3_ok(a.non_corrected + 7 * (size_t)i)) mt_flag(a.status, EG_ST_SIM3);
+    else if (atomicMax(&a.gpos[k], i) != -1) mt_flag(a.status, EG_ST_KF);        // (a keyframe listed twice: its last instance counts)
   }
   if (i < a.ntgt) {
     int lo, hi;
-    if (!la_range_ok(a.link_off, i, a.n_link, &lo, &hi)) la_flag(a.status, EG_ST_OFFSETS);
+    if (!mt_range(a.link_off, i, a.n_link, &lo, &hi)) mt_flag(a.status, EG_ST_OFFSETS);
     const int k = a.tgt_kf[i];
-    if (!eg_in(a, k)) la_flag(a.status, EG_ST_KF);
-    else if (atomicMax(&a.tpos[k], i) != -1) la_flag(a.status, EG_ST_KF);
+    if (!eg_in(a, k)) mt_flag(a.status, EG_ST_KF);
+    else if (atomicMax(&a.tpos[k], i) != -1) mt_flag(a.status, EG_ST_KF);
   }
   // every entry of the five tables: one out of range is skipped wherever the walk meets it
   if ((i < a.n_child && !eg_in(a, a.child_kf[i])) || (i < a.n_loop && !eg_in(a, a.loop_edge[i])) || (i < a.n_cw && !eg_in(a, a.conn_kf[i])) ||
       (i < a.n_ord && !eg_in(a, a.ord_kf[i])) || (i < a.n_link && !eg_in(a, a.link_kf[i])))
-    la_flag(a.status, EG_ST_KF);
+    mt_flag(a.status, EG_ST_KF);
 }
 
 __global__ __launch_bounds__(EG_WG) void k_eg_vscan(EgArgs a) {
-  __shared__ la_u64 sw[EG_WG / 64];
+  __shared__ mt_u64 sw[EG_WG / 64];
   const int r = blockIdx.x * EG_WG + threadIdx.x;
   const int k = r < a.nkf ? eg_kf_of_rank(a, r) : -1;
-  la_u64 tot;
-  const la_u64 ex = la_block_excl(k >= 0 && !eg_kf_bad(a, k) ? 1ull : 0ull, sw, &tot);
+  mt_u64 tot;
+  const mt_u64 ex = mt_block_excl<EG_WG>(k >= 0 && !eg_kf_bad(a, k) ? 1ull : 0ull, sw, &tot);
   if (r < a.nkf) a.vscan[r] = ex;
   if (threadIdx.x == 0) a.vsums[blockIdx.x] = tot;
 }
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(EG_WG) void k_eg_vertices(EgArgs a) {
   if (r == 0) {
     const int n = (int)a.vsums[a.nb];
     a.counts[0] = n;
-    if (n > a.cap_vtx) la_flag(a.status, EG_ST_CAP_VTX);
+    if (n > a.cap_vtx) mt_flag(a.status, EG_ST_CAP_VTX);
   }
   const int k = eg_kf_of_rank(a, r);
   if (k < 0 || eg_kf_bad(a, k)) return;                                        // (kf_vtx was set to -1)
@@ -153,7 +153,7 @@ __device__ __forceinline__ bool eg_holds(const int32_t* arr, int lo, int hi, int
 // KeyFrame::GetWeight (src/KeyFrame.cc:312-319): 0 when j is not connected
 __device__ __forceinline__ int eg_weight(const EgArgs& a, int i, int j) {
   int lo, hi;
-  eg_row(a.conn_off, i, a.n_cw, &lo, &hi);
+  mt_range(a.conn_off, i, a.n_cw, &lo, &hi);
   for (int e = lo; e < hi; e++) if (a.conn_kf[e] == j) return a.conn_w[e];
   return 0;
 }
@@ -166,7 +166,7 @@ __device__ __forceinline__ bool eg_linked(const EgArgs& a, int t_kf, int other) 
   const int t = a.tpos[t_kf];
   if (t < 0) return false;
   int lo, hi;
-  eg_row(a.link_off, t, a.n_link, &lo, &hi);
+  mt_range(a.link_off, t, a.n_link, &lo, &hi);
   return eg_holds(a.link_kf, lo, hi, other) && a.kf_vtx[t_kf] >= 0 && a.kf_vtx[other] >= 0 && eg_lc_pass(a, t_kf, other);
 }
 
@@ -187,7 +187,7 @@ __device__ __forceinline__ void eg_walk(const EgArgs& a, int i, int atA, int atB
   const bool has_vtx = a.kf_vtx[i] >= 0;
   const int t = a.tpos[i];
   if (t >= 0) {
-    eg_row(a.link_off, t, a.n_link, &lo, &hi);
+    mt_range(a.link_off, t, a.n_link, &lo, &hi);
     double Swi[7];
     if (EMIT && has_vtx && lo < hi) s3_inverse(a.wB + 7 * (size_t)i, Swi);     // (exp of the block, not the non-corrected Sim3: :799-800)
     long long prev = -1;
@@ -210,7 +210,7 @@ __device__ __forceinline__ void eg_walk(const EgArgs& a, int i, int atA, int atB
       else { if (EMIT) eg_edge(a, atB + cB, par, i, 1, a.wW + 7 * (size_t)par, Swi); cB++; }
     }
     int llo, lhi;
-    eg_row(a.loop_off, i, a.n_loop, &llo, &lhi);
+    mt_range(a.loop_off, i, a.n_loop, &llo, &lhi);
     long long prev = -1;
     for (;;) {                                                                 // (:857-876) std::set<KeyFrame*>: ascending kf_rank
       const int l = eg_next(a, a.loop_edge, llo, lhi, &prev);
@@ -221,8 +221,8 @@ __device__ __forceinline__ void eg_walk(const EgArgs& a, int i, int atA, int atB
       cB++;
     }
     int clo, chi;
-    eg_row(a.child_off, i, a.n_child, &clo, &chi);
-    eg_row(a.ord_off, i, a.n_ord, &lo, &hi);
+    mt_range(a.child_off, i, a.n_child, &clo, &chi);
+    mt_range(a.ord_off, i, a.n_ord, &lo, &hi);
     int nw = 0;
     while (lo + nw < hi && a.ord_w[lo + nw] >= a.min_weight) nw++;
     if (lo + nw == hi) nw = 0;                                                 // (src/KeyFrame.cc:218-235: upper_bound gave end())
@@ -240,31 +240,31 @@ __device__ __forceinline__ void eg_walk(const EgArgs& a, int i, int atA, int atB
 }
 
 __global__ __launch_bounds__(EG_WG) void k_eg_escan(EgArgs a) {
-  __shared__ la_u64 sw[EG_WG / 64];
+  __shared__ mt_u64 sw[EG_WG / 64];
   const int r = blockIdx.x * EG_WG + threadIdx.x;
   const int i = r < a.nkf ? eg_kf_of_rank(a, r) : -1;
   int nA = 0, nB = 0, drop = 0;
   if (i >= 0) eg_walk<false>(a, i, 0, 0, &nA, &nB, &drop);
-  la_u64 tot;
-  const la_u64 ex = la_block_excl(((la_u64)(uint32_t)nB << 32) | (la_u64)(uint32_t)nA, sw, &tot);   // (neither sum reaches 2^31)
+  mt_u64 tot;
+  const mt_u64 ex = mt_block_excl<EG_WG>(((mt_u64)(uint32_t)nB << 32) | (mt_u64)(uint32_t)nA, sw, &tot);   // (neither sum reaches 2^31)
   if (r < a.nkf) a.escan[r] = ex;
   if (threadIdx.x == 0) a.esums[blockIdx.x] = tot;
-  drop = ap_wave_sum(drop);
+  drop = mt_wave_sum(drop);
   if ((threadIdx.x & 63) == 0 && drop) atomicAdd(&a.counts[3], drop);
 }
 
 __global__ __launch_bounds__(EG_WG) void k_eg_emit(EgArgs a) {
   const int r = blockIdx.x * EG_WG + threadIdx.x;
   if (r >= a.nkf) return;
-  const la_u64 t = a.esums[a.nb];
+  const mt_u64 t = a.esums[a.nb];
   const int totA = (int)(uint32_t)t, totB = (int)(t >> 32);
   if (r == 0) {
     a.counts[1] = totA + totB; a.counts[2] = totA;
-    if (totA + totB > a.cap_edges) la_flag(a.status, EG_ST_CAP_EDGES);
+    if (totA + totB > a.cap_edges) mt_flag(a.status, EG_ST_CAP_EDGES);
   }
   const int i = eg_kf_of_rank(a, r);
   if (i < 0) return;
-  const la_u64 at = a.escan[r] + a.esums[blockIdx.x];
+  const mt_u64 at = a.escan[r] + a.esums[blockIdx.x];
   int nA, nB, drop;
   eg_walk<true>(a, i, (int)(uint32_t)at, totA + (int)(at >> 32), &nA, &nB, &drop);
 }
@@ -298,9 +298,9 @@ __global__ __launch_bounds__(EG_WG) void k_ea_stamp(EaArgs a) {
   const int k = a.vtx_kf[v];
   bool fin = true;
   for (int q = 0; q < 7; q++) fin = fin && isfinite(a.lie_orig[7 * (size_t)v + q]) && isfinite(a.lie_opt[7 * (size_t)v + q]);
-  if (k < 0 || k >= a.nkf) la_flag(a.status, EG_ST_KF);
-  else if (!fin) la_flag(a.status, EG_ST_SIM3);                                // (the vertex is absent: its keyframe and its points stay)
-  else if (atomicMax(&a.vtx_of[k], v) != -1) la_flag(a.status, EG_ST_KF);      // (a keyframe listed twice: its last vertex counts)
+  if (k < 0 || k >= a.nkf) mt_flag(a.status, EG_ST_KF);
+  else if (!fin) mt_flag(a.status, EG_ST_SIM3);                                // (the vertex is absent: its keyframe and its points stay)
+  else if (atomicMax(&a.vtx_of[k], v) != -1) mt_flag(a.status, EG_ST_KF);      // (a keyframe listed twice: its last vertex counts)
 }
 
 __global__ __launch_bounds__(EG_WG) void k_ea_pose(EaArgs a) {
@@ -310,14 +310,13 @@ __global__ __launch_bounds__(EG_WG) void k_ea_pose(EaArgs a) {
   const uint64_t m = __ballot(own);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.counts[0], (int)__popcll(m));
   if (!own) return;
-  double So[7], Sn[7], Si[7], T[12], Twc[12];
+  double So[7], Sn[7], Si[7], T[12];
   s3_exp(a.lie_orig + 7 * (size_t)v, So);
   s3_exp(a.lie_opt + 7 * (size_t)v, Sn);                                       // (:918-929) Tiw = [R | t / s]
   s3_inverse(Sn, Si);
   for (int q = 0; q < 7; q++) { a.Sorig[7 * (size_t)v + q] = So[q]; a.Sinv[7 * (size_t)v + q] = Si[q]; }
   s3_to_pose34(Sn, T);
-  for (int q = 0; q < 12; q++) a.kf_Tcw[12 * (size_t)k + q] = T[q];
-  if (a.kf_center) { mc_pose_inverse(T, Twc); for (int q = 0; q < 3; q++) a.kf_center[3 * (size_t)k + q] = Twc[4 * q + 3]; }
+  mt_set_pose(a.kf_Tcw, a.kf_center, k, T);
 }
 
 __global__ __launch_bounds__(EG_WG) void k_ea_points(EaArgs a) {
@@ -328,7 +327,7 @@ __global__ __launch_bounds__(EG_WG) void k_ea_points(EaArgs a) {
     const int done = a.pt_done ? (int)a.pt_done[p] : 0;
     const int rc = a.pt_done ? a.pt_corr_ref[p] : -1, rr = a.pt_ref_kf[p];
     const int r = done != 0 ? rc : rr;
-    if (r < -1 || r >= a.nkf) la_flag(a.status, EG_ST_KF);
+    if (r < -1 || r >= a.nkf) mt_flag(a.status, EG_ST_KF);
     else if (r >= 0) v = a.vtx_of[r];
   }
   const uint64_t m = __ballot(v >= 0);
@@ -343,31 +342,17 @@ __global__ __launch_bounds__(EG_WG) void k_ea_points(EaArgs a) {
   s3_act(a.Sinv + 7 * (size_t)v, Pc, Pw);
   a.X[3 * (size_t)p] = Pw[0]; a.X[3 * (size_t)p + 1] = Pw[1]; a.X[3 * (size_t)p + 2] = Pw[2];
   if (!a.nd_written) return;
-  // UpdateNormalAndDepth (:955) with k_mp_prep's arithmetic: every SetPose precedes the point loop, so every centre is the new one
+  // UpdateNormalAndDepth (:955): every SetPose precedes the point loop, so every centre is the new one
   int lo, hi;
-  if (!la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) { la_flag(a.status, EG_ST_OFFSETS); return; }
+  if (!mt_range(a.obs_off, p, a.nobs, &lo, &hi)) { mt_flag(a.status, EG_ST_OFFSETS); return; }
   if (lo == hi) return;
   const int r = a.pt_ref_kf[p], lvl = a.ref_level[p];
-  if (r < 0 || r >= a.nkf) { if (r != -1) la_flag(a.status, EG_ST_KF); return; }      // (-1: a point without a reference keyframe gets no normal)
-  if (lvl < 0 || lvl >= a.n_levels) { la_flag(a.status, EG_ST_LEVEL); return; }
-  const double x = Pw[0], y = Pw[1], z = Pw[2];
-  double nx = 0.0, ny = 0.0, nz = 0.0;
-  for (int e = lo; e < hi; e++) {
-    const int k = a.obs_kf[e];
-    if (k < 0 || k >= a.nkf) { la_flag(a.status, EG_ST_KF); return; }
-    const double vx = x - a.kf_center[3 * (size_t)k], vy = y - a.kf_center[3 * (size_t)k + 1], vz = z - a.kf_center[3 * (size_t)k + 2];
-    const double nn = sqrt((vx * vx + vy * vy) + vz * vz);
-    nx = nx + vx / nn; ny = ny + vy / nn; nz = nz + vz / nn;
-  }
-  const double n = (double)(hi - lo);
-  double* nv = a.normal + 3 * (size_t)p;
-  nv[0] = nx / n; nv[1] = ny / n; nv[2] = nz / n;
-  const double px = x - a.kf_center[3 * (size_t)r], py = y - a.kf_center[3 * (size_t)r + 1], pz = z - a.kf_center[3 * (size_t)r + 2];
-  const float dist = (float)sqrt((px * px + py * py) + pz * pz);
-  const float mx = dist * a.scale_factors[lvl];
-  a.min_max[2 * (size_t)p] = mx / a.scale_factors[a.n_levels - 1];
-  a.min_max[2 * (size_t)p + 1] = mx;
-  a.nd_written[p] = 1;
+  if (r < 0 || r >= a.nkf) { if (r != -1) mt_flag(a.status, EG_ST_KF); return; }      // (-1: a point without a reference keyframe gets no normal)
+  if (lvl < 0 || lvl >= a.n_levels) { mt_flag(a.status, EG_ST_LEVEL); return; }
+  const int res = mt_normal_depth(a.obs_kf, lo, hi, a.nkf, a.kf_center, Pw[0], Pw[1], Pw[2], r, lvl, a.scale_factors, a.n_levels, a.normal + 3 * (size_t)p,
+                                  a.min_max + 2 * (size_t)p);
+  if (res == MT_ND_KF) mt_flag(a.status, EG_ST_KF);
+  if (res == MT_ND_OK) a.nd_written[p] = 1;
 }
 
 struct EaWs { size_t vtx_of, Sorig, Sinv, total; };
@@ -439,7 +424,7 @@ int orbl_essential_graph_assemble_device(int nkf, const int32_t* kf_id, const ui
   A.counts = counts; A.vtx_kf = vtx_kf; A.kf_vtx = kf_vtx; A.lie7 = lie7; A.vtx_fixed = vtx_fixed; A.edge_j = edge_j; A.edge_i = edge_i; A.edge_S = edge_Sji;
   A.edge_kind = edge_kind; A.status = status;
   A.inv_kf = (int32_t*)(wb + ws.inv_kf); A.gpos = (int32_t*)(wb + ws.gpos); A.tpos = (int32_t*)(wb + ws.tpos);
-  A.vscan = (la_u64*)(wb + ws.vscan); A.vsums = (la_u64*)(wb + ws.vsums); A.escan = (la_u64*)(wb + ws.escan); A.esums = (la_u64*)(wb + ws.esums);
+  A.vscan = (mt_u64*)(wb + ws.vscan); A.vsums = (mt_u64*)(wb + ws.vsums); A.escan = (mt_u64*)(wb + ws.escan); A.esums = (mt_u64*)(wb + ws.esums);
   A.wB = (double*)(wb + ws.wB); A.wW = (double*)(wb + ws.wW);
   hipStream_t st = (hipStream_t)stream;
   if (status) ORBHIP_CHECK_HIP(hipMemsetAsync(status, 0, 4, st));
@@ -450,10 +435,10 @@ int orbl_essential_graph_assemble_device(int nkf, const int32_t* kf_id, const ui
   const int n_stamp = std::max(std::max(std::max(nkf, nconn), std::max(ntgt, n_child)), std::max(std::max(n_loop, n_connw), std::max(n_ord, n_link)));
   hipLaunchKernelGGL(k_eg_stamp, grid(n_stamp), dim3(EG_WG), 0, st, A);
   hipLaunchKernelGGL(k_eg_vscan, grid(nkf), dim3(EG_WG), 0, st, A);
-  hipLaunchKernelGGL(k_la_scan_sums, dim3(1), dim3(LA_SUM_WG), 0, st, A.vsums, A.nb);
+  hipLaunchKernelGGL(k_mt_scan_sums<mt_u64>, dim3(1), dim3(MT_SUM_WG), 0, st, A.vsums, A.nb);
   hipLaunchKernelGGL(k_eg_vertices, grid(nkf), dim3(EG_WG), 0, st, A);
   hipLaunchKernelGGL(k_eg_escan, grid(nkf), dim3(EG_WG), 0, st, A);
-  hipLaunchKernelGGL(k_la_scan_sums, dim3(1), dim3(LA_SUM_WG), 0, st, A.esums, A.nb);
+  hipLaunchKernelGGL(k_mt_scan_sums<mt_u64>, dim3(1), dim3(MT_SUM_WG), 0, st, A.esums, A.nb);
   hipLaunchKernelGGL(k_eg_emit, grid(nkf), dim3(EG_WG), 0, st, A);
   ORBHIP_CHECK_HIP(hipGetLastError());
   return 0;

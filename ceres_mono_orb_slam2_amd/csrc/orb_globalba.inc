@@ -3,8 +3,9 @@
 // (src/CeresOptimizer.cc:87-176, in the reading csrc/compat/orbslam_dropin.h fixed: cameras by keyframe id, an observer outside the list
 // gives no row, a point without rows is left out), and orbl_global_ba_apply* writes the result back (:190-224): SetPose, SetWorldPos and
 // UpdateNormalAndDepth (stage 0, Tracking.cc:502), or global_BA_Tcw_ / global_BA_pose_ with their stamps (stage 1, LoopClosing.cc:656).
-// Textually included by orb_localmap.hip after orb_localba.inc, whose scan helpers and status bits it uses.  FP64 throughout, no fused
-// multiply-add (-ffp-contract=off) (DESIGN.md section 2, "GlobalBundleAdjustment on the tables").
+// Textually included by orb_localmap.hip.  The scan, the row gate, LA_WG and the LA_ST_* status bits it shares with orb_localba.inc come
+// from orb_maptable.h.  FP64 throughout, no fused multiply-add (-ffp-contract=off) (DESIGN.md section 2, "GlobalBundleAdjustment on the
+// tables").
 //
 // assemble: every list is an ORDERED compaction; atomics only take order-free minima and integer sums.
 //   k_ga_stamp     one lane per list position / point: firstk[k], firstp[p] = the least position that names it (atomicMin), the offset checks
@@ -13,12 +14,14 @@
 //                  number of keys below its own is added to below[position] (n^2 compares over the whole device, no bound on the ids)
 //   k_ga_cams      one lane per ba_kf position: the camera's row at place below[position], kf_cam, counts[0]
 //   k_ga_pscan     one lane per ba_pt position: (rows of the point << 32 | 1) for a point with rows, scanned per workgroup;
-//                  k_la_scan_sums scans the workgroup sums;   k_ga_emit: the points and their rows, pt_idx, counts[1..2]
+//                  k_mt_scan_sums scans the workgroup sums;   k_ga_emit: the points and their rows, pt_idx, counts[1..2]
 // apply:
 //   k_gp_stamp     one lane per camera / problem point: cam_of[k], pt_of[p] = the last place that names it (atomicMax), the pose check
 //   k_gp_write     one lane per keyframe / point: stage 0 the pose with its centre and the position, stage 1 the gba arrays and flags
-//   k_gp_normals   one lane per point (stage 0): k_mp_prep's walk over the NEW centres
+//   k_gp_normals   one lane per point (stage 0): the normal / depth walk (mt_normal_depth) over the NEW centres
 // Outputs are written with vector stores only.
+#include "orb_maptable.h"
+
 namespace orbhip {
 
 #define GA_ST_REPEAT 1024u        /* assemble: a point twice in ba_pt (its first position counts) */
@@ -33,7 +36,7 @@ struct GaArgs {
   int32_t* gobs_cam; int32_t* gobs_pt; double* gobs_uv; double* gobs_weight; uint8_t* gobs_robust; int32_t* gobs_src; uint32_t* status;
   // workspace: firstk[nkf] | firstp[npts] (both set to all ones per call) | key[n_ba_kf] | below[n_ba_kf] | meta[4] (both cleared per call) |
   // pscan[n_ba_pt] | psums[nbp + 1]
-  uint32_t* firstk; uint32_t* firstp; la_u64* key; int32_t* below; int32_t* meta; la_u64 *pscan, *psums;
+  uint32_t* firstk; uint32_t* firstp; mt_u64* key; int32_t* below; int32_t* meta; mt_u64 *pscan, *psums;
 };
 
 __device__ __forceinline__ int ga_kf_at(const GaArgs& a, int q) { return a.ba_kf ? a.ba_kf[q] : q; }
@@ -43,17 +46,17 @@ __global__ __launch_bounds__(LA_WG) void k_ga_stamp(GaArgs a) {
   const int i = blockIdx.x * LA_WG + threadIdx.x;
   if (i < a.n_ba_kf) {
     const int k = ga_kf_at(a, i);
-    if (k < 0 || k >= a.nkf) la_flag(a.status, LA_ST_KF);
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, LA_ST_KF);
     else atomicMin(&a.firstk[k], (uint32_t)i);
   }
   if (i < a.n_ba_pt) {
     const int p = ga_pt_at(a, i);
-    if (p < 0 || p >= a.npts) la_flag(a.status, LA_ST_PT);
-    else if (atomicMin(&a.firstp[p], (uint32_t)i) != LA_NONE) la_flag(a.status, GA_ST_REPEAT);      // (whichever of the two arrives second sees the other)
+    if (p < 0 || p >= a.npts) mt_flag(a.status, LA_ST_PT);
+    else if (atomicMin(&a.firstp[p], (uint32_t)i) != LA_NONE) mt_flag(a.status, GA_ST_REPEAT);      // (whichever of the two arrives second sees the other)
   }
   if (i < a.npts) {
     int lo, hi;
-    if (!la_range_ok(a.obs_off, i, a.nobs, &lo, &hi)) la_flag(a.status, LA_ST_OFFSETS);
+    if (!mt_range(a.obs_off, i, a.nobs, &lo, &hi)) mt_flag(a.status, LA_ST_OFFSETS);
   }
 }
 
@@ -68,15 +71,15 @@ __global__ __launch_bounds__(LA_WG) void k_ga_keys(GaArgs a) {
   const int q = blockIdx.x * LA_WG + threadIdx.x;
   const int k = q < a.n_ba_kf ? ga_cand_at(a, q) : -1;
   // (kf_id, position) in one word that compares as the pair does: the id with its sign bit turned (int32 order), then the position
-  if (q < a.n_ba_kf) a.key[q] = k >= 0 ? (((la_u64)((uint32_t)a.kf_id[k] ^ 0x80000000u) << 32) | (la_u64)(uint32_t)q) : ~0ull;
+  if (q < a.n_ba_kf) a.key[q] = k >= 0 ? (((mt_u64)((uint32_t)a.kf_id[k] ^ 0x80000000u) << 32) | (mt_u64)(uint32_t)q) : ~0ull;
   const uint64_t m = __ballot(k >= 0);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.meta[0], (int)__popcll(m));
 }
 
 __global__ __launch_bounds__(LA_WG) void k_ga_rank(GaArgs a) {
-  __shared__ la_u64 tile[LA_WG];
+  __shared__ mt_u64 tile[LA_WG];
   const int q = blockIdx.x * LA_WG + threadIdx.x;
-  const la_u64 own = q < a.n_ba_kf ? a.key[q] : ~0ull;
+  const mt_u64 own = q < a.n_ba_kf ? a.key[q] : ~0ull;
   const int nt = (a.n_ba_kf + LA_WG - 1) / LA_WG;
   int below = 0;
   for (int t = blockIdx.y; t < nt; t += gridDim.y) {                           // (workgroup-uniform)
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(LA_WG) void k_ga_cams(GaArgs a) {
   if (q == 0) {
     const int ncam = a.meta[0];
     a.counts[0] = ncam;
-    if (ncam > a.cap_cam) la_flag(a.status, LA_ST_CAP_CAM);
+    if (ncam > a.cap_cam) mt_flag(a.status, LA_ST_CAP_CAM);
   }
   if (q >= a.n_ba_kf) return;
   const int k = ga_cand_at(a, q);
@@ -103,12 +106,7 @@ __global__ __launch_bounds__(LA_WG) void k_ga_cams(GaArgs a) {
   const int c = a.below[q];
   a.kf_cam[k] = c;
   if (c >= a.cap_cam) return;
-  const double* T = a.kf_Tcw + 12 * (size_t)k;                                 // Matrix4dToMatrix_7_1 (ba_matrix4d_to_pose7)
-  const double m[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
-  double qq[4];
-  rot_to_quat(m, qq);
-  double* o = a.poses7 + 7 * (size_t)c;
-  o[0] = T[3]; o[1] = T[7]; o[2] = T[11]; o[3] = qq[0]; o[4] = qq[1]; o[5] = qq[2]; o[6] = qq[3];
+  mt_pose34_to_pose7(a.kf_Tcw + 12 * (size_t)k, a.poses7 + 7 * (size_t)c);
   for (int j = 0; j < 4; j++) a.K4[4 * (size_t)c + j] = a.kf_K4[4 * (size_t)k + j];
   a.cam_kf[c] = k;
   a.cam_fixed[c] = a.kf_id[k] == 0 ? 1 : 0;                                    // (:115-120)
@@ -116,12 +114,7 @@ __global__ __launch_bounds__(LA_WG) void k_ga_cams(GaArgs a) {
 
 // whether observation e becomes a row: its keyframe is not bad and has a camera (:142 - the id gate is implied - and dropin :831)
 __device__ __forceinline__ bool ga_row_ok(const GaArgs& a, int e) {
-  const int k = a.obs_kf[e];
-  if (k < 0 || k >= a.nkf) { la_flag(a.status, LA_ST_KF); return false; }
-  if ((a.kf_bad && a.kf_bad[k]) || a.kf_cam[k] < 0) return false;
-  const int lvl = a.obs_level[e];
-  if (lvl < 0 || lvl >= a.n_levels) { la_flag(a.status, LA_ST_LEVEL); return false; }
-  return true;
+  return mt_row_ok(a.obs_kf, a.obs_level, e, a.nkf, a.n_levels, a.kf_bad, a.kf_cam, a.status, LA_ST_KF, LA_ST_LEVEL);
 }
 
 // the point of list position r when that position is where the list first names it, it is not bad and its list is in range, else -1;
@@ -130,7 +123,7 @@ __device__ __forceinline__ int ga_point_at(const GaArgs& a, int r, int* lo, int*
   *rows = 0;
   const int p = ga_pt_at(a, r);
   if (p < 0 || p >= a.npts || a.firstp[p] != (uint32_t)r || (a.pt_bad && a.pt_bad[p])) return -1;
-  if (!la_range_ok(a.obs_off, p, a.nobs, lo, hi)) return -1;
+  if (!mt_range(a.obs_off, p, a.nobs, lo, hi)) return -1;
   int n = 0;
   for (int e = *lo; e < *hi; e++) n += ga_row_ok(a, e) ? 1 : 0;
   *rows = n;
@@ -138,13 +131,13 @@ __device__ __forceinline__ int ga_point_at(const GaArgs& a, int r, int* lo, int*
 }
 
 __global__ __launch_bounds__(LA_WG) void k_ga_pscan(GaArgs a) {
-  __shared__ la_u64 sw[LA_WG / 64];
+  __shared__ mt_u64 sw[LA_WG / 64];
   const int r = blockIdx.x * LA_WG + threadIdx.x;
   int lo, hi, rows = 0;
   if (r < a.n_ba_pt) (void)ga_point_at(a, r, &lo, &hi, &rows);
-  const la_u64 v = rows > 0 ? (((la_u64)(uint32_t)rows << 32) | 1ull) : 0ull;   // (rows, points): a point without rows is left out (:170-172)
-  la_u64 tot;
-  const la_u64 ex = la_block_excl(v, sw, &tot);
+  const mt_u64 v = rows > 0 ? (((mt_u64)(uint32_t)rows << 32) | 1ull) : 0ull;   // (rows, points): a point without rows is left out (:170-172)
+  mt_u64 tot;
+  const mt_u64 ex = mt_block_excl<LA_WG>(v, sw, &tot);
   if (r < a.n_ba_pt) a.pscan[r] = ex;
   if (threadIdx.x == 0) a.psums[blockIdx.x] = tot;
 }
@@ -153,16 +146,16 @@ __global__ __launch_bounds__(LA_WG) void k_ga_emit(GaArgs a) {
   const int r = blockIdx.x * LA_WG + threadIdx.x;
   if (r >= a.n_ba_pt) return;
   if (r == 0) {
-    const la_u64 t = a.psums[a.nbp];
+    const mt_u64 t = a.psums[a.nbp];
     const int np = (int)(uint32_t)t, no = (int)(t >> 32);
     a.counts[1] = np; a.counts[2] = no;
-    if (np > a.cap_pts) la_flag(a.status, LA_ST_CAP_PTS);
-    if (no > a.cap_obs) la_flag(a.status, LA_ST_CAP_OBS);
+    if (np > a.cap_pts) mt_flag(a.status, LA_ST_CAP_PTS);
+    if (no > a.cap_obs) mt_flag(a.status, LA_ST_CAP_OBS);
   }
   int lo, hi, rows;
   const int p = ga_point_at(a, r, &lo, &hi, &rows);
   if (p < 0 || rows == 0) return;
-  const la_u64 at = a.pscan[r] + a.psums[blockIdx.x];
+  const mt_u64 at = a.pscan[r] + a.psums[blockIdx.x];
   const int j = (int)(uint32_t)at;
   int row = (int)(at >> 32);
   a.pt_idx[p] = j;
@@ -216,14 +209,14 @@ __global__ __launch_bounds__(LA_WG) void k_gp_stamp(GpArgs a) {
     const double* s = a.poses7 + 7 * (size_t)i;
     bool fin = true;
     for (int q = 0; q < 7; q++) fin = fin && isfinite(s[q]);
-    if (k < 0 || k >= a.nkf) la_flag(a.status, LA_ST_KF);
-    else if (!fin || !(((s[3] * s[3] + s[4] * s[4]) + s[5] * s[5]) + s[6] * s[6] > 0.0)) la_flag(a.status, GA_ST_POSE);
-    else if (atomicMax(&a.cam_of[k], i) != -1) la_flag(a.status, LA_ST_KF);    // (a keyframe listed twice: its last camera counts)
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, LA_ST_KF);
+    else if (!fin || !(((s[3] * s[3] + s[4] * s[4]) + s[5] * s[5]) + s[6] * s[6] > 0.0)) mt_flag(a.status, GA_ST_POSE);
+    else if (atomicMax(&a.cam_of[k], i) != -1) mt_flag(a.status, LA_ST_KF);    // (a keyframe listed twice: its last camera counts)
   }
   if (i < a.npts_ba) {
     const int p = a.gpt_pt[i];
-    if (p < 0 || p >= a.npts) la_flag(a.status, LA_ST_PT);
-    else if (atomicMax(&a.pt_of[p], i) != -1) la_flag(a.status, LA_ST_PT);      // (a point listed twice: its last place counts)
+    if (p < 0 || p >= a.npts) mt_flag(a.status, LA_ST_PT);
+    else if (atomicMax(&a.pt_of[p], i) != -1) mt_flag(a.status, LA_ST_PT);      // (a point listed twice: its last place counts)
   }
 }
 
@@ -234,16 +227,10 @@ __global__ __launch_bounds__(LA_WG) void k_gp_write(GpArgs a) {
     c = a.cam_of[i];
     if (c >= 0 && a.kf_bad && a.kf_bad[i]) c = -1;                              // (:193: the keyframe turned bad since)
     if (a.stage) a.kf_in_gba[i] = c >= 0 ? 1 : 0;
-    if (c >= 0) {                                                              // Matrix_7_1_ToMatrix4d (ba_pose7_to_matrix4d)
-      const double* s = a.poses7 + 7 * (size_t)c;
-      const double n = sqrt(((s[3] * s[3] + s[4] * s[4]) + s[5] * s[5]) + s[6] * s[6]);
-      const double q[4] = {s[3] / n, s[4] / n, s[5] / n, s[6] / n};
-      double R[9], T[12], Twc[12];
-      quat_to_R(q, R);
-      for (int r = 0; r < 3; r++) { T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2]; T[4 * r + 3] = s[r]; }
-      double* o = (a.stage ? a.kf_gba_Tcw : a.kf_Tcw) + 12 * (size_t)i;          // (:199-204)
-      for (int r = 0; r < 12; r++) o[r] = T[r];
-      if (!a.stage && a.kf_center) { mc_pose_inverse(T, Twc); for (int r = 0; r < 3; r++) a.kf_center[3 * (size_t)i + r] = Twc[4 * r + 3]; }
+    if (c >= 0) {                                                              // (:199-204) stage 1 keeps the pose aside: no centre
+      double T[12];
+      mt_pose7_to_pose34(a.poses7 + 7 * (size_t)c, T);
+      mt_set_pose(a.stage ? a.kf_gba_Tcw : a.kf_Tcw, a.stage ? nullptr : a.kf_center, i, T);
     }
   }
   if (i < a.npts) {
@@ -268,33 +255,17 @@ __global__ __launch_bounds__(LA_WG) void k_gp_normals(GpArgs a) {
   int wrote = 0;
   int lo = 0, hi = 0;
   if (p < a.npts && a.pt_of[p] >= 0 && !(a.pt_bad && a.pt_bad[p])) {
-    // UpdateNormalAndDepth (:219) with k_mp_prep's arithmetic: every SetPose precedes the point loop, so every centre is the new one
-    if (!la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) { la_flag(a.status, LA_ST_OFFSETS); hi = lo = 0; }
+    // UpdateNormalAndDepth (:219): every SetPose precedes the point loop, so every centre is the new one
+    if (!mt_range(a.obs_off, p, a.nobs, &lo, &hi)) mt_flag(a.status, LA_ST_OFFSETS);
     if (lo < hi) {
       const int r = a.pt_ref_kf[p], lvl = a.ref_level[p];
-      bool ok = true;
-      if (r < 0 || r >= a.nkf) { if (r != -1) la_flag(a.status, LA_ST_KF); ok = false; }      // (-1: a point without a reference keyframe gets no normal)
-      else if (lvl < 0 || lvl >= a.n_levels) { la_flag(a.status, LA_ST_LEVEL); ok = false; }
-      const double x = a.X[3 * (size_t)p], y = a.X[3 * (size_t)p + 1], z = a.X[3 * (size_t)p + 2];
-      double nx = 0.0, ny = 0.0, nz = 0.0;
-      for (int e = lo; ok && e < hi; e++) {
-        const int k = a.obs_kf[e];
-        if (k < 0 || k >= a.nkf) { la_flag(a.status, LA_ST_KF); ok = false; break; }
-        const double vx = x - a.kf_center[3 * (size_t)k], vy = y - a.kf_center[3 * (size_t)k + 1], vz = z - a.kf_center[3 * (size_t)k + 2];
-        const double nn = sqrt((vx * vx + vy * vy) + vz * vz);
-        nx = nx + vx / nn; ny = ny + vy / nn; nz = nz + vz / nn;
-      }
-      if (ok) {
-        const double n = (double)(hi - lo);
-        double* nv = a.normal + 3 * (size_t)p;
-        nv[0] = nx / n; nv[1] = ny / n; nv[2] = nz / n;
-        const double px = x - a.kf_center[3 * (size_t)r], py = y - a.kf_center[3 * (size_t)r + 1], pz = z - a.kf_center[3 * (size_t)r + 2];
-        const float dist = (float)sqrt((px * px + py * py) + pz * pz);
-        const float mx = dist * a.scale_factors[lvl];
-        a.min_max[2 * (size_t)p] = mx / a.scale_factors[a.n_levels - 1];
-        a.min_max[2 * (size_t)p + 1] = mx;
-        a.nd_written[p] = 1;
-        wrote = 1;
+      if (r < 0 || r >= a.nkf) { if (r != -1) mt_flag(a.status, LA_ST_KF); }      // (-1: a point without a reference keyframe gets no normal)
+      else if (lvl < 0 || lvl >= a.n_levels) mt_flag(a.status, LA_ST_LEVEL);
+      else {
+        const int res = mt_normal_depth(a.obs_kf, lo, hi, a.nkf, a.kf_center, a.X[3 * (size_t)p], a.X[3 * (size_t)p + 1], a.X[3 * (size_t)p + 2], r, lvl, a.scale_factors,
+                                        a.n_levels, a.normal + 3 * (size_t)p, a.min_max + 2 * (size_t)p);
+        if (res == MT_ND_KF) mt_flag(a.status, LA_ST_KF);
+        if (res == MT_ND_OK) { a.nd_written[p] = 1; wrote = 1; }
       }
     }
   }
@@ -352,8 +323,8 @@ int orbl_global_ba_assemble_device(int n_ba_kf, const int32_t* ba_kf, int n_ba_p
   A.obs_off = obs_off; A.obs_kf = obs_kf; A.obs_uv = obs_uv; A.obs_level = obs_level; A.inv_level_sigma2 = inv_level_sigma2;
   A.counts = counts; A.cam_kf = cam_kf; A.kf_cam = kf_cam; A.K4 = K4; A.poses7 = poses7; A.cam_fixed = cam_fixed; A.gpt_pt = gpt_pt; A.pt_idx = pt_idx; A.pts3 = pts3;
   A.gobs_cam = gobs_cam; A.gobs_pt = gobs_pt; A.gobs_uv = gobs_uv; A.gobs_weight = gobs_weight; A.gobs_robust = gobs_robust; A.gobs_src = gobs_src; A.status = status;
-  A.firstk = (uint32_t*)(wb + ws.firstk); A.firstp = (uint32_t*)(wb + ws.firstp); A.key = (la_u64*)(wb + ws.key); A.below = (int32_t*)(wb + ws.below);
-  A.meta = (int32_t*)(wb + ws.meta); A.pscan = (la_u64*)(wb + ws.pscan); A.psums = (la_u64*)(wb + ws.psums);
+  A.firstk = (uint32_t*)(wb + ws.firstk); A.firstp = (uint32_t*)(wb + ws.firstp); A.key = (mt_u64*)(wb + ws.key); A.below = (int32_t*)(wb + ws.below);
+  A.meta = (int32_t*)(wb + ws.meta); A.pscan = (mt_u64*)(wb + ws.pscan); A.psums = (mt_u64*)(wb + ws.psums);
   hipStream_t st = (hipStream_t)stream;
   if (status) ORBHIP_CHECK_HIP(hipMemsetAsync(status, 0, 4, st));
   ORBHIP_CHECK_HIP(hipMemsetAsync(counts, 0, 12, st));
@@ -372,7 +343,7 @@ int orbl_global_ba_assemble_device(int n_ba_kf, const int32_t* ba_kf, int n_ba_p
   }
   if (n_ba_pt > 0 && npts > 0) {
     hipLaunchKernelGGL(k_ga_pscan, grid(n_ba_pt), dim3(LA_WG), 0, st, A);
-    hipLaunchKernelGGL(k_la_scan_sums, dim3(1), dim3(LA_SUM_WG), 0, st, A.psums, A.nbp);
+    hipLaunchKernelGGL(k_mt_scan_sums<mt_u64>, dim3(1), dim3(MT_SUM_WG), 0, st, A.psums, A.nbp);
     hipLaunchKernelGGL(k_ga_emit, grid(n_ba_pt), dim3(LA_WG), 0, st, A);
   }
   ORBHIP_CHECK_HIP(hipGetLastError());

@@ -20,6 +20,8 @@
 //   k_cull_export   the final state into the caller's arrays.
 // Inside k_cull_resolve every word of the mutable state has ONE writer per phase (a point is handled by the one slot that claimed
 // it), all accesses are plain loads and stores, and phases are separated by workgroup barriers: no atomics on global memory there.
+#include "orb_maptable.h"
+
 namespace orbhip {
 
 #define KC_WG 256
@@ -40,36 +42,26 @@ struct CullArgs {
   int32_t *cnt, *spt, *sobs, *snext, *ohead, *dead, *bad, *ncur, *claim;
 };
 
-__device__ __forceinline__ void kc_flag(const CullArgs& a, uint32_t bits) { if (a.status) atomicOr(a.status, bits); }
-
-// [off[i], off[i + 1]) clamped into [0, total]; false (and an empty range) when the offsets are not usable
-__device__ __forceinline__ bool kc_range(const int32_t* off, int i, int total, int* lo, int* hi) {
-  const int l = off[i], h = off[i + 1];
-  const bool ok = l >= 0 && l <= h && h <= total;
-  *lo = ok ? l : 0; *hi = ok ? h : 0;
-  return ok;
-}
-
 __global__ __launch_bounds__(KC_WG) void k_cull_init(CullArgs a) {
   const int i = blockIdx.x * KC_WG + threadIdx.x;
   if (i < a.npts) {
     int lo, hi;
-    if (!kc_range(a.obs_off, i, a.nobs, &lo, &hi)) kc_flag(a, KC_ST_OFFSETS);
+    if (!mt_range(a.obs_off, i, a.nobs, &lo, &hi)) mt_flag(a.status, KC_ST_OFFSETS);
     a.bad[i] = a.pt_bad ? (a.pt_bad[i] != 0) : 0;
     a.ncur[i] = a.pt_nobs ? a.pt_nobs[i] : hi - lo;
     a.claim[i] = -1;
   }
   if (i < a.nobs) {
     const int k = a.obs_kf[i];
-    if (k < 0 || k >= a.nkf) kc_flag(a, KC_ST_INDEX);
-    if (a.obs_level[i] < 0) kc_flag(a, KC_ST_LEVEL);
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, KC_ST_INDEX);
+    if (a.obs_level[i] < 0) mt_flag(a.status, KC_ST_LEVEL);
     a.dead[i] = 0; a.ohead[i] = -1;
   }
   if (i < a.ncand) {
     int lo, hi;
-    if (!kc_range(a.slot_off, i, a.nslots, &lo, &hi)) kc_flag(a, KC_ST_OFFSETS);
+    if (!mt_range(a.slot_off, i, a.nslots, &lo, &hi)) mt_flag(a.status, KC_ST_OFFSETS);
     const int k = a.cand_kf[i];
-    if (k < 0 || k >= a.nkf) kc_flag(a, KC_ST_INDEX);
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, KC_ST_INDEX);
   }
 }
 
@@ -110,12 +102,12 @@ __global__ __launch_bounds__(KC_WG) void k_cull_count(CullArgs a) {
   const int p = c >= 0 ? a.slot_pt[s] : -1, l = c >= 0 ? a.slot_level[s] : 0;
   const bool kok = k >= 0 && k < a.nkf, pok = p >= 0 && p < a.npts;
   if (kok && r == 0) {
-    if (!pok) kc_flag(a, KC_ST_INDEX);
-    if (l < 0) kc_flag(a, KC_ST_LEVEL);
+    if (!pok) mt_flag(a.status, KC_ST_INDEX);
+    if (l < 0) mt_flag(a.status, KC_ST_LEVEL);
   }
   const bool ok = kok && pok && l >= 0;
   int lo = 0, hi = 0;
-  if (ok) kc_range(a.obs_off, p, a.nobs, &lo, &hi);
+  if (ok) mt_range(a.obs_off, p, a.nobs, &lo, &hi);
   const bool is_long = hi - lo > 64;
   int count = 0, mine = KC_NONE;
   if (!is_long) kc_scan(a, lo, hi, r, G, k, l, &count, &mine);
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(KC_WG) void k_cull_count(CullArgs a) {
 // observer's slots lose one from their count when the erased level is within their reach.
 __device__ __forceinline__ void kc_walk(const CullArgs& a, int p, int k, int lvl, bool now_bad, int first, int stride) {
   int lo, hi;
-  kc_range(a.obs_off, p, a.nobs, &lo, &hi);
+  mt_range(a.obs_off, p, a.nobs, &lo, &hi);
   for (int e = lo + first; e < hi; e += stride) {
     if (now_bad) { a.dead[e] = 1; continue; }
     if (a.dead[e] || a.obs_kf[e] == k) continue;
@@ -163,7 +155,7 @@ __global__ __launch_bounds__(KC_RWG) void k_cull_resolve(CullArgs a) {
       continue;
     }
     int lo, hi;
-    kc_range(a.slot_off, c, a.nslots, &lo, &hi);
+    mt_range(a.slot_off, c, a.nslots, &lo, &hi);
     int red = 0, mp = 0;
     for (int s = lo + tid; s < hi; s += KC_RWG) {                   // (:595-631) under the state the culls so far have left
       const int p = a.spt[s];

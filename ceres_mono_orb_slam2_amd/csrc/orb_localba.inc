@@ -6,8 +6,8 @@
 // sum is taken in the order written here (DESIGN.md section 2, "LocalBundleAdjustment on the tables").
 //
 // assemble: every list is an ORDERED compaction.  A flag per element is laid out in the order of the list (keyframe id, kf_rank,
-// pt_rank), an exclusive scan gives each flagged element its place (k_la_*scan: per workgroup, then the workgroup sums by one
-// workgroup), and the element's own lane writes it there.  Atomics only take order-free minima, maxima and ors.
+// pt_rank), an exclusive scan gives each flagged element its place (k_la_*scan: mt_block_excl per workgroup, then the workgroup sums by
+// k_mt_scan_sums), and the element's own lane writes it there.  Atomics only take order-free minima, maxima and ors.
 //   k_la_stamp       one lane per list position / keyframe / point: first[k] = the least position of (cur_kf, nbr_kf...) that names
 //                    keyframe k (atomicMin), the inverses of the two ranks (atomicMax: a repeat is flagged), the offset checks
 //   k_la_local       one lane per list position: kf_role 1 / 3, the place among the local cameras by counting the (kf_id, position)
@@ -20,24 +20,11 @@
 //   k_ap_mark        one lane per row: want[e] = the first row that erases observation e (atomicMin)
 //   k_ap_erase       one lane per point: its marked observations in row order, the reference keyframe, the bad flag and its cascade
 //   k_ap_write       one lane per camera / local point: SetPose with the centre, SetWorldPos
-//   k_ap_normals     one lane per local point: UpdateNormalAndDepth over the alive observations, the new centres
+//   k_ap_normals     one lane per local point: UpdateNormalAndDepth (mt_normal_depth) over the alive observations, the new centres
 // Outputs are written with vector stores only.
+#include "orb_maptable.h"        /* LA_WG, the LA_ST_* bits of *status (orbl_local_ba_assemble_device, orbl_local_ba_apply_device), LA_NONE */
+
 namespace orbhip {
-
-#define LA_WG 256
-#define LA_SUM_WG 1024            /* k_la_scan_sums: one workgroup */
-#define LA_ST_OFFSETS 1u          /* *status bits of orbl_local_ba_assemble_device and orbl_local_ba_apply_device */
-#define LA_ST_KF 2u
-#define LA_ST_PT 4u
-#define LA_ST_RANK 8u
-#define LA_ST_LEVEL 16u
-#define LA_ST_CAP_CAM 32u
-#define LA_ST_CAP_PTS 64u
-#define LA_ST_CAP_OBS 128u
-#define LA_ST_OBS 256u            /* apply: a row names an observation out of range, or an observation a slot its keyframe does not have */
-#define LA_NONE 0xFFFFFFFFu
-
-typedef unsigned long long la_u64;
 
 struct LaArgs {
   int cur_kf, n_nbr, nkf, nslots, npts, nobs, n_levels, cap_cam, cap_pts, cap_obs, nbk, nbp;
@@ -48,10 +35,9 @@ struct LaArgs {
   int32_t* lobs_cam; int32_t* lobs_pt; double* lobs_uv; float* lobs_isg; int32_t* lobs_src; uint8_t* kf_role; uint8_t* pt_local; uint32_t* status;
   // workspace: first[nkf] | inv_kf[nkf] | inv_pt[npts] | cam_of[nkf] (all set to all ones per call) | fixed[nkf] (cleared per call) |
   // kscan[nkf] | ksums[nbk + 1] | pscan[npts] | psums[nbp + 1] | meta[4]
-  uint32_t* first; int32_t* inv_kf; int32_t* inv_pt; int32_t* cam_of; uint8_t* fixed; la_u64 *kscan, *ksums, *pscan, *psums; int32_t* meta;
+  uint32_t* first; int32_t* inv_kf; int32_t* inv_pt; int32_t* cam_of; uint8_t* fixed; mt_u64 *kscan, *ksums, *pscan, *psums; int32_t* meta;
 };
 
-__device__ __forceinline__ void la_flag(uint32_t* status, uint32_t bits) { if (status) atomicOr(status, bits); }
 __device__ __forceinline__ bool la_kf_bad(const LaArgs& a, int k) { return a.kf_bad && a.kf_bad[k]; }
 __device__ __forceinline__ int la_kf_at(const LaArgs& a, int pos) { return pos == 0 ? a.cur_kf : a.nbr_kf[pos - 1]; }
 // the keyframe of list position q when that position is where the list first names it and it becomes a local camera, else -1
@@ -60,63 +46,30 @@ __device__ __forceinline__ int la_local_at(const LaArgs& a, int q) {
   if (k < 0 || k >= a.nkf || a.first[k] != (uint32_t)q) return -1;
   return (q == 0 || !la_kf_bad(a, k)) ? k : -1;                                // (:359: a bad neighbour is stamped, not collected)
 }
-__device__ __forceinline__ bool la_range_ok(const int32_t* off, int i, int n, int* lo, int* hi) {
-  *lo = off[i]; *hi = off[i + 1];
-  return *lo >= 0 && *lo <= *hi && *hi <= n;
-}
-
-// exclusive scan of one value per lane across the workgroup (blockDim.x a multiple of 64, at most 1024); *total = the workgroup's sum
-__device__ __forceinline__ la_u64 la_block_excl(la_u64 v, la_u64* sw, la_u64* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  la_u64 incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const la_u64 u = __shfl_up(incl, o); if (lane >= o) incl += u; }
-  if (lane == 63) sw[w] = incl;
-  __syncthreads();
-  la_u64 base = 0, tot = 0;
-  for (int q = 0; q < nw; q++) { const la_u64 s = sw[q]; if (q < w) base += s; tot += s; }
-  __syncthreads();                                                              // (sw is free for the next call)
-  *total = tot;
-  return base + (incl - v);
-}
-
-// ONE workgroup: sums[0..nb) -> their exclusive scan, sums[nb] = the total
-__global__ __launch_bounds__(LA_SUM_WG) void k_la_scan_sums(la_u64* sums, int nb) {
-  __shared__ la_u64 sw[LA_SUM_WG / 64];
-  la_u64 carry = 0;
-  for (int b0 = 0; b0 < nb; b0 += LA_SUM_WG) {                                  // (workgroup-uniform)
-    const int i = b0 + (int)threadIdx.x;
-    la_u64 tot;
-    const la_u64 ex = la_block_excl(i < nb ? sums[i] : 0ull, sw, &tot);
-    if (i < nb) sums[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) sums[nb] = carry;
-}
 
 __global__ __launch_bounds__(LA_WG) void k_la_stamp(LaArgs a) {
   const int i = blockIdx.x * LA_WG + threadIdx.x;
   if (i <= a.n_nbr) {
     const int k = la_kf_at(a, i);
-    if (k < 0 || k >= a.nkf) la_flag(a.status, LA_ST_KF);
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, LA_ST_KF);
     else atomicMin(&a.first[k], (uint32_t)i);
   }
   if (i < a.nkf) {
     int lo, hi;
-    if (!la_range_ok(a.slot_off, i, a.nslots, &lo, &hi)) la_flag(a.status, LA_ST_OFFSETS);
+    if (!mt_range(a.slot_off, i, a.nslots, &lo, &hi)) mt_flag(a.status, LA_ST_OFFSETS);
     if (a.kf_rank) {
       const int r = a.kf_rank[i];
-      if (r < 0 || r >= a.nkf) la_flag(a.status, LA_ST_RANK);
-      else if (atomicMax(&a.inv_kf[r], i) != -1) la_flag(a.status, LA_ST_RANK);  // (not a permutation: the highest index holds the place)
+      if (r < 0 || r >= a.nkf) mt_flag(a.status, LA_ST_RANK);
+      else if (atomicMax(&a.inv_kf[r], i) != -1) mt_flag(a.status, LA_ST_RANK);  // (not a permutation: the highest index holds the place)
     }
   }
   if (i < a.npts) {
     int lo, hi;
-    if (!la_range_ok(a.obs_off, i, a.nobs, &lo, &hi)) la_flag(a.status, LA_ST_OFFSETS);
+    if (!mt_range(a.obs_off, i, a.nobs, &lo, &hi)) mt_flag(a.status, LA_ST_OFFSETS);
     if (a.pt_rank) {
       const int r = a.pt_rank[i];
-      if (r < 0 || r >= a.npts) la_flag(a.status, LA_ST_RANK);
-      else if (atomicMax(&a.inv_pt[r], i) != -1) la_flag(a.status, LA_ST_RANK);
+      if (r < 0 || r >= a.npts) mt_flag(a.status, LA_ST_RANK);
+      else if (atomicMax(&a.inv_pt[r], i) != -1) mt_flag(a.status, LA_ST_RANK);
     }
   }
 }
@@ -125,12 +78,7 @@ __global__ __launch_bounds__(LA_WG) void k_la_stamp(LaArgs a) {
 __device__ __forceinline__ void la_write_cam(const LaArgs& a, int c, int k, bool local) {
   a.cam_of[k] = c;
   if (c >= a.cap_cam) return;
-  const double* T = a.kf_Tcw + 12 * (size_t)k;
-  const double m[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
-  double q[4];
-  rot_to_quat(m, q);
-  double* o = a.poses7 + 7 * (size_t)c;
-  o[0] = T[3]; o[1] = T[7]; o[2] = T[11]; o[3] = q[0]; o[4] = q[1]; o[5] = q[2]; o[6] = q[3];
+  mt_pose34_to_pose7(a.kf_Tcw + 12 * (size_t)k, a.poses7 + 7 * (size_t)c);
   for (int j = 0; j < 4; j++) a.K4[4 * (size_t)c + j] = a.kf_K4[4 * (size_t)k + j];
   a.cam_kf[c] = k;
   a.cam_local[c] = local ? 1 : 0;
@@ -162,10 +110,10 @@ __global__ __launch_bounds__(LA_WG) void k_la_slots(LaArgs a) {
   const int k = la_local_at(a, (int)blockIdx.x);                               // (workgroup-uniform)
   if (k < 0) return;
   int lo, hi;
-  if (!la_range_ok(a.slot_off, k, a.nslots, &lo, &hi)) return;
+  if (!mt_range(a.slot_off, k, a.nslots, &lo, &hi)) return;
   for (int s = lo + (int)threadIdx.x; s < hi; s += LA_WG) {
     const int p = a.slot_pt[s];
-    if (p < -1 || p >= a.npts) { la_flag(a.status, LA_ST_PT); continue; }
+    if (p < -1 || p >= a.npts) { mt_flag(a.status, LA_ST_PT); continue; }
     if (p >= 0 && !(a.pt_bad && a.pt_bad[p])) a.pt_local[p] = 1;               // (:375-380)
   }
 }
@@ -174,10 +122,10 @@ __global__ __launch_bounds__(LA_WG) void k_la_fixed(LaArgs a) {
   const int p = blockIdx.x * LA_WG + threadIdx.x;
   if (p >= a.npts || !a.pt_local[p]) return;
   int lo, hi;
-  if (!la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) return;
+  if (!mt_range(a.obs_off, p, a.nobs, &lo, &hi)) return;
   for (int e = lo; e < hi; e++) {                                              // (:389-405)
     const int k = a.obs_kf[e];
-    if (k < 0 || k >= a.nkf) { la_flag(a.status, LA_ST_KF); continue; }
+    if (k < 0 || k >= a.nkf) { mt_flag(a.status, LA_ST_KF); continue; }
     if (a.kf_role[k] == 0 && !la_kf_bad(a, k)) a.fixed[k] = 1;
   }
 }
@@ -186,11 +134,11 @@ __device__ __forceinline__ int la_kf_of_rank(const LaArgs& a, int r) { return a.
 __device__ __forceinline__ int la_pt_of_rank(const LaArgs& a, int r) { return a.pt_rank ? a.inv_pt[r] : r; }
 
 __global__ __launch_bounds__(LA_WG) void k_la_kscan(LaArgs a) {
-  __shared__ la_u64 sw[LA_WG / 64];
+  __shared__ mt_u64 sw[LA_WG / 64];
   const int r = blockIdx.x * LA_WG + threadIdx.x;
   const int k = r < a.nkf ? la_kf_of_rank(a, r) : -1;
-  la_u64 tot;
-  const la_u64 ex = la_block_excl(k >= 0 && a.fixed[k] ? 1ull : 0ull, sw, &tot);
+  mt_u64 tot;
+  const mt_u64 ex = mt_block_excl<LA_WG>(k >= 0 && a.fixed[k] ? 1ull : 0ull, sw, &tot);
   if (r < a.nkf) a.kscan[r] = ex;
   if (threadIdx.x == 0) a.ksums[blockIdx.x] = tot;
 }
@@ -202,7 +150,7 @@ __global__ __launch_bounds__(LA_WG) void k_la_fixed_cams(LaArgs a) {
   if (r == 0) {
     const int ncam = n_local + (int)a.ksums[a.nbk];
     a.counts[0] = ncam; a.counts[1] = n_local;
-    if (ncam > a.cap_cam) la_flag(a.status, LA_ST_CAP_CAM);
+    if (ncam > a.cap_cam) mt_flag(a.status, LA_ST_CAP_CAM);
   }
   const int k = la_kf_of_rank(a, r);
   if (k < 0 || !a.fixed[k]) return;
@@ -212,27 +160,22 @@ __global__ __launch_bounds__(LA_WG) void k_la_fixed_cams(LaArgs a) {
 
 // whether observation e of a local point becomes a row: its keyframe is not bad and has a camera (:432, :458, :483)
 __device__ __forceinline__ bool la_row_ok(const LaArgs& a, int e) {
-  const int k = a.obs_kf[e];
-  if (k < 0 || k >= a.nkf) { la_flag(a.status, LA_ST_KF); return false; }
-  if (la_kf_bad(a, k) || a.cam_of[k] < 0) return false;
-  const int lvl = a.obs_level[e];
-  if (lvl < 0 || lvl >= a.n_levels) { la_flag(a.status, LA_ST_LEVEL); return false; }
-  return true;
+  return mt_row_ok(a.obs_kf, a.obs_level, e, a.nkf, a.n_levels, a.kf_bad, a.cam_of, a.status, LA_ST_KF, LA_ST_LEVEL);
 }
 
 __global__ __launch_bounds__(LA_WG) void k_la_pscan(LaArgs a) {
-  __shared__ la_u64 sw[LA_WG / 64];
+  __shared__ mt_u64 sw[LA_WG / 64];
   const int r = blockIdx.x * LA_WG + threadIdx.x;
   const int p = r < a.npts ? la_pt_of_rank(a, r) : -1;
-  la_u64 v = 0;
+  mt_u64 v = 0;
   if (p >= 0 && a.pt_local[p]) {
     int lo, hi, rows = 0;
-    if (la_range_ok(a.obs_off, p, a.nobs, &lo, &hi))
+    if (mt_range(a.obs_off, p, a.nobs, &lo, &hi))
       for (int e = lo; e < hi; e++) rows += la_row_ok(a, e) ? 1 : 0;
-    v = ((la_u64)(uint32_t)rows << 32) | 1ull;                                  // (rows, points): neither sum reaches 2^31
+    v = ((mt_u64)(uint32_t)rows << 32) | 1ull;                                  // (rows, points): neither sum reaches 2^31
   }
-  la_u64 tot;
-  const la_u64 ex = la_block_excl(v, sw, &tot);
+  mt_u64 tot;
+  const mt_u64 ex = mt_block_excl<LA_WG>(v, sw, &tot);
   if (r < a.npts) a.pscan[r] = ex;
   if (threadIdx.x == 0) a.psums[blockIdx.x] = tot;
 }
@@ -241,15 +184,15 @@ __global__ __launch_bounds__(LA_WG) void k_la_emit(LaArgs a) {
   const int r = blockIdx.x * LA_WG + threadIdx.x;
   if (r >= a.npts) return;
   if (r == 0) {
-    const la_u64 t = a.psums[a.nbp];
+    const mt_u64 t = a.psums[a.nbp];
     const int np = (int)(uint32_t)t, no = (int)(t >> 32);
     a.counts[2] = np; a.counts[3] = no;
-    if (np > a.cap_pts) la_flag(a.status, LA_ST_CAP_PTS);
-    if (no > a.cap_obs) la_flag(a.status, LA_ST_CAP_OBS);
+    if (np > a.cap_pts) mt_flag(a.status, LA_ST_CAP_PTS);
+    if (no > a.cap_obs) mt_flag(a.status, LA_ST_CAP_OBS);
   }
   const int p = la_pt_of_rank(a, r);
   if (p < 0 || !a.pt_local[p]) return;
-  const la_u64 at = a.pscan[r] + a.psums[blockIdx.x];
+  const mt_u64 at = a.pscan[r] + a.psums[blockIdx.x];
   const int j = (int)(uint32_t)at;
   int row = (int)(at >> 32);
   if (j < a.cap_pts) {
@@ -257,7 +200,7 @@ __global__ __launch_bounds__(LA_WG) void k_la_emit(LaArgs a) {
     for (int q = 0; q < 3; q++) a.pts3[3 * (size_t)j + q] = a.X[3 * (size_t)p + q];
   }
   int lo, hi;
-  if (!la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) return;
+  if (!mt_range(a.obs_off, p, a.nobs, &lo, &hi)) return;
   for (int e = lo; e < hi; e++) {
     if (!la_row_ok(a, e)) continue;
     if (row < a.cap_obs) {
@@ -298,7 +241,7 @@ __global__ __launch_bounds__(LA_WG) void k_ap_mark(ApArgs a) {
   const int i = blockIdx.x * LA_WG + threadIdx.x;
   if (i >= a.nobs_local || !a.obs_erase[i]) return;
   const int e = a.lobs_src[i];
-  if (e < 0 || e >= a.nobs) { la_flag(a.status, LA_ST_OBS); return; }
+  if (e < 0 || e >= a.nobs) { mt_flag(a.status, LA_ST_OBS); return; }
   atomicMin(&a.want[e], (uint32_t)i);                                          // (a later row on the same observation finds it dead)
 }
 
@@ -306,25 +249,19 @@ __global__ __launch_bounds__(LA_WG) void k_ap_mark(ApArgs a) {
 __device__ __forceinline__ void ap_kill(const ApArgs& a, int e) {
   a.obs_erased[e] = 1;
   const int k = a.obs_kf[e];
-  if (k < 0 || k >= a.nkf) { la_flag(a.status, LA_ST_KF); return; }
+  if (k < 0 || k >= a.nkf) { mt_flag(a.status, LA_ST_KF); return; }
   int lo, hi;
-  if (!la_range_ok(a.slot_off, k, a.nslots, &lo, &hi)) { la_flag(a.status, LA_ST_OFFSETS); return; }
+  if (!mt_range(a.slot_off, k, a.nslots, &lo, &hi)) { mt_flag(a.status, LA_ST_OFFSETS); return; }
   const int s = a.obs_slot[e];
-  if (s < 0 || s >= hi - lo) { la_flag(a.status, LA_ST_OBS); return; }
+  if (s < 0 || s >= hi - lo) { mt_flag(a.status, LA_ST_OBS); return; }
   a.slot_pt[lo + s] = -1;
-}
-
-__device__ __forceinline__ int ap_wave_sum(int v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 __global__ __launch_bounds__(LA_WG) void k_ap_erase(ApArgs a) {
   const int p = blockIdx.x * LA_WG + threadIdx.x;
   int n_erased = 0, n_dead = 0, n_bad = 0;
   int lo = 0, hi = 0;
-  if (p < a.npts && !la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) { la_flag(a.status, LA_ST_OFFSETS); hi = lo = 0; }
+  if (p < a.npts && !mt_range(a.obs_off, p, a.nobs, &lo, &hi)) mt_flag(a.status, LA_ST_OFFSETS);
   if (lo < hi) {
     int nobs = a.pt_nobs[p], ref = a.pt_ref_kf[p];
     long long prev = -1;
@@ -346,7 +283,7 @@ __global__ __launch_bounds__(LA_WG) void k_ap_erase(ApArgs a) {
     }
     if (n_erased) { a.pt_nobs[p] = nobs; a.pt_ref_kf[p] = ref; }
   }
-  n_erased = ap_wave_sum(n_erased); n_dead = ap_wave_sum(n_dead); n_bad = ap_wave_sum(n_bad);
+  n_erased = mt_wave_sum(n_erased); n_dead = mt_wave_sum(n_dead); n_bad = mt_wave_sum(n_bad);
   if ((threadIdx.x & 63) == 0) {
     if (n_erased) atomicAdd(&a.counts[0], n_erased);
     if (n_bad) atomicAdd(&a.counts[1], n_bad);
@@ -358,21 +295,16 @@ __global__ __launch_bounds__(LA_WG) void k_ap_write(ApArgs a) {
   const int i = blockIdx.x * LA_WG + threadIdx.x;
   if (i < a.ncam && a.cam_local[i]) {                                          // (:585-591) Matrix_7_1_ToMatrix4d (ba_pose7_to_matrix4d), KeyFrame::SetPose
     const int k = a.cam_kf[i];
-    if (k < 0 || k >= a.nkf) la_flag(a.status, LA_ST_KF);
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, LA_ST_KF);
     else {
-      const double* s = a.poses7 + 7 * (size_t)i;
-      const double n = sqrt(((s[3] * s[3] + s[4] * s[4]) + s[5] * s[5]) + s[6] * s[6]);
-      const double q[4] = {s[3] / n, s[4] / n, s[5] / n, s[6] / n};
-      double R[9], T[12], Twc[12];
-      quat_to_R(q, R);
-      for (int r = 0; r < 3; r++) { T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2]; T[4 * r + 3] = s[r]; }
-      for (int j = 0; j < 12; j++) a.kf_Tcw[12 * (size_t)k + j] = T[j];
-      if (a.kf_center) { mc_pose_inverse(T, Twc); for (int j = 0; j < 3; j++) a.kf_center[3 * (size_t)k + j] = Twc[4 * j + 3]; }
+      double T[12];
+      mt_pose7_to_pose34(a.poses7 + 7 * (size_t)i, T);
+      mt_set_pose(a.kf_Tcw, a.kf_center, k, T);
     }
   }
   if (i < a.npts_local) {                                                      // (:596) SetWorldPos, bad points included
     const int p = a.lpt_pt[i];
-    if (p < 0 || p >= a.npts) la_flag(a.status, LA_ST_PT);
+    if (p < 0 || p >= a.npts) mt_flag(a.status, LA_ST_PT);
     else for (int j = 0; j < 3; j++) a.X[3 * (size_t)p + j] = a.pts3[3 * (size_t)i + j];
   }
 }
@@ -382,39 +314,17 @@ __global__ __launch_bounds__(LA_WG) void k_ap_normals(ApArgs a) {
   int wrote = 0;
   const int p = j < a.npts_local ? a.lpt_pt[j] : -1;
   int lo = 0, hi = 0;
-  if (p >= 0 && p < a.npts && !a.pt_bad[p] && la_range_ok(a.obs_off, p, a.nobs, &lo, &hi)) {       // (src/MapPoint.cc:342)
-    const double x = a.X[3 * (size_t)p], y = a.X[3 * (size_t)p + 1], z = a.X[3 * (size_t)p + 2];
+  if (p >= 0 && p < a.npts && !a.pt_bad[p] && mt_range(a.obs_off, p, a.nobs, &lo, &hi)) {       // (src/MapPoint.cc:342)
     const int ref = a.pt_ref_kf[p];
-    double nx = 0.0, ny = 0.0, nz = 0.0;
-    int n = 0, lvl = -1;
-    bool ok = true;
-    for (int e = lo; e < hi; e++) {                                            // k_mp_prep's walk over what is alive (:352-360)
-      if (a.obs_erased[e]) continue;
-      const int k = a.obs_kf[e];
-      if (k < 0 || k >= a.nkf) { ok = false; la_flag(a.status, LA_ST_KF); break; }
-      const double vx = x - a.kf_center[3 * (size_t)k], vy = y - a.kf_center[3 * (size_t)k + 1], vz = z - a.kf_center[3 * (size_t)k + 2];
-      const double nn = sqrt((vx * vx + vy * vy) + vz * vz);
-      nx = nx + vx / nn; ny = ny + vy / nn; nz = nz + vz / nn;
-      n++;
-      if (k == ref) lvl = a.obs_level[e];
-    }
-    if (ok && n > 0) {                                                         // (:348)
-      if (ref < 0 || ref >= a.nkf) { ok = false; la_flag(a.status, LA_ST_KF); }
-      else if (lvl == -1) lvl = a.kf_level0 ? a.kf_level0[ref] : 0;            // (:366: operator[] on the copy inserts index 0)
-      if (ok && (lvl < 0 || lvl >= a.n_levels)) { ok = false; la_flag(a.status, LA_ST_LEVEL); }
-      if (ok) {
-        const double dn = (double)n;
-        double* nv = a.normal + 3 * (size_t)p;
-        nv[0] = nx / dn; nv[1] = ny / dn; nv[2] = nz / dn;
-        const double px = x - a.kf_center[3 * (size_t)ref], py = y - a.kf_center[3 * (size_t)ref + 1], pz = z - a.kf_center[3 * (size_t)ref + 2];
-        const float dist = (float)sqrt((px * px + py * py) + pz * pz);
-        const float mx = dist * a.scale_factors[lvl];
-        a.min_max[2 * (size_t)p] = mx / a.scale_factors[a.n_levels - 1];
-        a.min_max[2 * (size_t)p + 1] = mx;
-        a.nd_written[p] = 1;
-        wrote = 1;
-      }
-    }
+    // over what is alive (:352-360); the level is that of the reference keyframe's own observation, and without one operator[] on the
+    // copy of the observations inserts index 0 (:366)
+    const int res = mt_normal_depth(a.obs_kf, lo, hi, a.nkf, a.X[3 * (size_t)p], a.X[3 * (size_t)p + 1], a.X[3 * (size_t)p + 2], ref, a.scale_factors, a.n_levels,
+                                    a.normal + 3 * (size_t)p, a.min_max + 2 * (size_t)p, [&](int e) { return !a.obs_erased[e]; },
+                                    [&](int k) { return make_double3(a.kf_center[3 * (size_t)k], a.kf_center[3 * (size_t)k + 1], a.kf_center[3 * (size_t)k + 2]); },
+                                    [&](int e) { const int l = e >= 0 ? a.obs_level[e] : -1; return l != -1 ? l : a.kf_level0 ? a.kf_level0[ref] : 0; });
+    if (res == MT_ND_KF || res == MT_ND_REF) mt_flag(a.status, LA_ST_KF);
+    if (res == MT_ND_LEVEL) mt_flag(a.status, LA_ST_LEVEL);
+    if (res == MT_ND_OK) { a.nd_written[p] = 1; wrote = 1; }
   }
   const uint64_t m = __ballot(wrote != 0);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.counts[3], (int)__popcll(m));
@@ -468,7 +378,7 @@ int orbl_local_ba_assemble_device(int cur_kf, int n_nbr, const int32_t* nbr_kf, 
   A.lobs_cam = lobs_cam; A.lobs_pt = lobs_pt; A.lobs_uv = lobs_uv; A.lobs_isg = lobs_inv_sigma2; A.lobs_src = lobs_src; A.kf_role = kf_role; A.pt_local = pt_local;
   A.status = status;
   A.first = (uint32_t*)(wb + ws.first); A.inv_kf = (int32_t*)(wb + ws.inv_kf); A.inv_pt = (int32_t*)(wb + ws.inv_pt); A.cam_of = (int32_t*)(wb + ws.cam_of);
-  A.fixed = wb + ws.fixed; A.kscan = (la_u64*)(wb + ws.kscan); A.ksums = (la_u64*)(wb + ws.ksums); A.pscan = (la_u64*)(wb + ws.pscan); A.psums = (la_u64*)(wb + ws.psums);
+  A.fixed = wb + ws.fixed; A.kscan = (mt_u64*)(wb + ws.kscan); A.ksums = (mt_u64*)(wb + ws.ksums); A.pscan = (mt_u64*)(wb + ws.pscan); A.psums = (mt_u64*)(wb + ws.psums);
   A.meta = (int32_t*)(wb + ws.meta);
   hipStream_t st = (hipStream_t)stream;
   if (status) ORBHIP_CHECK_HIP(hipMemsetAsync(status, 0, 4, st));
@@ -483,11 +393,11 @@ int orbl_local_ba_assemble_device(int cur_kf, int n_nbr, const int32_t* nbr_kf, 
   if (nslots > 0 && npts > 0) hipLaunchKernelGGL(k_la_slots, dim3((unsigned)(n_nbr + 1)), dim3(LA_WG), 0, st, A);
   if (npts > 0) hipLaunchKernelGGL(k_la_fixed, grid(npts), dim3(LA_WG), 0, st, A);
   hipLaunchKernelGGL(k_la_kscan, grid(nkf), dim3(LA_WG), 0, st, A);
-  hipLaunchKernelGGL(k_la_scan_sums, dim3(1), dim3(LA_SUM_WG), 0, st, A.ksums, A.nbk);
+  hipLaunchKernelGGL(k_mt_scan_sums<mt_u64>, dim3(1), dim3(MT_SUM_WG), 0, st, A.ksums, A.nbk);
   hipLaunchKernelGGL(k_la_fixed_cams, grid(nkf), dim3(LA_WG), 0, st, A);
   if (npts > 0) {
     hipLaunchKernelGGL(k_la_pscan, grid(npts), dim3(LA_WG), 0, st, A);
-    hipLaunchKernelGGL(k_la_scan_sums, dim3(1), dim3(LA_SUM_WG), 0, st, A.psums, A.nbp);
+    hipLaunchKernelGGL(k_mt_scan_sums<mt_u64>, dim3(1), dim3(MT_SUM_WG), 0, st, A.psums, A.nbp);
     hipLaunchKernelGGL(k_la_emit, grid(npts), dim3(LA_WG), 0, st, A);
   }
   ORBHIP_CHECK_HIP(hipGetLastError());

@@ -11,7 +11,7 @@
 //     k_ml_pose    one lane per connected keyframe: both Sim3, the inverse of the corrected one, the new pose and centre (to the workspace:
 //                  the tables still hold the values at entry, which the other lanes and the point kernel read)
 //     k_ml_slots   one lane per slot, twice: the owner; then whether a second keyframe lists the point
-//     k_ml_points  one lane per point: the new position, the normal / depth walk of k_mp_prep with the centre rule above
+//     k_ml_points  one lane per point: the new position, the normal / depth walk (mt_normal_depth) with the centre rule above
 //                  (both centres are loaded and one is picked by value: DESIGN.md section 2 says why)
 //     k_ml_store   one lane per connected keyframe: the new pose and centre into the tables
 //   propagate_global_ba   a keyframe's matrix needs its parent's, so k_gb_walk is ONE workgroup that advances one tree level per round
@@ -21,6 +21,9 @@
 //     k_gb_apply   one lane per keyframe: bef = Tcw, Tcw = gba, the centre, the flags
 //     k_gb_points  one lane per point
 // Outputs are written with vector stores only, each element by the one lane that owns it.
+#include "orb_maptable.h"
+#include "sim3_math.h"
+
 namespace orbhip {
 
 #define MC_WG 256
@@ -36,37 +39,6 @@ namespace orbhip {
 #define GB_ST_STALE 4u
 #define MC_NONE 0xFFFFFFFFFFFFFFFFull
 
-#define MC_HD __host__ __device__ __forceinline__
-
-// C = A o B for row-major 3x4 matrices standing for 4x4 ones with the last row 0 0 0 1; every sum in index order k = 0..3
-MC_HD void mc_affine_mul(const double* A, const double* B, double* C) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 4; j++) {
-      const double b3 = j == 3 ? 1.0 : 0.0;
-      C[4 * i + j] = ((A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j]) + A[4 * i + 2] * B[8 + j]) + A[4 * i + 3] * b3;
-    }
-}
-
-// Twc as KeyFrame::SetPose stores it (src/KeyFrame.cc:119-130): Rwc = Rcw^T, Ow = -(Rwc tcw); the centre is its last column
-MC_HD void mc_pose_inverse(const double* T, double* Twc) {
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) Twc[4 * i + j] = T[4 * j + i];
-    Twc[4 * i + 3] = -((T[i] * T[3] + T[4 + i] * T[7]) + T[8 + i] * T[11]);
-  }
-}
-
-// Sophus::Sim3d(Sophus::RxSO3d(1.0, R), t): the codec's matrix -> quaternion branches, un-normalised, scale 1
-MC_HD void mc_se3_as_sim3(const double* T, double* S) {
-  const double m[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
-  rot_to_quat(m, S);
-  S[4] = T[3]; S[5] = T[7]; S[6] = T[11];
-}
-
-// R x + t, each row (r0 x + r1 y) + r2 z, then + t
-MC_HD void mc_apply34(const double* T, const double* x, double* out) {
-  for (int i = 0; i < 3; i++) out[i] = ((T[4 * i] * x[0] + T[4 * i + 1] * x[1]) + T[4 * i + 2] * x[2]) + T[4 * i + 3];
-}
-
 // ---------------------------------------------------------------------------------------------------------- CorrectLoop
 struct MlArgs {
   int nkf, nconn, nslots, npts, nobs, n_levels;
@@ -79,32 +51,28 @@ struct MlArgs {
   int32_t *kpos, *rhit, *cval; unsigned long long* own; uint8_t* contested; double *cinv, *newT, *newC;
 };
 
-__device__ __forceinline__ void ml_flag(const MlArgs& a, uint32_t bits) { if (a.status) atomicOr(a.status, bits); }
 __device__ __forceinline__ uint32_t ml_rank(const MlArgs& a, int c) { return (uint32_t)(a.conn_rank ? a.conn_rank[c] : c); }
 __device__ __forceinline__ bool ml_takes_part(const MlArgs& a, int p) { return !(a.pt_bad && a.pt_bad[p]) && !(a.pt_done && a.pt_done[p]); }
 
 __global__ __launch_bounds__(MC_WG) void k_ml_init(MlArgs a) {
   const int i = blockIdx.x * MC_WG + threadIdx.x;
+  int lo, hi;
   if (i < a.nconn) {
-    const int l = a.slot_off[i], h = a.slot_off[i + 1];
-    if (!(l >= 0 && l <= h && h <= a.nslots)) ml_flag(a, ML_ST_OFFSETS);
+    if (!mt_range(a.slot_off, i, a.nslots, &lo, &hi)) mt_flag(a.status, ML_ST_OFFSETS);
     const int k = a.conn_kf[i];
-    if (k < 0 || k >= a.nkf) ml_flag(a, ML_ST_KF);
-    else if (atomicMax(&a.kpos[k], i) != -1) ml_flag(a, ML_ST_KF);            // (a keyframe listed twice: its last instance counts)
+    if (k < 0 || k >= a.nkf) mt_flag(a.status, ML_ST_KF);
+    else if (atomicMax(&a.kpos[k], i) != -1) mt_flag(a.status, ML_ST_KF);            // (a keyframe listed twice: its last instance counts)
     if (a.conn_rank) {
       const int r = a.conn_rank[i];
-      if (r < 0 || r >= a.nconn) ml_flag(a, ML_ST_RANK);
-      else if (atomicAdd(&a.rhit[r], 1) != 0) ml_flag(a, ML_ST_RANK);          // (not a permutation)
+      if (r < 0 || r >= a.nconn) mt_flag(a.status, ML_ST_RANK);
+      else if (atomicAdd(&a.rhit[r], 1) != 0) mt_flag(a.status, ML_ST_RANK);          // (not a permutation)
     }
   }
-  if (i < a.npts && a.obs_off) {
-    const int l = a.obs_off[i], h = a.obs_off[i + 1];
-    if (!(l >= 0 && l <= h && h <= a.nobs)) ml_flag(a, ML_ST_OFFSETS);
-  }
+  if (i < a.npts && a.obs_off && !mt_range(a.obs_off, i, a.nobs, &lo, &hi)) mt_flag(a.status, ML_ST_OFFSETS);
   if (i == 0) {
     bool fin = true;
     for (int q = 0; q < 7; q++) fin = fin && isfinite(a.Scw[q]);
-    if (!fin || !((a.Scw[0] * a.Scw[0] + a.Scw[1] * a.Scw[1]) + (a.Scw[2] * a.Scw[2] + a.Scw[3] * a.Scw[3]) > 0.0)) ml_flag(a, ML_ST_SCW);
+    if (!fin || !((a.Scw[0] * a.Scw[0] + a.Scw[1] * a.Scw[1]) + (a.Scw[2] * a.Scw[2] + a.Scw[3] * a.Scw[3]) > 0.0)) mt_flag(a.status, ML_ST_SCW);
   }
 }
 
@@ -133,13 +101,11 @@ __global__ __launch_bounds__(MC_WG) void k_ml_pose(MlArgs a) {
     s3_mul(Sic, a.Scw, C);
   }
   for (int q = 0; q < 7; q++) Sc[q] = C[q];
-  double Ci[7], T[12], Twc[12];
+  double Ci[7], T[12];
   s3_inverse(C, Ci);                                                          // (:479)
   for (int q = 0; q < 7; q++) a.cinv[7 * (size_t)c + q] = Ci[q];
   s3_to_pose34(C, T);                                                         // (:508-516)
-  mc_pose_inverse(T, Twc);
-  for (int q = 0; q < 12; q++) a.newT[12 * (size_t)c + q] = T[q];
-  for (int q = 0; q < 3; q++) a.newC[3 * (size_t)c + q] = Twc[4 * q + 3];
+  mt_set_pose(a.newT, a.newC, c, T);
 }
 
 // the connected keyframe that holds slot s, or -1
@@ -147,9 +113,8 @@ __device__ __forceinline__ int ml_row_of(const MlArgs& a, int s) {
   int b = 0, t = a.nconn;
   while (b < t) { const int m = (b + t) >> 1; if (a.slot_off[m] <= s) b = m + 1; else t = m; }
   const int c = b - 1;
-  if (c < 0) return -1;
-  const int l = a.slot_off[c], h = a.slot_off[c + 1];
-  if (!(l >= 0 && l <= h && h <= a.nslots) || s < l || s >= h) return -1;
+  int l, h;
+  if (c < 0 || !mt_range(a.slot_off, c, a.nslots, &l, &h) || s < l || s >= h) return -1;
   return c;
 }
 
@@ -160,7 +125,7 @@ __global__ __launch_bounds__(MC_WG) void k_ml_slots(MlArgs a) {
   const int c = ml_row_of(a, s);
   if (c < 0 || !a.cval[c]) return;
   const int p = a.slot_pt[s];
-  if (p < -1 || p >= a.npts) { if (PASS == 0) ml_flag(a, ML_ST_PT); return; }
+  if (p < -1 || p >= a.npts) { if (PASS == 0) mt_flag(a.status, ML_ST_PT); return; }
   if (p < 0 || !ml_takes_part(a, p)) return;                                   // (:485-493)
   if (PASS == 0) atomicMin(&a.own[p], ((unsigned long long)ml_rank(a, c) << 32) | (uint32_t)c);
   else if ((uint32_t)a.own[p] != (uint32_t)c) a.contested[p] = 1;              // (every writer stores the same byte)
@@ -185,20 +150,15 @@ __global__ __launch_bounds__(MC_WG) void k_ml_points(MlArgs a) {
   s3_act(a.cinv + 7 * (size_t)c, Pc, Pw);
   a.X[3 * (size_t)p] = Pw[0]; a.X[3 * (size_t)p + 1] = Pw[1]; a.X[3 * (size_t)p + 2] = Pw[2];
   if (!a.nd_written) return;
-  // UpdateNormalAndDepth (:503) with k_mp_prep's arithmetic; a group keyframe of lower rank than the owner has had its SetPose (:519)
+  // UpdateNormalAndDepth (:503); a group keyframe of lower rank than the owner has had its SetPose (:519)
   uint8_t wrote = 0;
-  const int lo = a.obs_off[p], hi = a.obs_off[p + 1];
-  const bool live = lo >= 0 && lo < hi && hi <= a.nobs;
+  int lo, hi;
+  const bool live = mt_range(a.obs_off, p, a.nobs, &lo, &hi) && lo < hi;
   const int r = live ? a.ref_kf[p] : -1, lvl = live ? a.ref_level[p] : -1;
-  if (live && (r < 0 || r >= a.nkf)) ml_flag(a, ML_ST_KF);
-  if (live && (lvl < 0 || lvl >= a.n_levels)) ml_flag(a, ML_ST_LEVEL);
+  if (live && (r < 0 || r >= a.nkf)) mt_flag(a.status, ML_ST_KF);
+  if (live && (lvl < 0 || lvl >= a.n_levels)) mt_flag(a.status, ML_ST_LEVEL);
   if (r >= 0 && r < a.nkf && lvl >= 0 && lvl < a.n_levels) {
-    const double x = Pw[0], y = Pw[1], z = Pw[2];
-    double nx = 0.0, ny = 0.0, nz = 0.0;
-    bool ok = true;
-    for (int e = lo; e <= hi; e++) {                                           // (e == hi: the reference keyframe's centre)
-      const int k = e < hi ? a.obs_kf[e] : r;
-      if (k < 0 || k >= a.nkf) { ok = false; ml_flag(a, ML_ST_KF); break; }
+    const auto centre = [&](int k) {
       const int kc = a.kpos[k];
       // both centres are loaded and one is picked by value (no pointer is selected across the three-part condition)
       const int kcs = kc >= 0 ? kc : 0;
@@ -206,21 +166,12 @@ __global__ __launch_bounds__(MC_WG) void k_ml_points(MlArgs a) {
       const double* cn = a.newC + 3 * (size_t)kcs;
       const double* co = a.kf_center + 3 * (size_t)k;
       const double n0 = cn[0], n1 = cn[1], n2 = cn[2], o0 = co[0], o1 = co[1], o2 = co[2];
-      const double vx = x - (use_new ? n0 : o0), vy = y - (use_new ? n1 : o1), vz = z - (use_new ? n2 : o2);
-      const double nn = sqrt((vx * vx + vy * vy) + vz * vz);
-      if (e < hi) { nx = nx + vx / nn; ny = ny + vy / nn; nz = nz + vz / nn; }
-      else {
-        const double n = (double)(hi - lo);
-        double* nv = a.normal + 3 * (size_t)p;
-        nv[0] = nx / n; nv[1] = ny / n; nv[2] = nz / n;
-        const float dist = (float)nn;
-        const float mx = dist * a.scale_factors[lvl];
-        a.min_max[2 * (size_t)p] = mx / a.scale_factors[a.n_levels - 1];
-        a.min_max[2 * (size_t)p + 1] = mx;
-        wrote = 1;
-      }
-    }
-    (void)ok;
+      return make_double3(use_new ? n0 : o0, use_new ? n1 : o1, use_new ? n2 : o2);
+    };
+    const int res = mt_normal_depth(a.obs_kf, lo, hi, a.nkf, Pw[0], Pw[1], Pw[2], r, a.scale_factors, a.n_levels, a.normal + 3 * (size_t)p, a.min_max + 2 * (size_t)p,
+                                    [](int) { return true; }, centre, [&](int) { return lvl; });
+    if (res == MT_ND_KF) mt_flag(a.status, ML_ST_KF);
+    wrote = res == MT_ND_OK;
   }
   a.nd_written[p] = wrote;
 }
@@ -259,13 +210,11 @@ struct GbArgs {
 #define GB_READY_DONE 3           /* open, the parent was settled before this round: finished after the barrier */
 #define GB_READY_DEAD 4
 
-__device__ __forceinline__ void gb_flag(const GbArgs& a, uint32_t bits) { if (a.status) atomicOr(a.status, bits); }
-
 __global__ __launch_bounds__(MC_WG) void k_gb_origins(GbArgs a) {
   const int i = blockIdx.x * MC_WG + threadIdx.x;
   if (i >= a.n_origin) return;
   const int k = a.origin_kf[i];
-  if (k < 0 || k >= a.nkf) gb_flag(a, GB_ST_KF);
+  if (k < 0 || k >= a.nkf) mt_flag(a.status, GB_ST_KF);
   else a.state[k] = GB_DONE;                                                   // (every writer stores the same byte)
 }
 
@@ -273,8 +222,8 @@ __global__ __launch_bounds__(MC_WG) void k_gb_init(GbArgs a) {
   const int k = blockIdx.x * MC_WG + threadIdx.x;
   if (k >= a.nkf || a.state[k] == GB_DONE) return;
   const int par = a.kf_parent[k];
-  if (par < -1 || par >= a.nkf) gb_flag(a, GB_ST_KF);
-  if (par == k) gb_flag(a, GB_ST_CYCLE);
+  if (par < -1 || par >= a.nkf) mt_flag(a.status, GB_ST_KF);
+  if (par == k) mt_flag(a.status, GB_ST_CYCLE);
   if (par < 0 || par >= a.nkf || par == k) a.state[k] = GB_DEAD;
 }
 
@@ -321,13 +270,12 @@ __global__ __launch_bounds__(MC_WG) void k_gb_apply(GbArgs a) {
     if (m_p) atomicAdd(&a.counts[1], (int)__popcll(m_p));
   }
   if (k >= a.nkf) return;
-  if (st == GB_OPEN) gb_flag(a, GB_ST_CYCLE);
+  if (st == GB_OPEN) mt_flag(a.status, GB_ST_CYCLE);
   a.kf_reached[k] = reached;
   if (!reached) return;
-  double T[12], Twc[12];
+  double T[12];
   for (int q = 0; q < 12; q++) { a.kf_bef[12 * (size_t)k + q] = a.kf_Tcw[12 * (size_t)k + q]; T[q] = a.kf_gba[12 * (size_t)k + q]; }      // (:700-701)
-  for (int q = 0; q < 12; q++) a.kf_Tcw[12 * (size_t)k + q] = T[q];
-  if (a.kf_center) { mc_pose_inverse(T, Twc); for (int q = 0; q < 3; q++) a.kf_center[3 * (size_t)k + q] = Twc[4 * q + 3]; }
+  mt_set_pose(a.kf_Tcw, a.kf_center, k, T);
   if (prop) a.kf_in_gba[k] = 1;
 }
 
@@ -339,7 +287,7 @@ __global__ __launch_bounds__(MC_WG) void k_gb_points(GbArgs a) {
     if (a.pt_in_gba && a.pt_in_gba[p]) kind = 1;                               // (:713-715)
     else {
       r = a.pt_ref_kf[p];
-      if (r < 0 || r >= a.nkf) gb_flag(a, GB_ST_KF);
+      if (r < 0 || r >= a.nkf) mt_flag(a.status, GB_ST_KF);
       else if (a.kf_reached[r]) kind = 2;
       else stale = a.kf_in_gba[r] != 0;      // (flagged but not walked: the reference would read a stale global_BA_Bef_Tcw_; here the point stays)
     }
@@ -347,7 +295,7 @@ __global__ __launch_bounds__(MC_WG) void k_gb_points(GbArgs a) {
   const uint64_t m_m = __ballot(kind != 0), m_s = __ballot(stale);
   if ((threadIdx.x & 63) == 0) {
     if (m_m) atomicAdd(&a.counts[2], (int)__popcll(m_m));
-    if (m_s) { atomicAdd(&a.counts[3], (int)__popcll(m_s)); gb_flag(a, GB_ST_STALE); }
+    if (m_s) { atomicAdd(&a.counts[3], (int)__popcll(m_s)); mt_flag(a.status, GB_ST_STALE); }
   }
   if (p >= a.npts) return;
   a.pt_moved[p] = (uint8_t)kind;

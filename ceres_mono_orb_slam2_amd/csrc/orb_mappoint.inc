@@ -13,6 +13,8 @@
 //               (workgroup points), the argmin as a min of (median, row): ties go to the lowest row, as `median < best_median`.
 // Rows are numbered by LIST position (bad-keyframe entries skipped): the reference's index among the good descriptors is monotone
 // in it, so the first-minimum rule picks the same entry, and the result IS the list position the caller needs.
+#include "orb_maptable.h"
+
 namespace orbhip {
 
 #define MP_WG 256
@@ -41,35 +43,15 @@ __device__ __forceinline__ int mp_ham(const uint32_t (&own)[8], const uint32_t* 
 __global__ __launch_bounds__(MP_WG) void k_mp_prep(MpArgs a) {
   const int p = blockIdx.x * MP_WG + threadIdx.x;
   if (p >= a.npts) return;
-  const int lo = a.obs_off[p], hi = a.obs_off[p + 1];
   // empty list, bad point, or offsets the device entry point could not check: the point is left unchanged
-  const bool live = lo >= 0 && lo < hi && hi <= a.nobs && (!a.pt_good || a.pt_good[p]);
-  if (a.what & ORBL_MP_NORMAL_DEPTH) {
+  int lo, hi;
+  const bool live = mt_range(a.obs_off, p, a.nobs, &lo, &hi) && lo < hi && (!a.pt_good || a.pt_good[p]);
+  if (a.what & ORBL_MP_NORMAL_DEPTH) {                               // the walk covers the whole list, bad keyframes included, as the reference's
     uint8_t wrote = 0;
     const int r = live ? a.ref_kf[p] : -1, lvl = live ? a.ref_level[p] : -1;
-    if (r >= 0 && r < a.nkf && lvl >= 0 && lvl < a.n_levels) {
-      const double x = a.X[3 * (size_t)p], y = a.X[3 * (size_t)p + 1], z = a.X[3 * (size_t)p + 2];
-      double nx = 0.0, ny = 0.0, nz = 0.0;
-      bool ok = true;
-      for (int e = lo; e < hi; e++) {                            // (:356-364) normal + normali / normali.norm(), list order
-        const int k = a.obs_kf[e];
-        if (k < 0 || k >= a.nkf) { ok = false; break; }
-        const double vx = x - a.kf_center[3 * (size_t)k], vy = y - a.kf_center[3 * (size_t)k + 1], vz = z - a.kf_center[3 * (size_t)k + 2];
-        const double nn = sqrt((vx * vx + vy * vy) + vz * vz);
-        nx = nx + vx / nn; ny = ny + vy / nn; nz = nz + vz / nn;
-      }
-      if (ok) {
-        const double n = (double)(hi - lo);
-        double* nv = a.normal + 3 * (size_t)p;
-        nv[0] = nx / n; nv[1] = ny / n; nv[2] = nz / n;                 // (:376)
-        const double px = x - a.kf_center[3 * (size_t)r], py = y - a.kf_center[3 * (size_t)r + 1], pz = z - a.kf_center[3 * (size_t)r + 2];
-        const float dist = (float)sqrt((px * px + py * py) + pz * pz);  // (:366-368)
-        const float mx = dist * a.scale_factors[lvl];                   // (:374)
-        a.min_max[2 * (size_t)p] = mx / a.scale_factors[a.n_levels - 1];
-        a.min_max[2 * (size_t)p + 1] = mx;
-        wrote = 1;
-      }
-    }
+    if (r >= 0 && r < a.nkf && lvl >= 0 && lvl < a.n_levels)
+      wrote = mt_normal_depth(a.obs_kf, lo, hi, a.nkf, a.kf_center, a.X[3 * (size_t)p], a.X[3 * (size_t)p + 1], a.X[3 * (size_t)p + 2], r, lvl, a.scale_factors,
+                              a.n_levels, a.normal + 3 * (size_t)p, a.min_max + 2 * (size_t)p) == MT_ND_OK;
     a.nd_written[p] = wrote;
   }
   if (a.what & ORBL_MP_DESC) {

@@ -25,6 +25,8 @@
 //                 the map's own order): exact, no comparison network, rows of any length tiled through LDS; one workgroup per target
 //                 for its links in rank order.
 // Outputs are written with vector stores only, each element by the one lane that owns it; nothing is written beyond a capacity.
+#include "orb_maptable.h"
+
 namespace orbhip {
 
 #define UC_WG 256                 /* every kernel but the scan; also the sort tile */
@@ -51,23 +53,13 @@ struct UcArgs {
   uint8_t* pmark; long long* ent_key; size_t ent_cap;
 };
 
-__device__ __forceinline__ void uc_flag(const UcArgs& a, uint32_t bits) { if (a.status) atomicOr(a.status, bits); }
-
-// [off[i], off[i + 1]) when it lies inside [0, total]; false (and an empty range) when the offsets are not usable
-__device__ __forceinline__ bool uc_range(const int32_t* off, int i, int total, int* lo, int* hi) {
-  const int l = off[i], h = off[i + 1];
-  const bool ok = l >= 0 && l <= h && h <= total;
-  *lo = ok ? l : 0; *hi = ok ? h : 0;
-  return ok;
-}
-
 // the row of CSR `off` (rows of them, `total` entries) that holds entry s, or -1
 __device__ __forceinline__ int uc_row_of(const int32_t* off, int rows, int total, int s) {
   int b = 0, t = rows;
   while (b < t) { const int m = (b + t) >> 1; if (off[m] <= s) b = m + 1; else t = m; }
   const int c = b - 1;
   int lo, hi;
-  if (c < 0 || !uc_range(off, c, total, &lo, &hi) || s < lo || s >= hi) return -1;
+  if (c < 0 || !mt_range(off, c, total, &lo, &hi) || s < lo || s >= hi) return -1;
   return c;
 }
 
@@ -111,21 +103,21 @@ __global__ __launch_bounds__(UC_WG) void k_uc_init(UcArgs a) {
   const int i = blockIdx.x * UC_WG + threadIdx.x;
   int lo, hi;
   if (i < a.ntgt) {
-    if (!uc_range(a.slot_off, i, a.nslots, &lo, &hi)) uc_flag(a, UC_ST_OFFSETS);
-    if (a.prev_off && !uc_range(a.prev_off, i, a.nprev, &lo, &hi)) uc_flag(a, UC_ST_OFFSETS);
+    if (!mt_range(a.slot_off, i, a.nslots, &lo, &hi)) mt_flag(a.status, UC_ST_OFFSETS);
+    if (a.prev_off && !mt_range(a.prev_off, i, a.nprev, &lo, &hi)) mt_flag(a.status, UC_ST_OFFSETS);
     const int k = a.tgt_kf[i];
-    if (!uc_kf_ok(a, k)) uc_flag(a, UC_ST_INDEX);
-    else if (atomicMax(&a.tpos[k], i) != -1) uc_flag(a, UC_ST_INDEX);         // (a keyframe listed twice: its last instance counts)
+    if (!uc_kf_ok(a, k)) mt_flag(a.status, UC_ST_INDEX);
+    else if (atomicMax(&a.tpos[k], i) != -1) mt_flag(a.status, UC_ST_INDEX);         // (a keyframe listed twice: its last instance counts)
   }
   if (i < a.nkf) {
-    if (!uc_range(a.conn_off, i, a.nconn, &lo, &hi)) uc_flag(a, UC_ST_OFFSETS);
+    if (!mt_range(a.conn_off, i, a.nconn, &lo, &hi)) mt_flag(a.status, UC_ST_OFFSETS);
     if (a.kf_rank) {
       const int r = a.kf_rank[i];
-      if (r < 0 || r >= a.nkf) uc_flag(a, UC_ST_INDEX);
-      else if (atomicAdd(&a.rhit[r], 1) != 0) uc_flag(a, UC_ST_INDEX);        // (not a permutation)
+      if (r < 0 || r >= a.nkf) mt_flag(a.status, UC_ST_INDEX);
+      else if (atomicAdd(&a.rhit[r], 1) != 0) mt_flag(a.status, UC_ST_INDEX);        // (not a permutation)
     }
   }
-  if (i < a.npts && !uc_range(a.obs_off, i, a.nobs, &lo, &hi)) uc_flag(a, UC_ST_OFFSETS);
+  if (i < a.npts && !mt_range(a.obs_off, i, a.nobs, &lo, &hi)) mt_flag(a.status, UC_ST_OFFSETS);
 }
 
 __global__ __launch_bounds__(UC_WG) void k_uc_votes(UcArgs a) {
@@ -134,13 +126,13 @@ __global__ __launch_bounds__(UC_WG) void k_uc_votes(UcArgs a) {
     const int t = uc_row_of(a.slot_off, a.ntgt, a.nslots, i);
     if (t >= 0 && uc_tgt_ok(a, t)) {
       const int A = a.tgt_kf[t], p = a.slot_pt[i];
-      if (p < -1 || p >= a.npts) uc_flag(a, UC_ST_INDEX);
+      if (p < -1 || p >= a.npts) mt_flag(a.status, UC_ST_INDEX);
       else if (p >= 0 && !(a.pt_bad && a.pt_bad[p])) {
         int lo, hi;
-        uc_range(a.obs_off, p, a.nobs, &lo, &hi);
+        mt_range(a.obs_off, p, a.nobs, &lo, &hi);
         for (int e = lo; e < hi; e++) {
           const int k = a.obs_kf[e];
-          if (!uc_kf_ok(a, k)) { uc_flag(a, UC_ST_INDEX); continue; }
+          if (!uc_kf_ok(a, k)) { mt_flag(a.status, UC_ST_INDEX); continue; }
           if (k != A) atomicAdd(&uc_cnt(a, t, k), 1);
         }
       }
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(UC_WG) void k_uc_votes(UcArgs a) {
     const int B = uc_row_of(a.conn_off, a.nkf, a.nconn, i);
     if (B >= 0) {
       const int k = a.conn_kf[i];
-      if (!uc_kf_ok(a, k) || k == B) uc_flag(a, UC_ST_INDEX);
+      if (!uc_kf_ok(a, k) || k == B) mt_flag(a.status, UC_ST_INDEX);
       else if (a.tpos[k] >= 0) a.inpos[(size_t)B * a.ntgt + a.tpos[k]] = i + 1;
     }
   }
@@ -204,7 +196,7 @@ __device__ __forceinline__ UcRow uc_row(const UcArgs& a, int B) {
   UcRow R;
   R.tB = a.tpos[B];
   R.own = R.tB >= 0 && a.t_nkeys[R.tB] > 0;
-  uc_range(a.conn_off, B, a.nconn, &R.lo, &R.hi);
+  mt_range(a.conn_off, B, a.nconn, &R.lo, &R.hi);
   return R;
 }
 
@@ -248,8 +240,8 @@ __device__ __forceinline__ void uc_link_candidates(const UcArgs& a, int t, int t
   if (!uc_tgt_ok(a, t)) { if (tid == 0) a.t_nlink[t] = 0; return; }
   const int A = a.tgt_kf[t];
   int lo, hi, plo, phi;
-  uc_range(a.conn_off, A, a.nconn, &lo, &hi);
-  uc_range(a.prev_off, t, a.nprev, &plo, &phi);
+  mt_range(a.conn_off, A, a.nconn, &lo, &hi);
+  mt_range(a.prev_off, t, a.nprev, &plo, &phi);
   // was A's list re-sorted before its turn: an effective send of an earlier target, judged against A's input row
   int pre = 0;
   for (int u = tid; u < t; u += UC_WG) {
@@ -263,7 +255,7 @@ __device__ __forceinline__ void uc_link_candidates(const UcArgs& a, int t, int t
     for (int e = lo + tid; e < hi; e += UC_WG) { const int k = a.conn_kf[e]; if (uc_kf_ok(a, k)) mark[k] = 1; }
   for (int e = plo + tid; e < phi; e += UC_WG) {                    // (the previous list is checked even where the re-sorted row replaces it)
     const int k = a.prev_kf[e];
-    if (!uc_kf_ok(a, k)) uc_flag(a, UC_ST_INDEX);
+    if (!uc_kf_ok(a, k)) mt_flag(a.status, UC_ST_INDEX);
     else if (!pre) mark[k] = 1;
   }
   if (tid == 0) *s_n = 0;
@@ -334,7 +326,7 @@ __global__ __launch_bounds__(UC_SWG) void k_uc_scan(UcArgs a) {
     if (n_aff <= a.cap_aff) { a.oconn_off[n_aff] = n_conn; a.oord_off[n_aff] = n_ord; }      // (the offset arrays hold cap_aff + 1 entries)
     const uint32_t bits = (n_aff > a.cap_aff ? UC_ST_CAP_AFF : 0u) | (n_conn > a.cap_conn ? UC_ST_CAP_CONN : 0u) | (n_ord > a.cap_ord ? UC_ST_CAP_ORD : 0u) |
                           (n_link > a.cap_link ? UC_ST_CAP_LINK : 0u);
-    if (bits) uc_flag(a, bits);
+    if (bits) mt_flag(a.status, bits);
   }
 }
 

@@ -62,6 +62,8 @@ def test_seeded_structure(name, m):
     # what the maps are meant to contain
     if m["nkf"] == 300:
         assert ncam > 256 and len(ba_kf) < m["nkf"], "the cameras do not cross a tile of the all-pairs count, or no keyframe is outside the list"
+        at = np.array([at_p[p] for p in r["gpt_pt"]])
+        assert np.any(at < 256) and np.any(at >= 256), "the point scan carries no sum into its second workgroup"
     if m["npts"] == 70000:
         assert len(ba_pt) > 256 * 256 and set(np.diff(m["obs_off"]).tolist()) <= {0, 1, 2}, "the scan does not see more than 256 workgroup sums"
     listed = [p for p in ba_pt if not m["pt_bad"][p]]

@@ -67,7 +67,11 @@ def test_no_seeded_map_is_vacuous_and_sizes_cross_the_scan_units():
         assert 0.1 * len(res[2]) <= res[2].sum() <= 0.3 * len(res[2]), name
         assert np.any(asm["cam_fixed"][asm["cam_local"] == 1]), name   # keyframe id 0 is local
         assert np.any(out["nd_written"]) and np.any(asm["pt_local"] == 0), name
-        big = big or (asm["counts"][0] > 64 and asm["counts"][2] > 4096 and int(np.max(np.diff(m["obs_off"]))) > 256)
+        # the scan positions (kf_rank, pt_rank) of the fixed keyframes and of the local points lie on both sides of 256: both workgroup scans
+        # carry a sum into their second workgroup
+        rk, rp = m["kf_rank"][asm["kf_role"] == 2], m["pt_rank"][asm["pt_local"] != 0]
+        carry = np.any(rk < 256) and np.any(rk >= 256) and np.any(rp < 256) and np.any(rp >= 256)
+        big = big or (asm["counts"][0] > 64 and asm["counts"][2] > 4096 and int(np.max(np.diff(m["obs_off"]))) > 256 and carry)
     assert big
 
 
