@@ -1710,6 +1710,180 @@ struct FrameOpsT {
     return counts[0];
   }
 
+  // KeyFrame::SetBadFlag (src/KeyFrame.cc:460-553) on every keyframe of `keyframes`, in order, in ONE library call (orbl_set_bad_keyframes):
+  // `FrameOpsHip::SetBadFlags(culled);` for the keyframes LocalMapping::KeyFrameCulling decided on.  Flattened, through the reference's
+  // accessors and under its lock scopes: the targets; the keyframes their maps name, their parents and children and the observers of
+  // their points ("rows": map, ordered lists, parent, children, pose, slots - of a keyframe that is no target only the slots that hold
+  // a target's point); the keyframes those tables name are indexed too, with empty rows: nothing of them is read or written.  kf_rank =
+  // the order under std::less<KeyFrame*>.  Written back on the rows that changed: connected_keyframe_weights_, ordered_connected_keyframes_,
+  // ordered_weights_, parent_, childrens_, EraseMapPointMatch; on the points: observations_, n_observations_, reference_keyframe_,
+  // is_bad_; on the targets that went: Tcp_, is_bad_ - members the reference keeps protected: the friend declaration of INTEGRATION.md
+  // section 4.  Then the caller-side remainder: do_to_be_erased_ on a target with do_not_erase_ (:465-468), map_->EraseMapPoint of every
+  // point that turned bad, map_->EraseKeyFrame and keyframe_database_->erase of every keyframe that went (:551-552).  A keyframe listed
+  // twice, or a map the library refuses as inconsistent (a target that is bad or has no parent, an observation whose slot does not
+  // hold its point): nothing is called, nothing is changed, returns -1.  Otherwise returns the number of keyframes that went bad.
+  // (A member template over the keyframe type, as UpdateConnections is.)
+  template <class KF> static int SetBadFlags(const std::vector<KF*>& keyframes) {
+    typedef typename std::remove_pointer<typename std::decay<decltype(keyframes[0]->GetMapPointMatches()[0])>::type>::type MP;
+    typedef typename std::decay<decltype(keyframes[0]->GetPose())>::type M4;
+    const int ntgt = (int)keyframes.size();
+    if (ntgt == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    std::vector<int32_t> tgt_kf(ntgt);
+    std::vector<uint8_t> tgt_flags(ntgt, 0);
+    for (int t = 0; t < ntgt; t++) {
+      if (kf_at.count(keyframes[t])) return -1;
+      tgt_kf[t] = kf_index(keyframes[t]);                           // (targets are numbered first: index = list position)
+    }
+    // the points of the targets with their observations, and the rows
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*> pts;
+    std::vector<std::map<KF*, size_t> > pt_obs;
+    for (int t = 0; t < ntgt; t++) {
+      KF* kf = keyframes[t];
+      bool keep; KF* parent; std::set<KF*> children; std::map<KF*, int> weights;
+      {
+        std::unique_lock<std::mutex> lock = lock_connections(kf, 0);
+        keep = kf->do_not_erase_; parent = kf->parent_; children = kf->childrens_; weights = kf->connected_keyframe_weights_;
+      }
+      tgt_flags[t] = (uint8_t)((kf->id_ == 0 ? 1 : 0) | (keep ? 2 : 0));       // (:463-468)
+      if (tgt_flags[t]) continue;
+      if (parent) kf_index(parent);
+      for (KF* c : children) kf_index(c);
+      for (const auto& w : weights) kf_index(w.first);
+      const std::vector<MP*> matches = kf->GetMapPointMatches();
+      for (MP* mp : matches) {
+        if (!mp || pt_at.count(mp)) continue;
+        pt_at.emplace(mp, (int)pts.size());
+        pts.push_back(mp);
+        pt_obs.push_back(mp->GetObservations());
+        for (const auto& o : pt_obs.back()) kf_index(o.first);
+      }
+    }
+    const int n_rows = (int)kfs.size(), npts = (int)pts.size();
+    std::vector<int32_t> kf_parent, child_off(1, 0), child_kf, conn_off(1, 0), conn_kf, conn_w, ord_off(1, 0), ord_kf, ord_w, slot_off(1, 0), slot_pt;
+    std::vector<uint8_t> kf_bad;
+    for (int k = 0; k < n_rows; k++) {
+      KF* kf = kfs[k];
+      KF* parent; std::set<KF*> children; std::map<KF*, int> weights; std::vector<KF*> ordered; std::vector<int> ordered_w; bool bad;
+      {
+        std::unique_lock<std::mutex> lock = lock_connections(kf, 0);
+        parent = kf->parent_; children = kf->childrens_; weights = kf->connected_keyframe_weights_; ordered = kf->ordered_connected_keyframes_;
+        ordered_w = kf->ordered_weights_; bad = kf->is_bad_;
+      }
+      kf_parent.push_back(parent ? kf_index(parent) : -1);
+      kf_bad.push_back(bad ? 1 : 0);
+      for (KF* c : children) child_kf.push_back(kf_index(c));
+      child_off.push_back((int32_t)child_kf.size());
+      for (const auto& w : weights) { conn_kf.push_back(kf_index(w.first)); conn_w.push_back(w.second); }
+      conn_off.push_back((int32_t)conn_kf.size());
+      if (ordered.size() != ordered_w.size()) return -1;
+      for (size_t i = 0; i < ordered.size(); i++) { ord_kf.push_back(kf_index(ordered[i])); ord_w.push_back(ordered_w[i]); }
+      ord_off.push_back((int32_t)ord_kf.size());
+      const std::vector<MP*> matches = kf->GetMapPointMatches();
+      for (MP* mp : matches) { auto it = mp ? pt_at.find(mp) : pt_at.end(); slot_pt.push_back(it == pt_at.end() ? -1 : it->second); }
+      slot_off.push_back((int32_t)slot_pt.size());
+    }
+    const int nkf = (int)kfs.size();                               // (the keyframes the rows name beyond themselves: empty rows)
+    for (int k = n_rows; k < nkf; k++) { kf_parent.push_back(-1); kf_bad.push_back(kfs[k]->isBad() ? 1 : 0); }
+    child_off.resize(nkf + 1, child_off.back()); conn_off.resize(nkf + 1, conn_off.back()); ord_off.resize(nkf + 1, ord_off.back()); slot_off.resize(nkf + 1, slot_off.back());
+    std::vector<double> Tcw(12 * (size_t)nkf, 0.0);
+    for (int k = 0; k < nkf; k++) {
+      const M4 T = kfs[k]->GetPose();
+      for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c);
+    }
+    std::vector<int32_t> by_pointer(nkf), kf_rank(nkf);
+    for (int k = 0; k < nkf; k++) by_pointer[k] = k;
+    std::sort(by_pointer.begin(), by_pointer.end(), [&](int a, int b) { return std::less<KF*>()(kfs[a], kfs[b]); });
+    for (int r = 0; r < nkf; r++) kf_rank[by_pointer[r]] = r;
+    std::vector<int32_t> obs_off(1, 0), obs_kf, obs_slot, pt_nobs(npts), pt_ref(npts);
+    std::vector<uint8_t> pt_bad(npts);
+    for (int p = 0; p < npts; p++) {
+      for (const auto& o : pt_obs[p]) { obs_kf.push_back(kf_at[o.first]); obs_slot.push_back((int32_t)o.second); }
+      obs_off.push_back((int32_t)obs_kf.size());
+      pt_nobs[p] = pts[p]->Observations(); pt_bad[p] = pts[p]->isBad() ? 1 : 0;
+      std::unique_lock<std::mutex> lock = lock_features(pts[p], 0);
+      auto it = pts[p]->reference_keyframe_ ? kf_at.find(pts[p]->reference_keyframe_) : kf_at.end();
+      pt_ref[p] = it == kf_at.end() ? -1 : it->second;             // (a reference keyframe outside the rows cannot be a target)
+    }
+    const size_t cap_ord = conn_kf.size() + ord_kf.size(), cap_child = child_kf.size() + (size_t)ntgt * (size_t)nkf;
+    if (cap_ord > 0x7FFFFFFFu || cap_child > 0x7FFFFFFFu) throw std::runtime_error("FrameOpsT::SetBadFlags: keyframe list too large for one call");
+    const std::vector<int32_t> parent_in = kf_parent, slot_in = slot_pt;
+    std::vector<uint8_t> pt_bad_in = pt_bad, obs_erased(std::max<size_t>(obs_kf.size(), 1), 0);
+    std::vector<int32_t> tgt_status(ntgt), oconn_off(nkf + 1), oconn_kf(std::max<size_t>(conn_kf.size(), 1)), oconn_w(std::max<size_t>(conn_kf.size(), 1)),
+        oord_off(nkf + 1), oord_kf(std::max<size_t>(cap_ord, 1)), oord_w(std::max<size_t>(cap_ord, 1)), ochild_off(nkf + 1), ochild_kf(std::max<size_t>(cap_child, 1));
+    std::vector<double> Tcp(12 * (size_t)ntgt);
+    obs_kf.resize(std::max<size_t>(obs_kf.size(), 1)); obs_slot.resize(obs_kf.size()); slot_pt.resize(std::max<size_t>(slot_pt.size(), 1), -1);
+    child_kf.resize(std::max<size_t>(child_kf.size(), 1)); conn_kf.resize(std::max<size_t>(conn_kf.size(), 1)); conn_w.resize(conn_kf.size());
+    ord_kf.resize(std::max<size_t>(ord_kf.size(), 1)); ord_w.resize(ord_kf.size());
+    pt_bad.resize(std::max(npts, 1)); pt_nobs.resize(std::max(npts, 1)); pt_ref.resize(std::max(npts, 1));
+    int32_t counts[6] = {0, 0, 0, 0, 0, 0};
+    const int rc = orbl_set_bad_keyframes(ntgt, tgt_kf.data(), tgt_flags.data(), nullptr, nkf, kf_bad.data(), kf_parent.data(), kf_rank.data(), Tcw.data(), child_off.data(),
+                                          child_kf.data(), conn_off.data(), conn_kf.data(), conn_w.data(), ord_off.data(), ord_kf.data(), ord_w.data(), npts, slot_off.data(),
+                                          slot_pt.data(), pt_bad.data(), pt_nobs.data(), pt_ref.data(), obs_off.data(), obs_kf.data(), obs_slot.data(), obs_erased.data(),
+                                          (int)cap_ord, (int)cap_child, tgt_status.data(), Tcp.data(), oconn_off.data(), oconn_kf.data(), oconn_w.data(), oord_off.data(),
+                                          oord_kf.data(), oord_w.data(), ochild_off.data(), ochild_kf.data(), counts);
+    if (rc == ORBHIP_EINVAL) return -1;                             // (an inconsistent map: nothing was changed)
+    dropin::check(rc, "orbl_set_bad_keyframes");
+    for (int k = 0; k < n_rows; k++) {                              // the rows that changed
+      KF* kf = kfs[k];
+      const int c0 = oconn_off[k], c1 = oconn_off[k + 1], o0 = oord_off[k], o1 = oord_off[k + 1], h0 = ochild_off[k], h1 = ochild_off[k + 1];
+      const bool conn_changed = c1 - c0 != conn_off[k + 1] - conn_off[k];      // (a row only ever loses entries)
+      const bool ord_changed = o1 - o0 != ord_off[k + 1] - ord_off[k] || !std::equal(oord_kf.begin() + o0, oord_kf.begin() + o1, ord_kf.begin() + ord_off[k]) ||
+                               !std::equal(oord_w.begin() + o0, oord_w.begin() + o1, ord_w.begin() + ord_off[k]);
+      std::set<int32_t> child_in(child_kf.begin() + child_off[k], child_kf.begin() + child_off[k + 1]), child_out(ochild_kf.begin() + h0, ochild_kf.begin() + h1);
+      std::map<KF*, int> weights; std::vector<KF*> ordered; std::vector<int> ordered_w; std::set<KF*> children;
+      for (int e = c0; e < c1; e++) weights[kfs[oconn_kf[e]]] = oconn_w[e];
+      for (int e = o0; e < o1; e++) { ordered.push_back(kfs[oord_kf[e]]); ordered_w.push_back(oord_w[e]); }
+      for (int e = h0; e < h1; e++) children.insert(kfs[ochild_kf[e]]);
+      {
+        std::unique_lock<std::mutex> lock = lock_connections(kf, 0);
+        if (conn_changed) kf->connected_keyframe_weights_.swap(weights);
+        if (ord_changed) { kf->ordered_connected_keyframes_.swap(ordered); kf->ordered_weights_.swap(ordered_w); }
+        if (child_in != child_out) kf->childrens_.swap(children);
+        if (kf_parent[k] != parent_in[k]) kf->parent_ = kfs[kf_parent[k]];
+      }
+      for (int s = slot_off[k]; s < slot_off[k + 1]; s++)
+        if (slot_in[s] >= 0 && slot_pt[s] < 0) kf->EraseMapPointMatch((size_t)(s - slot_off[k]));       // (MapPoint::SetBadFlag, src/MapPoint.cc:183-188)
+    }
+    std::vector<MP*> turned_bad;
+    for (int p = 0; p < npts; p++) {                                // (src/MapPoint.cc:140-191)
+      bool any = false;
+      for (int e = obs_off[p]; e < obs_off[p + 1]; e++) any |= obs_erased[e] != 0;
+      if (!any) continue;
+      MP* mp = pts[p];
+      const bool bad = pt_bad[p] && !pt_bad_in[p];
+      {
+        std::unique_lock<std::mutex> lock1 = lock_features(mp, 0);
+        std::unique_lock<std::mutex> lock2 = bad ? lock_pose(mp, 0) : std::unique_lock<std::mutex>();
+        for (int e = obs_off[p]; e < obs_off[p + 1]; e++) if (obs_erased[e]) mp->observations_.erase(kfs[obs_kf[e]]);
+        mp->n_observations_ = pt_nobs[p];
+        if (pt_ref[p] >= 0) mp->reference_keyframe_ = kfs[pt_ref[p]];
+        if (bad) mp->is_bad_ = true;
+      }
+      if (bad) turned_bad.push_back(mp);
+    }
+    for (MP* mp : turned_bad) mp->map_->EraseMapPoint(mp);          // (:190)
+    for (int t = 0; t < ntgt; t++) {
+      KF* kf = keyframes[t];
+      if (tgt_status[t] == 2) { std::unique_lock<std::mutex> lock = lock_connections(kf, 0); kf->do_to_be_erased_ = true; }       // (:466)
+      if (tgt_status[t] != 0) continue;
+      M4 T = kf->GetPose();
+      for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) T(i, j) = Tcp[12 * (size_t)t + 4 * i + j];
+      T(3, 0) = 0; T(3, 1) = 0; T(3, 2) = 0; T(3, 3) = 1;
+      { std::unique_lock<std::mutex> lock = lock_connections(kf, 0); kf->Tcp_ = T; kf->is_bad_ = true; }        // (:547-548)
+      kf->map_->EraseKeyFrame(kf);                                  // (:551-552)
+      kf->keyframe_database_->erase(kf);
+    }
+    return counts[0];
+  }
+
   // LoopClosing::CorrectLoop, src/LoopClosing.cc:437-523, in ONE library call (orbl_correct_loop) followed by the UpdateConnections
   // drop-in: `FrameOpsHip::CorrectLoopPoses(current_keyframe_, current_connected_keyframes_, sophus_sim3_Scw_, sophus_corrected_sim3,
   // sophus_non_corrected_sim3);` under the mutex_map_update_ the caller holds, as the reference does.  Only the group's slots and the

@@ -346,6 +346,122 @@ def update_connections_device(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, c
     return r
 
 
+BF_OFFSETS, BF_INDEX, BF_TARGET, BF_ROW, BF_CAP_ORD, BF_CAP_CHILD = 1, 2, 4, 8, 16, 32      # *d_status bits of orbl_set_bad_keyframes_device
+
+_BF_KF = (("kf_bad", np.uint8), ("kf_parent", np.int32), ("kf_rank", np.int32), ("kf_Tcw", np.float64), ("child_off", np.int32), ("child_kf", np.int32),
+          ("conn_off", np.int32), ("conn_kf", np.int32), ("conn_w", np.int32), ("ord_off", np.int32), ("ord_kf", np.int32), ("ord_w", np.int32))
+_BF_PT = (("kf_slot_off", np.int32), ("kf_slot_pt", np.int32), ("pt_bad", np.uint8), ("pt_nobs", np.int32), ("pt_ref_kf", np.int32), ("obs_off", np.int32),
+          ("obs_kf", np.int32), ("obs_slot", np.int32))
+_BF_INOUT = ("kf_bad", "kf_parent", "kf_slot_pt", "pt_bad", "pt_nobs", "pt_ref_kf")
+_BF_OUT = ("tgt_status", "tgt_Tcp", "oconn_off", "oconn_kf", "oconn_w", "oord_off", "oord_kf", "oord_w", "ochild_off", "ochild_kf", "counts")
+
+
+class BadFlagResult:
+    """What orbl_set_bad_keyframes reports: tgt_status[ntgt], tgt_Tcp[ntgt][12]; the tables it changed in place kf_bad, kf_parent and -
+    with the point set - kf_slot_pt, pt_bad, pt_nobs, pt_ref_kf, obs_erased; the whole new tables oconn_*, oord_*, ochild_* (the host form
+    trims them to the written counts, the device form returns them at full capacity); counts[6] = {n_bad, n_conn_out, n_ord_out,
+    n_child_out, n_adopted, n_fallback}; rc; status: the device form's d_status tensor (None in the host form)."""
+    __slots__ = _BF_OUT + _BF_INOUT + ("obs_erased", "rc", "status", "_workspace")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _bf_default_caps(nkf, nchild, nconn, nord, ntgt):
+    """capacities no call can exceed: a list is copied or becomes what is left of its row; every turn adds at most one row entry per child
+    of its target"""
+    return nconn + nord, nchild + ntgt * nkf
+
+
+def set_bad_keyframes(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps=None, out=None, check=True):
+    """KeyFrame::SetBadFlag on the keyframes tgt_kf, one after the other, in one call (orbl_set_bad_keyframes; include/orbslam_hip.h states
+    the inputs and the semantics).  tables: a dict with kf_bad, kf_parent, kf_rank (may be None), kf_Tcw, child_off / child_kf, conn_off /
+    conn_kf / conn_w, ord_off / ord_kf / ord_w and - all of them or none - kf_slot_off, kf_slot_pt, pt_bad, pt_nobs, pt_ref_kf, obs_off,
+    obs_kf, obs_slot.  The in/out tables are COPIED: the changed ones come back in the result, the caller's arrays stay.  caps = (cap_ord,
+    cap_child), default: bounds no call exceeds.  out: optional dict of preset output arrays of those capacities.  Returns a BadFlagResult;
+    check=False returns rc = ORBHIP_ECAP with counts and the (then unchanged) copies of the in/out tables instead of raising."""
+    L = _lib.load()
+    tk = _c(tgt_kf, np.int32).reshape(-1); ntgt = len(tk)
+    tf = _c(tgt_flags, np.uint8).reshape(-1) if tgt_flags is not None else None
+    tm = _c(tgt_mask, np.uint8).reshape(-1) if tgt_mask is not None else None
+    assert (tf is None or len(tf) == ntgt) and (tm is None or len(tm) == ntgt)
+    points = tables.get("kf_slot_off") is not None
+    a = {}
+    for k, dt in _BF_KF + (_BF_PT if points else ()):
+        v = tables.get(k)
+        a[k] = None if v is None else (np.array(v, dt).reshape(-1) if k in _BF_INOUT else _c(v, dt).reshape(-1))
+    nkf = len(a["kf_bad"])
+    assert len(a["kf_parent"]) == nkf and len(a["kf_Tcw"]) == 12 * nkf and (a["kf_rank"] is None or len(a["kf_rank"]) == nkf)
+    for off, ent in (("child_off", ("child_kf",)), ("conn_off", ("conn_kf", "conn_w")), ("ord_off", ("ord_kf", "ord_w"))):
+        assert len(a[off]) == nkf + 1 and all(len(a[e]) >= a[off][-1] for e in ent), off      # (the library checks the rest)
+    npts = 0
+    if points:
+        npts = len(a["obs_off"]) - 1
+        assert len(a["kf_slot_off"]) == nkf + 1 and len(a["kf_slot_pt"]) >= a["kf_slot_off"][-1] and npts >= 0
+        assert len(a["pt_bad"]) == npts and len(a["pt_nobs"]) == npts and len(a["pt_ref_kf"]) == npts
+        assert len(a["obs_kf"]) >= a["obs_off"][-1] and len(a["obs_slot"]) == len(a["obs_kf"])
+        a["obs_erased"] = np.zeros(len(a["obs_kf"]), np.uint8)
+    nconn = len(a["conn_kf"])
+    cap_ord, cap_child = _bf_default_caps(nkf, len(a["child_kf"]), nconn, len(a["ord_kf"]), ntgt) if caps is None else caps
+    o = dict(tgt_status=np.zeros(ntgt, np.int32), tgt_Tcp=np.zeros((ntgt, 12), np.float64), oconn_off=np.zeros(nkf + 1, np.int32), oconn_kf=np.zeros(nconn, np.int32),
+             oconn_w=np.zeros(nconn, np.int32), oord_off=np.zeros(nkf + 1, np.int32), oord_kf=np.zeros(cap_ord, np.int32), oord_w=np.zeros(cap_ord, np.int32),
+             ochild_off=np.zeros(nkf + 1, np.int32), ochild_kf=np.zeros(cap_child, np.int32), counts=np.zeros(6, np.int32))
+    for k, v in ({} if out is None else out).items():
+        assert v.dtype == o[k].dtype and v.flags.c_contiguous and v.size == o[k].size, k
+        o[k] = v
+    rc = L.orbl_set_bad_keyframes(ntgt, _addr(tk), _addr(tf), _addr(tm), nkf, *[_addr(a[k]) for k, _ in _BF_KF], npts, *[_addr(a.get(k)) for k, _ in _BF_PT],
+                                  _addr(a.get("obs_erased")), int(cap_ord), int(cap_child), *[_addr(o[k]) for k in _BF_OUT])
+    if rc == ECAP and not check:
+        return BadFlagResult(rc=rc, counts=o["counts"], obs_erased=a.get("obs_erased"), **{k: a.get(k) for k in _BF_INOUT})
+    _lib.check(rc, "orbl_set_bad_keyframes")
+    _, n_conn, n_ord, n_child = (int(v) for v in o["counts"][:4])
+    o.update(oconn_kf=o["oconn_kf"][:n_conn], oconn_w=o["oconn_w"][:n_conn], oord_kf=o["oord_kf"][:n_ord], oord_w=o["oord_w"][:n_ord], ochild_kf=o["ochild_kf"][:n_child])
+    return BadFlagResult(rc=0, obs_erased=a.get("obs_erased"), **{k: a.get(k) for k in _BF_INOUT}, **o)
+
+
+def set_bad_keyframes_device(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps=None, out=None, workspace=None):
+    """orbl_set_bad_keyframes_device on torch CUDA tensors (dtypes as in set_bad_keyframes; None where a pointer may be NULL), enqueued on
+    the current stream, nothing synchronised.  The in/out tables of `tables` are changed IN PLACE.  tgt_mask may be the d_culled tensor
+    of keyframe_culling_device.  out: optional dict of preset device tensors of the capacities (and obs_erased); workspace: optional
+    uint8 tensor to reuse (it is cleared by every call).  Returns a BadFlagResult of device tensors of FULL capacity - counts[6] holds
+    the wanted sizes, status (uint32 as int32[1]) the BF_* bits."""
+    import torch
+    L = _lib.load()
+    dev = tgt_kf.device
+    points = tables.get("kf_slot_off") is not None
+    a = {k: tables.get(k) for k, _ in _BF_KF + _BF_PT}
+    ntgt, nkf = tgt_kf.numel(), a["kf_bad"].numel()
+    nchild, nconn, nord = a["child_kf"].numel(), a["conn_kf"].numel(), a["ord_kf"].numel()
+    npts, nslots, nobs = (a["obs_off"].numel() - 1, a["kf_slot_pt"].numel(), a["obs_kf"].numel()) if points else (0, 0, 0)
+    cap_ord, cap_child = _bf_default_caps(nkf, nchild, nconn, nord, ntgt) if caps is None else caps
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_set_bad_keyframes_workspace(ntgt, nkf, nchild, nconn, nobs, C.byref(nbytes)), "orbl_set_bad_keyframes_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else out
+    sizes = dict(tgt_status=ntgt, oconn_off=nkf + 1, oconn_kf=nconn, oconn_w=nconn, oord_off=nkf + 1, oord_kf=cap_ord, oord_w=cap_ord, ochild_off=nkf + 1,
+                 ochild_kf=cap_child, counts=6, status=1)
+    for k, n in sizes.items():
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        assert o[k].dtype == torch.int32 and o[k].is_contiguous() and o[k].numel() == n, k
+    if o.get("tgt_Tcp") is None:
+        o["tgt_Tcp"] = torch.empty((max(ntgt, 1), 12), dtype=torch.float64, device=dev)[:ntgt]
+    if points and o.get("obs_erased") is None:
+        o["obs_erased"] = torch.empty(max(nobs, 1), dtype=torch.uint8, device=dev)[:nobs]
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_set_bad_keyframes_device(ntgt, p(tgt_kf), p(tgt_flags), p(tgt_mask), nkf, p(a["kf_bad"]), p(a["kf_parent"]), p(a["kf_rank"]), p(a["kf_Tcw"]),
+                                               nchild, p(a["child_off"]), p(a["child_kf"]), nconn, p(a["conn_off"]), p(a["conn_kf"]), p(a["conn_w"]), nord,
+                                               p(a["ord_off"]), p(a["ord_kf"]), p(a["ord_w"]), npts, nslots, p(a["kf_slot_off"]), p(a["kf_slot_pt"]), p(a["pt_bad"]),
+                                               p(a["pt_nobs"]), p(a["pt_ref_kf"]), nobs, p(a["obs_off"]), p(a["obs_kf"]), p(a["obs_slot"]), p(o.get("obs_erased")),
+                                               int(cap_ord), int(cap_child), *[p(o[k]) for k in _BF_OUT], p(o["status"]), p(ws),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_set_bad_keyframes_device")
+    return BadFlagResult(rc=0, status=o["status"], obs_erased=o.get("obs_erased"), _workspace=ws, **{k: a.get(k) for k in _BF_INOUT}, **{k: o[k] for k in _BF_OUT})
+
+
 # *d_status bits of orbl_local_ba_assemble_device and orbl_local_ba_apply_device
 LA_OFFSETS, LA_KF, LA_PT, LA_RANK, LA_LEVEL, LA_CAP_CAM, LA_CAP_PTS, LA_CAP_OBS, LA_OBS = 1, 2, 4, 8, 16, 32, 64, 128, 256
 

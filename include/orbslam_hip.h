@@ -615,6 +615,91 @@ int orbl_update_connections_device(int ntgt, const int32_t* d_tgt_kf, const uint
  * section rounded up to 256 bytes; npts and nslots do not enter. */
 int orbl_update_connections_workspace(int ntgt, int nkf, int npts, int nslots, int nconn, size_t* bytes);
 
+/* ---- KeyFrame::SetBadFlag (src/KeyFrame.cc:460-553) with EraseConnection (:560-573), UpdateBestCovisibles (:172-193) and
+ * MapPoint::EraseObservation / SetBadFlag (src/MapPoint.cc:140-191, monocular) for a WHOLE list of keyframes in ONE call, with the exact
+ * sequential semantics of calling it on each in turn.  Keyframes are 0..nkf-1, points 0..npts-1.
+ *   targets, in call order: tgt_kf[t] in [0, nkf), distinct; tgt_flags[t] (nullable = all 0): bit 0 = id_ == 0, bit 1 = do_not_erase_ (the
+ *     bits of cand_flags in orbl_keyframe_culling); tgt_mask[t] (nullable = all 1): 0 = SetBadFlag is not called on this target - the
+ *     layout of culled[] from orbl_keyframe_culling, so the device entry can be enqueued directly behind the culling's with d_culled.
+ *   keyframe tables: kf_bad[nkf] (IN/OUT), kf_parent[nkf] (IN/OUT, -1 = none), kf_rank[nkf] (nullable = index order): a permutation, the
+ *     position under std::less<KeyFrame*>; kf_Tcw[nkf][12] row-major 3x4 (IN); child_off[nkf + 1] / child_kf[] = childrens_, rows in any
+ *     order; conn_off / conn_kf / conn_w = connected_keyframe_weights_, any order inside a row, a row names a keyframe at most once and
+ *     never itself; ord_off / ord_kf / ord_w = ordered_connected_keyframes_ / ordered_weights_ (the layouts
+ *     orbl_essential_graph_assemble reads).  Ids are unique, so the id comparison at :516 is index equality: no id table enters.
+ *   point tables, nullable AS A SET (without them step 2 is left out): kf_slot_off[nkf + 1] / kf_slot_pt[] (IN/OUT, -1 = null slot),
+ *     pt_bad[npts], pt_nobs[npts], pt_ref_kf[npts] (IN/OUT), obs_off[npts + 1] / obs_kf[] / obs_slot[], each list in std::map order and
+ *     naming a keyframe at most once, slot obs_slot[e] of keyframe obs_kf[e] holding the point; OUT obs_erased[nobs].  As in
+ *     orbl_local_ba_apply every observation listed at entry is alive and every death of this call is written to obs_erased.
+ * Per target t in order, B = tgt_kf[t]:
+ *   0. mask 0: tgt_status = 3; bit 0: tgt_status = 1 (:463); bit 1: tgt_status = 2 (:465-468; setting do_to_be_erased_ stays with the
+ *      caller).  Nothing changes in these cases.  Otherwise tgt_status = 0 and steps 1 to 5 run.
+ *   1. (:471-476) for every k in B's conn row whose OWN conn row names B: that entry of k goes, and k's ordered list becomes ALL that is
+ *      left of k's row by descending (weight, kf_rank) - the re-sort orbl_update_connections documents, which can make the list longer
+ *      than it was.  A keyframe that names B while B does not name it keeps the entry and its list; one B names that does not name B is
+ *      untouched.
+ *   2. (:478-480, only with the point tables) for every non-null slot of B in slot order, point p: nothing when p has no alive
+ *      observation by B (it turned bad already, or is listed twice).  Otherwise that observation dies and pt_nobs[p]--; pt_ref_kf[p] == B
+ *      becomes the observer of p's first alive entry (it stays when none is left); pt_nobs[p] <= 2 turns p bad: every observation of it
+ *      that is still alive dies and slot obs_slot[e] of its keyframe becomes -1.  B's own slots are not cleared.
+ *   3. (:486-487) B's conn and ord rows become empty.
+ *   4. (:490-544) P = kf_parent[B], candidates = {P}.  While B has children: over the children that are not bad NOW in ascending kf_rank,
+ *      over each child's ordered list as it stands now in list order, every entry that is a candidate with w = its weight in the child's
+ *      conn row (0 when absent) replaces the best when w is STRICTLY greater (the best starts at -1).  A best (child, entry):
+ *      kf_parent[child] = entry, the child joins entry's children, leaves B's and joins the candidates.  None: stop.  Every child still
+ *      in B's row, bad ones included, then gets kf_parent = P and joins P's children; it STAYS in B's row.
+ *   5. (:544-552) B leaves P's children; tgt_Tcp[t] = Tcw[B] o Twc[P], the product of orbl_propagate_global_ba (FP64, no fused
+ *      multiply-add, sums in index order); kf_bad[B] = 1; kf_parent[B] stays.
+ * Outputs: tgt_status[ntgt]; tgt_Tcp[ntgt][12], zeros where the status is not 0; the in/out tables; the WHOLE new tables, which are
+ * what the next entry reads: oconn_off[nkf + 1] / oconn_kf / oconn_w (each row in its input order with the removed entries closed up;
+ * arrays of conn_off[nkf] entries always suffice), oord_off[nkf + 1] / oord_kf / oord_w of capacity cap_ord (an untouched row is
+ * copied, a re-sorted one is the new list), ochild_off[nkf + 1] / ochild_kf of capacity cap_child, rows in ascending kf_rank; counts[6] =
+ * {n_bad, n_conn_out, n_ord_out, n_child_out, n_adopted (children given a candidate as parent), n_fallback (children handed to P)}.
+ * Every element inside the counts is written, nothing beyond a capacity; the outputs are the same bytes on every run.
+ * OUT OF SCOPE, stays with the caller: map_->EraseKeyFrame, keyframe_database_->erase (orbv_db_erase), map_->EraseMapPoint for the
+ * points that turned bad, do_to_be_erased_, LocalMapping::MapPointCulling.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for negative counts or
+ * capacities, NULL where an array is needed, part of the point set without the rest, offsets that do not ascend from 0, indices out of
+ * range, a kf_rank that is no permutation, a duplicate target, a status-0 target that is already bad or whose parent is -1 or itself
+ * (the reference dereferences it), a conn or child row that names a keyframe twice or itself, an obs_slot outside its keyframe's slots
+ * or whose slot does not hold the point, an observation list naming a keyframe twice; ORBHIP_ENODEV without a GPU; ORBHIP_ECAP, with
+ * only counts[] (the wanted sizes) written and the in/out tables untouched, when a list does not fit.                              */
+int orbl_set_bad_keyframes(int ntgt, const int32_t* tgt_kf, const uint8_t* tgt_flags, const uint8_t* tgt_mask, int nkf, uint8_t* kf_bad, int32_t* kf_parent,
+                           const int32_t* kf_rank, const double* kf_Tcw, const int32_t* child_off, const int32_t* child_kf, const int32_t* conn_off,
+                           const int32_t* conn_kf, const int32_t* conn_w, const int32_t* ord_off, const int32_t* ord_kf, const int32_t* ord_w, int npts,
+                           const int32_t* kf_slot_off, int32_t* kf_slot_pt, uint8_t* pt_bad, int32_t* pt_nobs, int32_t* pt_ref_kf, const int32_t* obs_off,
+                           const int32_t* obs_kf, const int32_t* obs_slot, uint8_t* obs_erased, int cap_ord, int cap_child, int32_t* tgt_status, double* tgt_Tcp,
+                           int32_t* oconn_off, int32_t* oconn_kf, int32_t* oconn_w, int32_t* oord_off, int32_t* oord_kf, int32_t* oord_w, int32_t* ochild_off,
+                           int32_t* ochild_kf, int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`, no synchronisation and no allocation inside (nchild = child_off[nkf], nconn =
+ * conn_off[nkf], nord = ord_off[nkf], nslots = kf_slot_off[nkf], nobs = obs_off[npts] given by the caller; the point set is absent when
+ * d_kf_slot_off is NULL).  d_counts[6] always holds the WANTED counts.  Counts, NULL pointers and alignment (4 bytes, 8 for the poses)
+ * are checked on the host; the data is bounds-checked on the device and an entry out of range counts as ABSENT: a connection, list
+ * entry, child, slot or observation that is not there, a target skipped with tgt_status = 4.  *d_status (nullable; zeroed first):
+ * 1 = offsets; 2 = an index out of range or a kf_rank that is no permutation; 4 = a target skipped with tgt_status = 4 (out of range,
+ * already bad, parent -1 / itself / out of range, or listed twice among the status-0 targets: the first instance counts); 8 = a conn
+ * row naming itself, a child row naming itself or a keyframe twice (the repeat is absent); 16 / 32 = cap_ord / cap_child exceeded
+ * (the elements below the capacity are still written, none beyond it).  PRECONDITIONS, not checked here: no conn row and no observation
+ * list names a keyframe twice, and an observation's slot holds its point.  `d_workspace`: at least orbl_set_bad_keyframes_workspace(...)
+ * bytes of device memory, 4-byte aligned, not shared with concurrent calls; it is cleared by every call, so calls may reuse it. */
+int orbl_set_bad_keyframes_device(int ntgt, const int32_t* d_tgt_kf, const uint8_t* d_tgt_flags, const uint8_t* d_tgt_mask, int nkf, uint8_t* d_kf_bad,
+                                  int32_t* d_kf_parent, const int32_t* d_kf_rank, const double* d_kf_Tcw, int nchild, const int32_t* d_child_off,
+                                  const int32_t* d_child_kf, int nconn, const int32_t* d_conn_off, const int32_t* d_conn_kf, const int32_t* d_conn_w, int nord,
+                                  const int32_t* d_ord_off, const int32_t* d_ord_kf, const int32_t* d_ord_w, int npts, int nslots, const int32_t* d_kf_slot_off,
+                                  int32_t* d_kf_slot_pt, uint8_t* d_pt_bad, int32_t* d_pt_nobs, int32_t* d_pt_ref_kf, int nobs, const int32_t* d_obs_off,
+                                  const int32_t* d_obs_kf, const int32_t* d_obs_slot, uint8_t* d_obs_erased, int cap_ord, int cap_child, int32_t* d_tgt_status,
+                                  double* d_tgt_Tcp, int32_t* d_oconn_off, int32_t* d_oconn_kf, int32_t* d_oconn_w, int32_t* d_oord_off, int32_t* d_oord_kf,
+                                  int32_t* d_oord_w, int32_t* d_ochild_off, int32_t* d_ochild_kf, int32_t* d_counts, uint32_t* d_status, void* d_workspace,
+                                  void* stream);
+/* *bytes = the workspace orbl_set_bad_keyframes_device needs (host arithmetic; nobs = 0 without the point set).  With R(x) = x rounded up
+ * to a multiple of 256 and adds = ntgt * nkf (a turn hands each child of its target to one new row, and a row is a set):
+ *   4 R(4 nkf) + R(4 nconn) + R(4) + R(nchild) + R(nobs)        cleared by every call: first turn, rank check, two stamp arrays per
+ *                                                                 keyframe; the mutual turn per conn entry; one counter; one byte per
+ *                                                                 child entry and per observation
+ * + R(4 nkf) + R(4 ntgt)                                        the first erasing turn per keyframe, the tentative status per target
+ * + 2 R(4 adds) + R(adds)                                       the new child memberships: parent, child, alive byte
+ * + 2 R(4 nkf) + R(12 nkf) + R(4 (nchild + adds))               the current target's children, three row sizes, the gathered children */
+int orbl_set_bad_keyframes_workspace(int ntgt, int nkf, int nchild, int nconn, int nobs, size_t* bytes);
+
 /* ---- LoopClosing::CorrectLoop, the part that moves the map (src/LoopClosing.cc:437-523): the corrected and non-corrected Sim3 of the
  * current keyframe's covisibility group, the correction of every map point those keyframes hold, UpdateNormalAndDepth of each moved
  * point, SetPose([R | t/s]) of each keyframe - with the exact semantics of the sequential loop.  Keyframes are 0..nkf-1, points 0..npts-1.
