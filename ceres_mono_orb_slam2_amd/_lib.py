@@ -13,6 +13,7 @@ SYMBOLS = [
     "orbhip_last_error", "orbhip_device_count", "orbhip_version", "orbhip_set_default_device", "orbhip_get_default_device", "orbhip_set_thread_priority", "orbhip_copy_pinned_async", "orbl_create_new_map_points", "orbl_fuse_batch", "orbl_update_map_points", "orbl_update_map_points_device", "orbl_update_map_points_workspace", "orbl_keyframe_culling", "orbl_keyframe_culling_device", "orbl_keyframe_culling_workspace",
     "orbl_update_connections", "orbl_update_connections_device", "orbl_update_connections_workspace",
     "orbl_set_bad_keyframes", "orbl_set_bad_keyframes_device", "orbl_set_bad_keyframes_workspace",
+    "orbl_apply_map_edits", "orbl_apply_map_edits_device", "orbl_apply_map_edits_workspace",
     "orbl_correct_loop", "orbl_correct_loop_device", "orbl_correct_loop_workspace",
     "orbl_propagate_global_ba", "orbl_propagate_global_ba_device", "orbl_propagate_global_ba_workspace",
     "orbl_local_ba_assemble", "orbl_local_ba_assemble_device", "orbl_local_ba_assemble_workspace",
@@ -238,6 +239,9 @@ def load():
     L.orbl_set_bad_keyframes_device.argtypes = ([i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32] + [vp] * 5 + [i32] +
                                                 [vp] * 4 + [i32, i32] + [vp] * 14)
     L.orbl_set_bad_keyframes_workspace.argtypes = [i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.orbl_apply_map_edits.argtypes = [i32] + [vp] * 5 + [i32] + [vp] * 5 + [i32] + [vp] * 9 + [i32] + [vp] * 10
+    L.orbl_apply_map_edits_device.argtypes = [i32] + [vp] * 5 + [i32, vp, vp, i32, vp, vp, vp, i32] + [vp] * 5 + [i32] + [vp] * 4 + [i32] + [vp] * 13
+    L.orbl_apply_map_edits_workspace.argtypes = [i32, i32, i32, i32, i32, C.POINTER(sz)]
     L.orbl_correct_loop.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, i32] + [vp] * 8 + [i32] + [vp] * 7
     L.orbl_correct_loop_device.argtypes = [i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32] + [vp] * 5 + [i32] + [vp] * 10
     L.orbl_correct_loop_workspace.argtypes = [i32, i32, i32, C.POINTER(sz)]

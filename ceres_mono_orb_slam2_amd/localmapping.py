@@ -462,6 +462,124 @@ def set_bad_keyframes_device(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps
     return BadFlagResult(rc=0, status=o["status"], obs_erased=o.get("obs_erased"), _workspace=ws, **{k: a.get(k) for k in _BF_INOUT}, **{k: o[k] for k in _BF_OUT})
 
 
+# op_kind values of orbl_apply_map_edits and the *d_status bits of orbl_apply_map_edits_device
+ME_NOP, ME_ADD, ME_REPLACE, ME_SET_BAD, ME_FUSE, ME_FIND_OR_ADD, ME_REPLACE_FOUND = range(7)
+ME_OFFSETS, ME_KF, ME_PT, ME_SLOT, ME_CAP = 1, 2, 4, 8, 16
+
+_ME_OPS = ("op_kind", "op_pt", "op_arg", "op_kf", "op_slot")
+_ME_IN = (("kf_slot_off", np.int32), ("kf_rank", np.int32), ("kf_slot_pt", np.int32), ("kf_slot_level", np.int32), ("kf_slot_uv", np.float32), ("pt_bad", np.uint8),
+          ("pt_nobs", np.int32), ("pt_found", np.int32), ("pt_visible", np.int32), ("pt_replaced", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32),
+          ("obs_slot", np.int32), ("obs_dead", np.uint8))
+_ME_INOUT = ("kf_slot_pt", "pt_bad", "pt_nobs", "pt_found", "pt_visible", "pt_replaced")
+_ME_OUT = (("op_status", np.int32), ("op_found", np.int32), ("pt_touched", np.uint8), ("oobs_off", np.int32), ("oobs_kf", np.int32), ("oobs_slot", np.int32),
+           ("oobs_src", np.int32), ("oobs_level", np.int32), ("oobs_uv", np.float32), ("counts", np.int32))
+
+
+class MapEditResult:
+    """What orbl_apply_map_edits reports: op_status[nops], op_found[nops], pt_touched[npts]; the tables it changed in place kf_slot_pt,
+    pt_bad, pt_nobs and - when given - pt_found, pt_visible, pt_replaced; the whole new observation tables oobs_off[npts + 1], oobs_kf,
+    oobs_slot, oobs_src and - with the kf_slot_level pair - oobs_level, oobs_uv (the host form trims them to counts[0], the device form
+    returns them at full capacity); counts[8] = {n_obs_out, n_obs_added, n_replace, n_set_bad, n_fused, n_touched, n_late_adds, 0}; rc;
+    status: the device form's d_status tensor (None in the host form)."""
+    __slots__ = tuple(k for k, _ in _ME_OUT) + _ME_INOUT + ("rc", "status", "_workspace")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _me_sizes(nops, npts, cap_obs, attrs):
+    return dict(op_status=nops, op_found=nops, pt_touched=npts, oobs_off=npts + 1, oobs_kf=cap_obs, oobs_slot=cap_obs, oobs_src=cap_obs,
+                oobs_level=cap_obs if attrs else None, oobs_uv=2 * cap_obs if attrs else None, counts=8)
+
+
+def apply_map_edits(ops, tables, cap_obs=None, out=None, check=True):
+    """An ordered list of map-point edits - AddObservation, Replace, SetBadFlag, both Fuse forms - replayed on the map tables in one call,
+    which returns the whole new observation tables (orbl_apply_map_edits; include/orbslam_hip.h states the kinds and the semantics).
+    ops: a dict with op_kind, op_pt, op_arg, op_kf, op_slot (equal lengths; empty lists = the pure rebuild).  tables: a dict with
+    kf_slot_off, kf_rank (may be None), kf_slot_pt, pt_bad, pt_nobs, obs_off, obs_kf, obs_slot and - each may be None or missing -
+    obs_dead, the pair kf_slot_level / kf_slot_uv, the pair pt_found / pt_visible, pt_replaced.  The in/out tables are COPIED: the
+    changed ones come back in the result, the caller's arrays stay.  cap_obs: default nobs + nops, which no call exceeds.  out: optional
+    dict of preset output arrays of that capacity.  Returns a MapEditResult; check=False returns rc = ORBHIP_ECAP with counts and the
+    (then unchanged) copies of the in/out tables instead of raising."""
+    L = _lib.load()
+    op = [_c(ops[k], np.int32).reshape(-1) for k in _ME_OPS]
+    nops = len(op[0])
+    assert all(len(v) == nops for v in op)
+    a = {}
+    for k, dt in _ME_IN:
+        v = tables.get(k)
+        a[k] = None if v is None else (np.array(v, dt).reshape(-1) if k in _ME_INOUT else _c(v, dt).reshape(-1))
+    nkf, npts, nobs = len(a["kf_slot_off"]) - 1, len(a["obs_off"]) - 1, len(a["obs_kf"])
+    assert nkf >= 0 and npts >= 0 and len(a["obs_slot"]) == nobs and len(a["pt_bad"]) == npts and len(a["pt_nobs"]) == npts     # (the library checks the rest)
+    assert len(a["kf_slot_pt"]) >= a["kf_slot_off"][-1] and nobs >= a["obs_off"][-1] and (a["kf_rank"] is None or len(a["kf_rank"]) == nkf)
+    for k in ("pt_found", "pt_visible", "pt_replaced"):
+        assert a[k] is None or len(a[k]) == npts, k
+    assert a["obs_dead"] is None or len(a["obs_dead"]) == nobs
+    attrs = a["kf_slot_level"] is not None
+    assert not attrs or (a["kf_slot_uv"] is not None and len(a["kf_slot_level"]) == len(a["kf_slot_pt"]) and len(a["kf_slot_uv"]) == 2 * len(a["kf_slot_pt"]))
+    cap_obs = nobs + nops if cap_obs is None else int(cap_obs)
+    sizes = _me_sizes(nops, npts, cap_obs, attrs)
+    o = {k: None if sizes[k] is None else np.zeros(sizes[k], dt) for k, dt in _ME_OUT}
+    for k, v in ({} if out is None else out).items():
+        assert k in o and o[k] is not None, "out[%r]: no such output (oobs_level / oobs_uv need the kf_slot_level pair)" % k
+        assert v.dtype == o[k].dtype and v.flags.c_contiguous and v.size == o[k].size, k
+        o[k] = v
+    rc = L.orbl_apply_map_edits(nops, *[_addr(v) for v in op], nkf, *[_addr(a[k]) for k in ("kf_slot_off", "kf_rank", "kf_slot_pt", "kf_slot_level", "kf_slot_uv")],
+                                npts, *[_addr(a[k]) for k in ("pt_bad", "pt_nobs", "pt_found", "pt_visible", "pt_replaced", "obs_off", "obs_kf", "obs_slot", "obs_dead")],
+                                cap_obs, *[_addr(o[k]) for k, _ in _ME_OUT])
+    if rc == ECAP and not check:
+        return MapEditResult(rc=rc, counts=o["counts"], **{k: a[k] for k in _ME_INOUT})
+    _lib.check(rc, "orbl_apply_map_edits")
+    n = int(o["counts"][0])
+    o.update(oobs_kf=o["oobs_kf"][:n], oobs_slot=o["oobs_slot"][:n], oobs_src=o["oobs_src"][:n])
+    if attrs:
+        o.update(oobs_level=o["oobs_level"][:n], oobs_uv=o["oobs_uv"].reshape(-1, 2)[:n])
+    return MapEditResult(rc=0, **{k: a[k] for k in _ME_INOUT}, **o)
+
+
+def apply_map_edits_device(ops, tables, cap_obs=None, out=None, workspace=None):
+    """orbl_apply_map_edits_device on torch CUDA tensors (dtypes as in apply_map_edits; None where a pointer may be NULL), enqueued on the
+    current stream, nothing synchronised.  The in/out tables of `tables` are changed IN PLACE.  obs_dead may be the obs_erased tensor of
+    set_bad_keyframes_device, keyframe_culling_device or local_ba_apply_device.  out: optional dict of preset device tensors of the
+    capacity - the dict is FILLED IN with the tensors the call creates, so passing the same dict again reuses them; workspace: optional
+    uint8 tensor to reuse (it is cleared by every call).  Returns a MapEditResult of device tensors of FULL
+    capacity - counts[8] holds the wanted sizes, status (uint32 as int32[1]) the ME_* bits."""
+    import torch
+    L = _lib.load()
+    op = [ops[k] for k in _ME_OPS]
+    a = {k: tables.get(k) for k, _ in _ME_IN}
+    dev = a["obs_off"].device
+    nops, nkf, npts = op[0].numel(), a["kf_slot_off"].numel() - 1, a["obs_off"].numel() - 1
+    nslots, nobs = a["kf_slot_pt"].numel(), a["obs_kf"].numel()
+    attrs = a["kf_slot_level"] is not None
+    cap_obs = nobs + nops if cap_obs is None else int(cap_obs)
+    nbytes = C.c_size_t(0)
+    _lib.check(L.orbl_apply_map_edits_workspace(nops, nkf, npts, nslots, nobs, C.byref(nbytes)), "orbl_apply_map_edits_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+    assert ws.numel() >= nbytes.value
+    o = {} if out is None else out
+    sizes = dict(_me_sizes(nops, npts, cap_obs, attrs), status=1)
+    tdt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
+    for k, dt in _ME_OUT + (("status", np.int32),):
+        n = sizes[k]
+        if n is None:
+            assert o.get(k) is None, "out[%r] needs the kf_slot_level pair" % k
+            o[k] = None
+            continue
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=tdt[dt], device=dev)[:n]
+        assert o[k].dtype == tdt[dt] and o[k].is_contiguous() and o[k].numel() == n, k
+
+    def p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+    _lib.check(L.orbl_apply_map_edits_device(nops, *[p(v) for v in op], nkf, p(a["kf_slot_off"]), p(a["kf_rank"]), nslots, p(a["kf_slot_pt"]), p(a["kf_slot_level"]),
+                                             p(a["kf_slot_uv"]), npts, p(a["pt_bad"]), p(a["pt_nobs"]), p(a["pt_found"]), p(a["pt_visible"]), p(a["pt_replaced"]), nobs,
+                                             p(a["obs_off"]), p(a["obs_kf"]), p(a["obs_slot"]), p(a["obs_dead"]), cap_obs, *[p(o[k]) for k, _ in _ME_OUT], p(o["status"]),
+                                             p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_apply_map_edits_device")
+    return MapEditResult(rc=0, status=o["status"], _workspace=ws, **{k: a[k] for k in _ME_INOUT}, **{k: o[k] for k, _ in _ME_OUT})
+
+
 # *d_status bits of orbl_local_ba_assemble_device and orbl_local_ba_apply_device
 LA_OFFSETS, LA_KF, LA_PT, LA_RANK, LA_LEVEL, LA_CAP_CAM, LA_CAP_PTS, LA_CAP_OBS, LA_OBS = 1, 2, 4, 8, 16, 32, 64, 128, 256
 

@@ -656,7 +656,7 @@ int orbl_update_connections_workspace(int ntgt, int nkf, int npts, int nslots, i
  * {n_bad, n_conn_out, n_ord_out, n_child_out, n_adopted (children given a candidate as parent), n_fallback (children handed to P)}.
  * Every element inside the counts is written, nothing beyond a capacity; the outputs are the same bytes on every run.
  * OUT OF SCOPE, stays with the caller: map_->EraseKeyFrame, keyframe_database_->erase (orbv_db_erase), map_->EraseMapPoint for the
- * points that turned bad, do_to_be_erased_, LocalMapping::MapPointCulling.
+ * points that turned bad, do_to_be_erased_, LocalMapping::MapPointCulling's tests (its SetBadFlag calls: orbl_apply_map_edits, kind 3).
  * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for negative counts or
  * capacities, NULL where an array is needed, part of the point set without the rest, offsets that do not ascend from 0, indices out of
  * range, a kf_rank that is no permutation, a duplicate target, a status-0 target that is already bad or whose parent is -1 or itself
@@ -699,6 +699,96 @@ int orbl_set_bad_keyframes_device(int ntgt, const int32_t* d_tgt_kf, const uint8
  * + 2 R(4 adds) + R(adds)                                       the new child memberships: parent, child, alive byte
  * + 2 R(4 nkf) + R(12 nkf) + R(4 (nchild + adds))               the current target's children, three row sizes, the gathered children */
 int orbl_set_bad_keyframes_workspace(int ntgt, int nkf, int nchild, int nconn, int nobs, size_t* bytes);
+
+/* ---- Map-point edits on the tables: an ORDERED list of MapPoint::AddObservation / Replace / SetBadFlag calls (src/MapPoint.cc:133-138,
+ * :199-233, :174-191, monocular), as LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:141-152), CreateNewMapPoints (:380-385),
+ * MapPointCulling (:167-194), ORBmatcher::Fuse (src/ORBmatcher.cc:746, :824-838; the Sim3 form :941-950), LoopClosing::CorrectLoop
+ * (src/LoopClosing.cc:527-539) and SearchAndFuse (:615-621) make them, replayed in call order in ONE call that returns the WHOLE new
+ * observation tables.  With nops = 0 it is the rebuild between two other table calls: every other entry only reports deaths in
+ * obs_erased[] and requires its input lists alive.  Keyframes are 0..nkf-1, points 0..npts-1; a freshly created map point is a row the
+ * caller appended with an empty list and pt_nobs = 0, a new keyframe a row with its slots.
+ *   IN: kf_slot_off[nkf + 1]; kf_rank[nkf] (nullable = index order; a permutation: the position under std::less<KeyFrame*>);
+ *     obs_off[npts + 1] / obs_kf[] / obs_slot[], a list naming a keyframe at most once, in any order; obs_dead[nobs] (nullable): an
+ *     obs_erased[] of an earlier call - such entries are ABSENT (only their obs_kf must be a keyframe); kf_slot_level[nslots] and kf_slot_uv[nslots][2] (float), nullable as a pair.
+ *   IN/OUT in place: kf_slot_pt[] (-1 = null); pt_bad[npts]; pt_nobs[npts] = Observations(), which is NOT the list length and is never
+ *     reset, exactly as in the reference; pt_found[npts] / pt_visible[npts] (nullable as a pair); pt_replaced[npts] (nullable, -1 = none).
+ *   The edits, in call order: op_kind[nops], op_pt, op_arg, op_kf, op_slot.
+ * The primitives:
+ *   AddObs(p, K, s)  false when p's list names K; otherwise the list gains (K, s), pt_nobs[p]++, true.
+ *   Replace(a, b)    nothing when a == b.  Otherwise a's list is taken and emptied, pt_bad[a] = 1, pt_replaced[a] = b; for each taken
+ *                    (k, s): when b's list does not name k, slot (k, s) becomes b and AddObs(b, k, s) runs, otherwise slot (k, s)
+ *                    becomes -1; pt_found[b] += pt_found[a], pt_visible[b] += pt_visible[a] (a's counters are NOT cleared: a second
+ *                    Replace of the same a adds them again, as SearchAndFuse can); b is TOUCHED (ComputeDistinctiveDescriptors, :230).
+ *                    No bad-flag test on a or on b.
+ *   SetBad(p)        pt_bad[p] = 1, p's list is emptied, every slot it named becomes -1.
+ * Kinds and op_status:
+ *   0 NOP                                  a row the caller masked out.  Status 0.
+ *   1 ADD(p = op_pt, K, s; op_arg bit 0 = touch)   ok = AddObs(p, K, s); slot (K, s) becomes p UNCONDITIONALLY (KeyFrame::AddMapPoint;
+ *                                          LoopClosing.cc:534-535 writes it even when p is observed elsewhere in K); with bit 0 p is
+ *                                          touched.  Status 5 when ok, 6 when not.
+ *   2 REPLACE(a = op_pt, b = op_arg)       Replace(a, b).  Status 8, or 1 when a == b.
+ *   3 SET_BAD(p)                           SetBad(p): the mutation of MapPointCulling; its found-ratio and age tests stay with the
+ *                                          caller.  Status 9.
+ *   4 FUSE(p, K, s)                        skipped (1) when pt_bad[p] or p's list names K.  Otherwise q = slot (K, s): q >= 0 and bad:
+ *                                          nothing (2); q >= 0 and not bad: pt_nobs[q] > pt_nobs[p] ? Replace(p, q) (3) : Replace(q, p)
+ *                                          (4; a tie replaces q); q < 0: ADD without touch (5; 6 cannot occur after the skip test).
+ *   5 FIND_OR_ADD(p, K, s)                 q = slot (K, s): q >= 0 and bad: nothing (2); q >= 0 and alive: op_found = q (7); q < 0: ADD
+ *                                          without touch (5 or 6).  No skip test: the caller filters isBad() || spAlreadyFound (:872)
+ *                                          before the call - exact, because a Sim3 Fuse changes no bad flag and the set is a snapshot.
+ *   6 REPLACE_FOUND(j = op_arg, b = op_pt) j < i names a kind-5 op: a = op_found[j]; -1: skipped (1); otherwise Replace(a, b) (8, or 1
+ *                                          when a == b).
+ *   op_found[i] = the point a kind-4 or kind-5 op met ALIVE in its slot, else -1.
+ * Outputs: op_status[nops], op_found[nops]; pt_touched[npts] (uint8, every element written); the in/out tables; the whole new tables,
+ * each list in ascending kf_rank (the std::map order every other entry wants): oobs_off[npts + 1], oobs_kf, oobs_slot, oobs_src
+ * (nullable: the input index e of a surviving or moved observation, nobs + i for the one op i created) and, with the kf_slot_level pair,
+ * oobs_level / oobs_uv gathered from (keyframe, slot) - of capacity cap_obs; nobs + nops always suffices.  counts[8] = {n_obs_out,
+ * n_obs_added (observations created: the ops that ended with status 5), n_replace (Replace calls that ran), n_set_bad, n_fused (ops of
+ * kinds 4 and 5 with status 2, 3, 4, 5 or 7: the nFused both Fuse functions return, with ONE exception - the Sim3 form increments
+ * nFused for a row whose AddObservation is refused as well (kind 5, status 6), which is not counted here; add the ops with that
+ * status for the reference's number), n_touched, n_late_adds, 0}.
+ * n_late_adds = the points that were touched and received an observation created by an op AFTER their last touch.  The caller recomputes
+ * descriptors after the call: one orbl_update_map_points(_device) on the pt_touched points equals the reference's in-loop
+ * ComputeDistinctiveDescriptors exactly when this count is 0.  It is 0 for any single-keyframe Fuse, for the CorrectLoop loop and for a
+ * SearchAndFuse keyframe, because after its touch a point is in the keyframe or bad: Replace(x, b) runs only when b is in the slot or
+ * takes it over from x, so b's list names K from then on and FUSE skips it (1), while x is bad and is skipped too; FIND_OR_ADD never
+ * touches, and the REPLACE_FOUND ops that do come after every add of their keyframe.
+ * Every element inside a count is written, nothing beyond a count or a capacity; the outputs are the same bytes on every run.
+ * Host pointers, synchronous, one packed upload and one download.  ORBHIP_EINVAL before any device work for negative counts or
+ * capacities, NULL where an array is needed or half of a nullable pair, offsets that do not ascend from 0, an index, slot or kind out of
+ * range, a kf_rank that is no permutation, a list naming a keyframe twice, an alive observation whose slot does not hold its point, the
+ * op_arg of a kind-6 op not in [0, i) or not naming a kind-5 op; ORBHIP_ENODEV without a GPU (there is no CPU fallback); ORBHIP_ECAP, with
+ * only counts[] written and the in/out tables untouched, when cap_obs is too small.                                                   */
+int orbl_apply_map_edits(int nops, const int32_t* op_kind, const int32_t* op_pt, const int32_t* op_arg, const int32_t* op_kf, const int32_t* op_slot, int nkf,
+                         const int32_t* kf_slot_off, const int32_t* kf_rank, int32_t* kf_slot_pt, const int32_t* kf_slot_level, const float* kf_slot_uv, int npts,
+                         uint8_t* pt_bad, int32_t* pt_nobs, int32_t* pt_found, int32_t* pt_visible, int32_t* pt_replaced, const int32_t* obs_off,
+                         const int32_t* obs_kf, const int32_t* obs_slot, const uint8_t* obs_dead, int cap_obs, int32_t* op_status, int32_t* op_found,
+                         uint8_t* pt_touched, int32_t* oobs_off, int32_t* oobs_kf, int32_t* oobs_slot, int32_t* oobs_src, int32_t* oobs_level, float* oobs_uv,
+                         int32_t* counts);
+/* The same with DEVICE pointers, enqueued on `stream`: no synchronisation, no allocation and no host read of the data (nslots =
+ * kf_slot_off[nkf], nobs = obs_off[npts] given by the caller; d_kf_slot_off and d_obs_off are needed even without rows: one 0).
+ * d_counts[8] always holds the WANTED counts.  Counts, NULL pointers and alignment (4 bytes) are checked on the host; the data is
+ * bounds-checked on the device: an op out of range is ABSENT (op_status 10, op_found -1), an observation out of range is absent, a slot
+ * holding a point out of range counts as null.  *d_status (nullable; zeroed first): 1 = offsets; 2 = a keyframe out of range or a
+ * kf_rank that is no permutation; 4 = a point out of range; 8 = a slot its keyframe does not have, a kind out of range or a kind-6 op
+ * whose op_arg names no earlier kind-5 op; 16 = cap_obs exceeded (the elements below the capacity are still written, none beyond it).
+ * PRECONDITIONS, not checked here: no list names a keyframe twice, and an alive observation's slot holds its point.  `d_workspace`: at
+ * least orbl_apply_map_edits_workspace(...) bytes of device memory, 4-byte aligned, not shared with concurrent calls; it is cleared by
+ * every call, so calls may reuse it.                                                                                                  */
+int orbl_apply_map_edits_device(int nops, const int32_t* d_op_kind, const int32_t* d_op_pt, const int32_t* d_op_arg, const int32_t* d_op_kf,
+                                const int32_t* d_op_slot, int nkf, const int32_t* d_kf_slot_off, const int32_t* d_kf_rank, int nslots, int32_t* d_kf_slot_pt,
+                                const int32_t* d_kf_slot_level, const float* d_kf_slot_uv, int npts, uint8_t* d_pt_bad, int32_t* d_pt_nobs, int32_t* d_pt_found,
+                                int32_t* d_pt_visible, int32_t* d_pt_replaced, int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf,
+                                const int32_t* d_obs_slot, const uint8_t* d_obs_dead, int cap_obs, int32_t* d_op_status, int32_t* d_op_found, uint8_t* d_pt_touched,
+                                int32_t* d_oobs_off, int32_t* d_oobs_kf, int32_t* d_oobs_slot, int32_t* d_oobs_src, int32_t* d_oobs_level, float* d_oobs_uv,
+                                int32_t* d_counts, uint32_t* d_status, void* d_workspace, void* stream);
+/* *bytes = the workspace orbl_apply_map_edits_device needs (host arithmetic; nslots does not enter).  With R(x) = x rounded up to a
+ * multiple of 256, ents = nobs + nops and blocks = ceil(npts / 256):
+ *   2 R(npts) + R(4 nkf) + R(8)                 cleared by every call: a point's list was emptied, it has a late add; the rank check;
+ *                                               two counters
+ * + R(4 npts) + R(4 ents) + R(nobs)             the head of a point's chain of received entries, the chain links, one byte per input
+ *                                               observation that is there
+ * + 2 R(4 npts) + R(4 (blocks + 1)) + R(4 ents) the new list lengths and their scan, the workgroup sums, the gathered entries         */
+int orbl_apply_map_edits_workspace(int nops, int nkf, int npts, int nslots, int nobs, size_t* bytes);
 
 /* ---- LoopClosing::CorrectLoop, the part that moves the map (src/LoopClosing.cc:437-523): the corrected and non-corrected Sim3 of the
  * current keyframe's covisibility group, the correction of every map point those keyframes hold, UpdateNormalAndDepth of each moved
