@@ -22,7 +22,7 @@ SYMBOLS = [
     "orbl_essential_graph_apply", "orbl_essential_graph_apply_device", "orbl_essential_graph_apply_workspace",
     "orbl_global_ba_assemble", "orbl_global_ba_assemble_device", "orbl_global_ba_assemble_workspace",
     "orbl_global_ba_apply", "orbl_global_ba_apply_device", "orbl_global_ba_apply_workspace",
-    "orbt_relocalization_search_by_bow",
+    "orbt_relocalization_search_by_bow", "orbt_relocalization_refine",
     "orbt_initialize", "orbt_initialize_batch_device", "orbt_initialize_workspace",
     "orbt_pnp_ransac_params", "orbt_pnp_iterate", "orbt_pnp_iterate_batch_device", "orbt_pnp_iterate_workspace",
     "orbt_sim3_ransac_params", "orbt_sim3_iterate", "orbt_sim3_iterate_batch_device", "orbt_sim3_iterate_workspace",
@@ -195,6 +195,7 @@ def load():
                                                 C.POINTER(i32), vp, vp, vp, vp]
     L.orbt_track_local_map.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp]
     L.orbt_track_local_map_device.argtypes = [vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp]
+    L.orbt_relocalization_refine.argtypes = [vp, vp, vp, f32, vp, i32, i32, i32, i32, vp, vp, vp, C.POINTER(i32)]
     L.orbt_update_local_keyframes.argtypes = [i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp]
     L.orbt_update_local_points.argtypes = [i32, vp, vp, i32] + [vp] * 7 + [i32, vp, i32, vp, i32, vp, C.POINTER(i32)] + [vp] * 8
     L.orbt_update_local_map_device.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, vp, i32] + [vp] * 7 + [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp,

@@ -1213,6 +1213,97 @@ struct FrameOpsT {
     return std::vector<size_t>(idx.begin(), idx.begin() + total);
   }
 
+  // Tracking::Relocalization, everything behind `Tcw = pSolver->iterate(...)` (src/Tracking.cc:1056-1126) for ALL candidates of one pass of
+  // the `while` loop in ONE call (orbt_relocalization_refine) on the frame `extractor` left on the device for this thread
+  // (orbt_relocalization_search_by_bow at the top of Relocalization): per candidate i that has a pose - poses[i] is not the identity,
+  // :1059 - matches[i] = map_point_matches_vector[i] and inliers[i] = is_inliers of its PnP solver.  Returns the index of the first
+  // candidate with nGood >= 50, where the reference breaks out (:1122-1125), and leaves Tcw_, map_points_ and is_outliers_ of
+  // current_frame as that candidate's refinement leaves them; -1: no candidate matched, and the frame is left as the LAST refined
+  // candidate leaves it (the reference went through all of them).  is_outliers_ is written for every feature (the reference keeps flags of
+  // earlier candidates on slots that are empty now; nothing reads a flag of an empty slot).  The map points' min_distance_ /
+  // max_distance_ are read directly: MapPoint.h declares `template <class> friend struct FrameOpsT;`.
+  // (Matrix4d is a template parameter: a Types bundle without Tracking's matrix type can still instantiate the rest of FrameOpsT.)
+  template <class Matrix4d>
+  static int RelocalizationRefine(orbx_ctx* extractor, Frame& current_frame, const std::vector<KeyFrame*>& candidate_keyframes,
+                                  const std::vector<std::vector<MapPoint*> >& matches, const std::vector<Matrix4d>& poses,
+                                  const std::vector<std::vector<bool> >& inliers, bool check_orientation = true, bool narrow_in_loop = true) {
+    using namespace dropin;
+    const size_t nc = candidate_keyframes.size();
+    if (matches.size() != nc || poses.size() != nc || inliers.size() != nc) throw std::runtime_error("FrameOpsT::RelocalizationRefine: one entry per candidate keyframe is needed");
+    if (!nc) return -1;
+    const int n_kp = current_frame.N_;
+    struct Cand { std::vector<int32_t> pt, slot; std::vector<double> X; std::vector<uint8_t> desc; std::vector<float> mn, mx, ang; std::vector<MapPoint*> row; double T[12]; bool has_pose; };
+    std::vector<Cand> C(nc);
+    std::vector<orbt_reloc_refine_candidate> flat(nc);
+    std::unordered_map<MapPoint*, int32_t> id_of;
+    auto is_identity = [](const Matrix4d& T) { for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) if (T(r, c) != (r == c ? 1.0 : 0.0)) return false; return true; };
+    for (size_t c = 0; c < nc; c++) {
+      Cand& Q = C[c];
+      KeyFrame* kf = candidate_keyframes[c];
+      Q.has_pose = kf && !is_identity(poses[c]);
+      if (kf) Q.row = kf->GetMapPointMatches();
+      auto push = [&](MapPoint* mp, bool searchable, float angle) {      // one row of the keyframe side
+        const bool usable = mp && !mp->isBad();
+        int32_t id = -1;
+        if (usable || (mp && !searchable)) { auto it = id_of.find(mp); id = it == id_of.end() ? (id_of[mp] = (int32_t)id_of.size()) : it->second; }
+        Q.pt.push_back(id);
+        const Vector3d p = mp ? mp->GetWorldPos() : Vector3d();
+        for (int k = 0; k < 3; k++) Q.X.push_back(mp ? p[k] : 0.0);
+        Q.desc.resize(Q.desc.size() + 32, 0);
+        if (mp) { const auto d = mp->GetDescriptor(); std::memcpy(&Q.desc[Q.desc.size() - 32], d.ptr(0), 32); }
+        // (a row that must not be searched - below - has an empty distance range: every distance is outside it)
+        Q.mn.push_back(mp && searchable ? mp->min_distance_ : 0.f); Q.mx.push_back(mp && searchable ? mp->max_distance_ : 0.f);
+        Q.ang.push_back(angle);
+      };
+      for (size_t i = 0; i < Q.row.size(); i++) push(Q.row[i], true, kf->undistort_keypoints_[i].angle);
+      Q.slot.assign((size_t)std::max(n_kp, 1), -1);
+      if (Q.has_pose) {
+        std::unordered_map<MapPoint*, int32_t> at;                      // the first feature of the keyframe that holds the point
+        for (size_t i = 0; i < Q.row.size(); i++) if (Q.row[i] && !Q.row[i]->isBad()) at.insert(std::make_pair(Q.row[i], (int32_t)i));
+        for (int f = 0; f < n_kp && f < (int)matches[c].size() && f < (int)inliers[c].size(); f++) {
+          MapPoint* mp = inliers[c][f] ? matches[c][f] : static_cast<MapPoint*>(nullptr);
+          if (!mp) continue;
+          auto it = at.find(mp);
+          if (it == at.end()) {
+            // an inlier point the keyframe does not hold (any more), or a bad one: it still is an observation of PoseOptimization and an
+            // element of `found`, but SearchByProjection never walks it - a row of its own behind the keyframe's, closed to the search
+            it = at.insert(std::make_pair(mp, (int32_t)Q.row.size())).first;
+            Q.row.push_back(mp); push(mp, false, 0.f);
+          }
+          Q.slot[f] = it->second;
+        }
+        for (int r = 0; r < 3; r++) for (int k = 0; k < 4; k++) Q.T[4 * r + k] = poses[c](r, k);
+      }
+      orbt_reloc_refine_candidate& q = flat[c];
+      q.pt = Q.pt.data(); q.Xw = Q.X.data(); q.desc = Q.desc.data(); q.min_dist = Q.mn.data(); q.max_dist = Q.mx.data(); q.angle = Q.ang.data();
+      q.n = (int32_t)Q.pt.size(); q.reserved = 0; q.Tcw = Q.has_pose ? Q.T : nullptr; q.slot_kf = Q.has_pose ? Q.slot.data() : nullptr;
+    }
+    const float K4[4] = {current_frame.fx_, current_frame.fy_, current_frame.cx_, current_frame.cy_};
+    const float bounds[4] = {(float)current_frame.min_x_, (float)current_frame.max_x_, (float)current_frame.min_y_, (float)current_frame.max_y_};
+    std::vector<orbt_reloc_refine_result> res(nc);
+    std::vector<int32_t> slot_out(nc * (size_t)std::max(n_kp, 1), -1); std::vector<uint8_t> outl(nc * (size_t)std::max(n_kp, 1), 0);
+    int32_t first = -1;
+    check(orbt_relocalization_refine(extractor, K4, bounds, current_frame.log_scale_factor_, flat.data(), (int)nc, n_kp, check_orientation ? 1 : 0, narrow_in_loop ? 1 : 0,
+                                     res.data(), slot_out.data(), outl.data(), &first), "orbt_relocalization_refine");
+    int take = first;
+    if (take < 0) for (size_t c = 0; c < nc; c++) if (C[c].has_pose) take = (int)c;
+    if (take < 0) return -1;                                              // nobody had a pose: the frame was not touched
+    Matrix4d T;
+    {
+      double M[16];
+      check(ba_pose7_to_matrix4d(res[take].pose7, M), "ba_pose7_to_matrix4d");
+      for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) T(r, k) = M[4 * r + k];
+    }
+    // (a candidate whose first PoseOptimization had fewer than 3 correspondences leaves the PnP pose as it was: current_frame_.Tcw_ = Tcw, :1060)
+    if (res[take].n_correspondences[0] < 3) current_frame.Tcw_ = poses[take]; else current_frame.SetPose(T);
+    for (int f = 0; f < n_kp; f++) {
+      const int32_t s = slot_out[(size_t)take * n_kp + f];
+      current_frame.map_points_[f] = s >= 0 ? C[take].row[s] : static_cast<MapPoint*>(nullptr);
+      current_frame.is_outliers_[f] = outl[(size_t)take * n_kp + f] != 0;
+    }
+    return first;
+  }
+
   // LocalMapping::CreateNewMapPoints, the body of "Triangulate each match" (src/LocalMapping.cc:267-378) for all matches of one
   // neighbour keyframe: x3D[k] / ok[k] for matched_indices[k]; the caller keeps the MapPoint construction (":380-395").
   static void TriangulateMatches(KeyFrame* current_keyframe, KeyFrame* neighbor_keyframe, const std::vector<std::pair<size_t, size_t> >& matched_indices,

@@ -41,6 +41,7 @@
 
 #include "../../include/orbslam_hip.h"
 #include "common.h"
+#include "ba_math.h"
 #include "orb_frame.h"
 
 namespace orbhip {
@@ -1668,9 +1669,9 @@ int orbt_track_reference_keyframe(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* i
 // vocabulary descent once, then the three kernels of the reference-keyframe step per candidate (k_trf_init, k_trf_bow: one wave per
 // vocabulary node, k_trf_finish: the rotation histogram), all on the calling thread's stream, one upload, one download.  The
 // candidates are independent (each fills its own vpMapPointMatches).  What follows in the reference - PnPsolver RANSAC per candidate,
-// then PoseOptimization / SearchByProjection(F, KF, found, th, ORBdist) rounds - is made of further calls: the PnP RANSAC of all
-// candidates is orbt_pnp_iterate_batch_device (orb_pnp.inc, included below), the rounds are ba_pose_optimization and
-// orbm_search_by_projection's reloc_kf form.
+// then PoseOptimization / SearchByProjection(F, KF, found, th, ORBdist) rounds - is made of two further calls: the PnP RANSAC of all
+// candidates is orbt_pnp_iterate_batch_device (orb_pnp.inc, included below), everything behind a PnP pose is
+// orbt_relocalization_refine (orb_relocrefine.inc, included below), for every candidate at once on the frame this call leaves.
 int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_t* img, int w, int h, int stride, const float* K4, const float* bounds,
                                       const orbt_reloc_keyframe* cand, int n_cand, float nnratio, int check_ori, orbx_keypoint* kps_out, uint8_t* desc_out, int cap,
                                       uint32_t* bow_word, double* bow_value, int* n_words, uint32_t* fv_node, uint32_t* fv_off, uint32_t* fv_idx, int* n_fv_nodes,
@@ -1745,3 +1746,4 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
 #include "orb_pnp.inc"                  /* PnPsolver::iterate with EPnP for a batch of candidates: orbt_pnp_* */
 #include "orb_sim3solver.inc"          /* Sim3Solver::iterate (Horn inside RANSAC) for a batch of loop candidates: orbt_sim3_* */
 #include "orb_localupdate.inc"         /* Tracking::UpdateLocalMap: local keyframes, local points and the gather TrackLocalMap reads: orbt_update_local_* */
+#include "orb_relocrefine.inc"         /* Tracking::Relocalization behind a PnP pose, every candidate of a round at once: orbt_relocalization_refine */

@@ -240,6 +240,65 @@ def relocalization_search_by_bow(extractor, vocabulary, image, K4, bounds, candi
                 fv=(on[:nf.value], oo[:nf.value + 1], oi[:oo[nf.value]]), owner=owner[:nc, :k], nmatches=nm[:nc], n_keypoints=k)
 
 
+# ---- Tracking::Relocalization behind a PnP pose (reference src/Tracking.cc:1056-1126) ----
+RR_MAX_CANDIDATES = 64
+RR_NO_POSE, RR_FEW_INLIERS, RR_MATCH_FIRST, RR_MATCH_SECOND, RR_MATCH_THIRD, RR_FAIL_WIDE, RR_FAIL_SECOND, RR_FAIL_NARROW, RR_FAIL_THIRD = range(9)
+
+
+class _RefineCand(C.Structure):      # orbt_reloc_refine_candidate
+    _fields_ = [("pt", C.c_void_p), ("Xw", C.c_void_p), ("desc", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p), ("angle", C.c_void_p),
+                ("n", C.c_int32), ("reserved", C.c_int32), ("Tcw", C.c_void_p), ("slot_kf", C.c_void_p)]
+
+
+class _RefineResult(C.Structure):    # orbt_reloc_refine_result
+    _fields_ = [("stage", C.c_int32), ("matched", C.c_int32), ("narrow_passes", C.c_int32), ("reserved", C.c_int32), ("n_good", C.c_int32 * 3),
+                ("n_additional", C.c_int32 * 2), ("n_correspondences", C.c_int32 * 3), ("pose7", C.c_double * 7)]
+
+
+def relocalization_refine(extractor, K4, bounds, candidates, log_scale_factor, check_ori=True, narrow_in_loop=True, n_kp=None, out=None):
+    """Everything Tracking::Relocalization does behind a PnP pose, for every candidate of a round in one call on the frame the last
+    extracting track_* / relocalization_search_by_bow call of THIS thread left on the device (include/orbslam_hip.h::
+    orbt_relocalization_refine).  candidates: dicts(pt[n] point ids or -1, Xw[n, 3], desc[n, 32], min_dist[n], max_dist[n], angle[n],
+    Tcw (3 or 4, 4) or None, slot_kf[n_kp] or None without a pose).  n_kp: the frame's keypoint count (default: the length of the first
+    slot_kf).  out: optional (slot_kf_out, outlier) int32 / uint8 arrays of n_cand x n_kp entries to write into.
+    Returns dict(first_match, results = one dict per candidate (stage, matched, narrow_passes, n_good[3], n_additional[2],
+    n_correspondences[3], pose7, slot_kf[n_kp], outlier[n_kp]))."""
+    L = _lib.load()
+    K4 = _c(K4, np.float32); bounds = _c(bounds, np.float32)
+    nc = len(candidates)
+    if n_kp is None:
+        n_kp = next((len(q["slot_kf"]) for q in candidates if q.get("slot_kf") is not None), 0)
+    n_kp = int(n_kp)
+    cs = (_RefineCand * max(nc, 1))()
+    keep = []
+    for i, q in enumerate(candidates):
+        P = _c(q["pt"], np.int32).reshape(-1); n = len(P)
+        X = _c(q["Xw"], np.float64).reshape(-1, 3); D = _c(q["desc"], np.uint8).reshape(-1, 32)
+        mn = _c(q["min_dist"], np.float32).reshape(-1); mx = _c(q["max_dist"], np.float32).reshape(-1); A = _c(q["angle"], np.float32).reshape(-1)
+        assert len(X) == n and len(D) == n and len(mn) == n and len(mx) == n and len(A) == n
+        keep += [P, X, D, mn, mx, A]
+        cs[i].pt, cs[i].Xw, cs[i].desc, cs[i].min_dist, cs[i].max_dist, cs[i].angle, cs[i].n = _addr(P), _addr(X), _addr(D), _addr(mn), _addr(mx), _addr(A), n
+        if q.get("Tcw") is not None:
+            T = np.ascontiguousarray(np.asarray(q["Tcw"], np.float64).reshape(-1)[:12]); S = _c(q["slot_kf"], np.int32).reshape(-1)
+            assert len(S) == n_kp
+            keep += [T, S]
+            cs[i].Tcw, cs[i].slot_kf = _addr(T), _addr(S)
+    res = (_RefineResult * max(nc, 1))()
+    if out is None:
+        slot = np.full((max(nc, 1), max(n_kp, 1)), -1, np.int32); outl = np.zeros((max(nc, 1), max(n_kp, 1)), np.uint8)
+    else:
+        slot, outl = out
+        assert slot.dtype == np.int32 and outl.dtype == np.uint8 and slot.flags.c_contiguous and outl.flags.c_contiguous and slot.size >= nc * n_kp and outl.size >= nc * n_kp
+    first = C.c_int32(-1)
+    _lib.check(L.orbt_relocalization_refine(extractor._h, _addr(K4), _addr(bounds), float(log_scale_factor), C.cast(cs, C.c_void_p), nc, n_kp, int(bool(check_ori)),
+                                            int(bool(narrow_in_loop)), C.cast(res, C.c_void_p), _addr(slot), _addr(outl), C.byref(first)), "orbt_relocalization_refine")
+    fs = slot.reshape(-1)[:nc * n_kp].reshape(nc, n_kp); fo = outl.reshape(-1)[:nc * n_kp].reshape(nc, n_kp)
+    results = [dict(stage=r.stage, matched=bool(r.matched), narrow_passes=r.narrow_passes, n_good=list(r.n_good), n_additional=list(r.n_additional),
+                    n_correspondences=list(r.n_correspondences), pose7=np.array(r.pose7[:], np.float64), slot_kf=fs[i], outlier=fo[i].view(np.bool_))
+               for i, r in enumerate(res[:nc])]
+    return dict(first_match=first.value, results=results)
+
+
 # ---- Tracking::UpdateLocalMap (reference src/Tracking.cc:838-977; include/orbslam_hip.h states the tables and the semantics) ----
 ULM_OK, ULM_NO_VOTES = 0, 1
 _PACKED = (("mp_Xw", np.float64, 3), ("mp_normal", np.float64, 3), ("mp_min_dist", np.float32, 1), ("mp_max_dist", np.float32, 1), ("mp_desc", np.uint8, 32),

@@ -407,8 +407,9 @@ int orbm_search_for_triangulation(const float* kps1, const uint8_t* desc1, const
  * frame an earlier orbt_* call of this thread left there.  Per candidate i: slot_owner[i][f] = the keyframe feature whose map
  * point vpMapPointMatches[f] holds (-1: none) after the rotation check, nmatches[i] = the return value (the caller discards the
  * candidate below 15, :1019).  What follows - PnPsolver::iterate per candidate, then PoseOptimization /
- * SearchByProjection(F, KF, found, th, ORBdist) rounds (:1040-1120) - is made of further calls: orbt_pnp_iterate_batch_device runs
- * one PnPsolver::iterate of every candidate, the rounds are ba_pose_optimization and the reloc_kf form of orbm_search_by_projection. */
+ * SearchByProjection(F, KF, found, th, ORBdist) rounds (:1040-1120) - is made of two further calls: orbt_pnp_iterate_batch_device runs
+ * one PnPsolver::iterate of every candidate, and orbt_relocalization_refine (below) runs everything behind a PnP pose for every
+ * candidate that has one, on the frame this call left on the device. */
 typedef struct orbt_reloc_keyframe {
   const uint8_t* desc; const uint8_t* valid; const float* angle; int n;      /* descriptors, 1 = usable map point (not NULL, not isBad()), keypoint angles */
   const uint32_t* fv_node; const uint32_t* fv_off; const uint32_t* fv_idx; int fv_n;      /* the keyframe's FeatureVector (orbv_transform's layout) */
@@ -418,6 +419,58 @@ int orbt_relocalization_search_by_bow(orbx_ctx* ctx, orbv_ctx* voc, const uint8_
                                       uint8_t* desc_out, int cap, uint32_t* bow_word, double* bow_value, int* n_words, uint32_t* fv_node, uint32_t* fv_off,
                                       uint32_t* fv_idx, int* n_fv_nodes, int32_t* slot_owner /*[n_candidates][cap]*/, int32_t* nmatches /*[n_candidates]*/,
                                       int* n_keypoints);
+
+/* ---- Tracking::Relocalization behind a PnP pose (src/Tracking.cc:1056-1126), for EVERY candidate of a `while` round in ONE call on
+ * the resident frame: PoseOptimization, SearchByProjection(F, KF, found, 10, 100), PoseOptimization, SearchByProjection(F, KF, found,
+ * 3, 64), PoseOptimization, with the gates `< 10`, `< 50`, `nadditional + nGood >= 50`, `30 < nGood < 50` and `>= 50` decided on the
+ * device: one upload, a fixed sequence of 14 launches whatever the sizes, one download, one synchronisation.  The candidates are
+ * independent (:1066-1072 overwrites every slot per candidate), so all of them are refined and *first_match is the lowest index with
+ * nGood >= 50 (-1: none): the candidate at which the reference breaks out of its loop.  The caller takes that candidate's outputs.
+ *   per candidate  n <= 4096 keyframe features; per feature i: pt[i] = an id (>= 0, any value) of the map point in
+ *        GetMapPointMatches()[i], -1 for NULL or isBad() - `found` is a set of these ids, so a point held at two features behaves as
+ *        in the reference's std::set<MapPoint*>; Xw[i][3]; desc[i][32] = MapPoint::GetDescriptor(); min_dist / max_dist = the raw
+ *        min_distance_ / max_distance_ (the 0.8 / 1.2 factors are applied inside); angle[i] = undistort_keypoints_[i].angle (the
+ *        five arrays are read where pt[i] >= 0).  Tcw = the PnP pose, row-major 3x4 (or the first 12 of a 4x4); NULL: the candidate has
+ *        no pose in this round and is not refined.  slot_kf[n_kp] = the keyframe feature whose point current_frame_.map_points_[f]
+ *        holds after the is_inliers masking of :1066-1072, -1 none; it must name features with pt >= 0.
+ *   call  K4, bounds, log_scale_factor as for orbt_track_local_map; n_kp = the resident frame's keypoint count; check_ori = the
+ *        matcher's mbCheckOrientation (the reference: 1); narrow_in_loop = 1: the narrow search sits INSIDE the `for (ip < N_)` loop
+ *        as in the reference (:1097-1104) - evaluated exactly as the passes in order, each with `found` as it stands at its ip, up
+ *        to the first pass that assigns nothing (every later pass is empty then, and nadditional is 0 unless pass N_ - 1 ran);
+ *        0: upstream ORB-SLAM2's placement, ONE search behind the loop with every slot's point in `found`.
+ *   out  res[c]: stage (ORBT_RR_*), matched, narrow_passes (passes run, <= N_), n_good[k] / n_correspondences[k] of the k-th
+ *        PoseOptimization and n_additional[0] / [1] of the wide / narrow search (-1 where one did not run), pose7 = the pose
+ *        current_frame_ ends with; slot_kf_out[c][n_kp] / outlier[c][n_kp] = map_points_ (as keyframe features) and is_outliers_ as
+ *        the reference leaves them for that candidate, starting from flags that are all false.  Nothing is written beyond
+ *        n_candidates x n_kp entries.  Quirks kept: outlier slots are cleared behind the first and the third solve, not behind the
+ *        second; `found` of the wide search is the PnP inlier set with the slots cleared since still in it; a point outside `found`
+ *        that already sits in a slot is matched a second time.
+ * At most ORBT_RR_MAX_CANDIDATES candidates per call.  ORBHIP_EINVAL, before any device work, for NULL arguments, negative counts,
+ * pt[i] < -1, a slot_kf entry out of range or naming a feature without a point (the message names the entry and the array), and -
+ * with a device - without a resident frame of ctx on the calling thread or with another n_kp than it has; ORBHIP_ECAP for more than 64
+ * candidates or 4096 features; ORBHIP_ENODEV without a GPU.  The call needs no caller scratch.                                      */
+#define ORBT_RR_MAX_CANDIDATES 64
+#define ORBT_RR_NO_POSE 0         /* no pose, or fewer than 3 correspondences: PoseOptimization returned 0 */
+#define ORBT_RR_FEW_INLIERS 1     /* nGood < 10 behind the first solve */
+#define ORBT_RR_MATCH_FIRST 2     /* nGood >= 50 behind the first solve */
+#define ORBT_RR_MATCH_SECOND 3    /* ... behind the second */
+#define ORBT_RR_MATCH_THIRD 4     /* ... behind the third */
+#define ORBT_RR_FAIL_WIDE 5       /* nadditional + nGood < 50 behind the wide search: no second solve */
+#define ORBT_RR_FAIL_SECOND 6     /* nGood <= 30 behind the second solve: no narrow search */
+#define ORBT_RR_FAIL_NARROW 7     /* nGood + nadditional < 50 behind the narrow search: no third solve */
+#define ORBT_RR_FAIL_THIRD 8      /* nGood < 50 behind the third solve */
+typedef struct orbt_reloc_refine_candidate {
+  const int32_t* pt; const double* Xw; const uint8_t* desc; const float* min_dist; const float* max_dist; const float* angle; int32_t n, reserved;
+  const double* Tcw; const int32_t* slot_kf;
+} orbt_reloc_refine_candidate;
+typedef struct orbt_reloc_refine_result {
+  int32_t stage, matched, narrow_passes, reserved;
+  int32_t n_good[3], n_additional[2], n_correspondences[3];
+  double pose7[7];
+} orbt_reloc_refine_result;
+int orbt_relocalization_refine(orbx_ctx* ctx, const float* K4, const float* bounds, float log_scale_factor, const orbt_reloc_refine_candidate* candidates,
+                               int n_candidates, int n_kp, int check_ori, int narrow_in_loop, orbt_reloc_refine_result* res /*[n_candidates]*/,
+                               int32_t* slot_kf_out /*[n_candidates][n_kp]*/, uint8_t* outlier /*[n_candidates][n_kp]*/, int32_t* first_match);
 
 /* ---- LocalMapping::CreateNewMapPoints, device-resident across the neighbour keyframes (src/LocalMapping.cc:196-396; round 5) ----
  * For every neighbour keyframe IN ORDER: ORBmatcher::SearchForTriangulation(current, neighbour, F12, pairs, false) with the matcher of
