@@ -14,6 +14,9 @@ SYMBOLS = [
     "orbl_update_connections", "orbl_update_connections_device", "orbl_update_connections_workspace",
     "orbl_set_bad_keyframes", "orbl_set_bad_keyframes_device", "orbl_set_bad_keyframes_workspace",
     "orbl_apply_map_edits", "orbl_apply_map_edits_device", "orbl_apply_map_edits_workspace",
+    "orbl_fuse_targets", "orbl_fuse_targets_device", "orbl_fuse_targets_workspace", "orbl_fuse_rows", "orbl_fuse_rows_device", "orbl_fuse_rows_workspace",
+    "orbl_fuse_candidates", "orbl_fuse_candidates_device", "orbl_fuse_candidates_workspace",
+    "orbl_update_map_points_on_tables", "orbl_update_map_points_on_tables_device", "orbl_update_map_points_on_tables_workspace",
     "orbl_correct_loop", "orbl_correct_loop_device", "orbl_correct_loop_workspace",
     "orbl_propagate_global_ba", "orbl_propagate_global_ba_device", "orbl_propagate_global_ba_workspace",
     "orbl_local_ba_assemble", "orbl_local_ba_assemble_device", "orbl_local_ba_assemble_workspace",
@@ -243,6 +246,18 @@ def load():
     L.orbl_apply_map_edits.argtypes = [i32] + [vp] * 5 + [i32] + [vp] * 5 + [i32] + [vp] * 9 + [i32] + [vp] * 10
     L.orbl_apply_map_edits_device.argtypes = [i32] + [vp] * 5 + [i32, vp, vp, i32, vp, vp, vp, i32] + [vp] * 5 + [i32] + [vp] * 4 + [i32] + [vp] * 13
     L.orbl_apply_map_edits_workspace.argtypes = [i32, i32, i32, i32, i32, C.POINTER(sz)]
+    L.orbl_fuse_targets.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.orbl_fuse_targets_device.argtypes = [i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32] + [vp] * 5
+    L.orbl_fuse_targets_workspace.argtypes = [i32, C.POINTER(sz)]
+    L.orbl_fuse_rows.argtypes = [i32, i32, vp, i32] + [vp] * 8 + [i32] + [vp] * 7 + [f32, i32, f32] + [vp] * 9
+    L.orbl_fuse_rows_device.argtypes = [vp, i32, vp, i32] + [vp] * 5 + [i32, vp, vp, vp, i32] + [vp] * 7 + [f32, i32, f32] + [vp] * 12
+    L.orbl_fuse_rows_workspace.argtypes = [i32, C.POINTER(sz)]
+    L.orbl_fuse_candidates.argtypes = [i32, vp, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp]
+    L.orbl_fuse_candidates_device.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32] + [vp] * 5
+    L.orbl_fuse_candidates_workspace.argtypes = [i32, i32, C.POINTER(sz)]
+    L.orbl_update_map_points_on_tables.argtypes = [i32, vp, i32, i32] + [vp] * 6 + [i32] + [vp] * 7 + [i32] + [vp] * 6
+    L.orbl_update_map_points_on_tables_device.argtypes = [i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32] + [vp] * 9
+    L.orbl_update_map_points_on_tables_workspace.argtypes = [i32, i32, C.POINTER(sz)]
     L.orbl_correct_loop.argtypes = [i32, vp, vp, i32, vp, vp, vp, vp, vp, i32] + [vp] * 8 + [i32] + [vp] * 7
     L.orbl_correct_loop_device.argtypes = [i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32] + [vp] * 5 + [i32] + [vp] * 10
     L.orbl_correct_loop_workspace.argtypes = [i32, i32, i32, C.POINTER(sz)]

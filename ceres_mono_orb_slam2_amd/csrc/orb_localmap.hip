@@ -396,6 +396,8 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_badflag.inc"
 // An ordered list of map-point edits (AddObservation, Replace, SetBadFlag, Fuse) and the rebuild of the observation tables (orbl_apply_map_edits*)
 #include "orb_mapedit.inc"
+// LocalMapping::SearchInNeighbors on the resident tables: targets, FUSE rows, candidates, the point update (orbl_fuse_targets*, orbl_fuse_rows*, ...)
+#include "orb_searchneighbors.inc"
 // LoopClosing::CorrectLoop's pose / point correction and the global-BA write-back (orbl_correct_loop*, orbl_propagate_global_ba*)
 #include "orb_mapcorrect.inc"
 // CeresOptimizer::LocalBundleAdjustment's problem from the map tables and its write-back (orbl_local_ba_assemble*, orbl_local_ba_apply*)

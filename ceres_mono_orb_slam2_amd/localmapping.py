@@ -805,3 +805,264 @@ def local_bundle_adjustment_on_tables(cur_kf, nbr_kf, tab, stop_flag=None, norma
     else:
         applied = local_ba_apply(asm, poses7, pts3, erase, tab, normals=normals, out=out)
     return dict(aborted=0, assembled=asm, solved=(poses7, pts3, erase), applied=applied, summaries=(s1, s2))
+
+
+# ---- LocalMapping::SearchInNeighbors on the resident tables (include/orbslam_hip.h: orbl_fuse_targets*, orbl_fuse_rows*, orbl_fuse_candidates*,
+# orbl_update_map_points_on_tables*)
+SN_OFFSETS, SN_KF, SN_PT, SN_LEVEL, SN_CAP, SN_SLOT = 1, 2, 4, 8, 16, 32         # *d_status bits of the device forms
+LOG_SCALE_FACTOR = 0.18232159316539764                                          # log_scale_factor_ = logf(1.2f), the float 0x1.756506p-3 (numpy's log is one ulp off)
+
+_SN_TAB = (("kf_bad", np.uint8), ("kf_rank", np.int32), ("kf_Tcw", np.float64), ("kf_center", np.float64), ("kf_K4", np.float32), ("kf_bounds", np.float32),
+           ("kf_slot_off", np.int32), ("kf_slot_pt", np.int32), ("kf_slot_uv", np.float32), ("kf_slot_level", np.int32), ("kf_slot_desc", np.uint8), ("X", np.float64),
+           ("pt_normal", np.float64), ("pt_min_dist", np.float32), ("pt_max_dist", np.float32), ("pt_desc", np.uint8), ("pt_bad", np.uint8), ("pt_nobs", np.int32),
+           ("pt_found", np.int32), ("pt_visible", np.int32), ("pt_replaced", np.int32), ("pt_ref_kf", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32),
+           ("obs_slot", np.int32), ("ord_off", np.int32), ("ord_kf", np.int32), ("conn_off", np.int32), ("conn_kf", np.int32), ("conn_w", np.int32),
+           ("kf_fuse_target", np.int32), ("pt_fuse_cand", np.int32), ("scale_factors", np.float32), ("inv_level_sigma2", np.float32))
+_SN_ROWS = ("op_kind", "op_pt", "op_arg", "op_kf", "op_slot", "best_idx", "best_dist", "q_uv", "q_level")
+
+
+def _sn_p(t):
+    """numpy array or torch tensor -> void*; None and empty ones -> NULL"""
+    if t is None:
+        return None
+    if hasattr(t, "data_ptr"):
+        return C.c_void_p(t.data_ptr()) if t.numel() else None
+    return _addr(t) if t.size else None
+
+
+def _sn_host(tab, keys):
+    dt = dict(_SN_TAB)
+    return {k: (None if tab.get(k) is None else _c(tab[k], dt[k]).reshape(-1)) for k in keys}
+
+
+def _sn_dev_out(o, sizes, dev):
+    import torch
+    tdt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
+    for k, dt, n in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=tdt[dt], device=dev)[:n]
+        assert o[k].dtype == tdt[dt] and o[k].is_contiguous() and o[k].numel() == n, k
+    return o
+
+
+def _sn_stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def fuse_targets(cur_kf, cur_id, tab, nn=20, nn2=5, cap_tgt=None, device=False, out=None):
+    """The target keyframes of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:400-431; orbl_fuse_targets, include/orbslam_hip.h states
+    the semantics).  tab: kf_bad (may be None), ord_off, ord_kf, kf_fuse_target.  cap_tgt: default nn (1 + nn2), which no call exceeds.
+    Host form: returns dict(tgt_kf trimmed, counts[2], kf_fuse_target = a new copy of the stamps).  device=True: torch CUDA tensors, the
+    stamps change IN PLACE, enqueued on the current stream, nothing synchronised; tgt_kf comes at full capacity with counts and status."""
+    L = _lib.load()
+    cap = nn * (1 + nn2) if cap_tgt is None else int(cap_tgt)
+    if device:
+        dev = tab["ord_off"].device
+        o = _sn_dev_out({} if out is None else out, (("tgt_kf", np.int32, cap), ("counts", np.int32, 2), ("status", np.int32, 1)), dev)
+        _lib.check(L.orbl_fuse_targets_device(int(cur_kf), int(cur_id), tab["ord_off"].numel() - 1, _sn_p(tab.get("kf_bad")), tab["ord_kf"].numel(),
+                                              C.c_void_p(tab["ord_off"].data_ptr()), _sn_p(tab["ord_kf"]), C.c_void_p(tab["kf_fuse_target"].data_ptr()), int(nn), int(nn2),
+                                              cap, _sn_p(o["tgt_kf"]), _sn_p(o["counts"]), _sn_p(o["status"]), None, _sn_stream()), "orbl_fuse_targets_device")
+        return dict(o, kf_fuse_target=tab["kf_fuse_target"])
+    t = _sn_host(tab, ("kf_bad", "ord_off", "ord_kf"))
+    stamp = np.array(tab["kf_fuse_target"], np.int32).reshape(-1)
+    tgt, counts = np.zeros(max(cap, 1), np.int32), np.zeros(2, np.int32)
+    _lib.check(L.orbl_fuse_targets(int(cur_kf), int(cur_id), len(t["ord_off"]) - 1, _sn_p(t["kf_bad"]), _addr(t["ord_off"]), _sn_p(t["ord_kf"]), _addr(stamp), int(nn),
+                                   int(nn2), cap, _addr(tgt) if cap else None, _addr(counts)), "orbl_fuse_targets")
+    return dict(tgt_kf=tgt[:counts[0]], counts=counts, kf_fuse_target=stamp)
+
+
+_SN_ROW_KF = ("kf_Tcw", "kf_center", "kf_K4", "kf_bounds", "kf_slot_off")
+_SN_ROW_SLOT = ("kf_slot_uv", "kf_slot_level", "kf_slot_desc")
+_SN_ROW_PT = ("X", "pt_normal", "pt_min_dist", "pt_max_dist", "pt_desc", "scale_factors", "inv_level_sigma2")
+
+
+def fuse_rows(kf, pts, tab, th=3.0, log_scale_factor=None, device=False, out=None, extras=True):
+    """The search of ORBmatcher::Fuse(pKF, vpMapPoints, th) for one keyframe and a list of points, as edit rows for apply_map_edits
+    (orbl_fuse_rows; include/orbslam_hip.h states the arithmetic and the row layout).  pts[n], -1 = null.  tab: kf_Tcw [nkf, 12], kf_center
+    [nkf, 3], kf_K4 [nkf, 4] and kf_bounds [nkf, 4] (float32), kf_slot_off, kf_slot_uv [nslots, 2], kf_slot_level, kf_slot_desc [nslots, 32],
+    X [npts, 3], pt_normal, pt_min_dist, pt_max_dist, pt_desc [npts, 32], scale_factors, inv_level_sigma2.  extras=False leaves best_idx,
+    best_dist, q_uv, q_level out.  Host form: kf an integer; returns a dict of arrays.  device=True: kf a device int32 tensor holding the
+    index (a view of a target list will do), everything a torch CUDA tensor, enqueued on the current stream, nothing synchronised."""
+    L = _lib.load()
+    lsf = LOG_SCALE_FACTOR if log_scale_factor is None else float(log_scale_factor)
+    names = _SN_ROWS if extras else _SN_ROWS[:5]
+    if device:
+        n, dev = pts.numel(), pts.device
+        o = _sn_dev_out({} if out is None else out, [(k, np.float32 if k == "q_uv" else np.int32, 2 * n if k == "q_uv" else n) for k in names] + [("status", np.int32, 1)],
+                        dev)
+        assert tab["kf_K4"].element_size() == 4 and tab["kf_bounds"].element_size() == 4, "kf_K4 and kf_bounds are float32 tables"
+        _lib.check(L.orbl_fuse_rows_device(C.c_void_p(kf.data_ptr()), n, _sn_p(pts), tab["kf_slot_off"].numel() - 1, *[_sn_p(tab[k]) for k in _SN_ROW_KF[:4]],
+                                           C.c_void_p(tab["kf_slot_off"].data_ptr()), tab["kf_slot_level"].numel(), *[_sn_p(tab[k]) for k in _SN_ROW_SLOT],
+                                           tab["pt_max_dist"].numel(), *[_sn_p(tab[k]) for k in _SN_ROW_PT], lsf, tab["scale_factors"].numel(), float(th),
+                                           *[_sn_p(o.get(k)) for k in _SN_ROWS], _sn_p(o["status"]), None, _sn_stream()), "orbl_fuse_rows_device")
+        return o
+    t = _sn_host(tab, _SN_ROW_KF + _SN_ROW_SLOT + _SN_ROW_PT)
+    pl = _c(pts, np.int32).reshape(-1)
+    n = len(pl)
+    o = {k: np.zeros(2 * n if k == "q_uv" else n, np.float32 if k == "q_uv" else np.int32) for k in names}
+    _lib.check(L.orbl_fuse_rows(int(kf), n, _sn_p(pl), len(t["kf_slot_off"]) - 1, *[_sn_p(t[k]) for k in _SN_ROW_KF[:4]], _addr(t["kf_slot_off"]),
+                                *[_sn_p(t[k]) for k in _SN_ROW_SLOT], len(t["pt_max_dist"]), *[_sn_p(t[k]) for k in _SN_ROW_PT], lsf, len(t["scale_factors"]), float(th),
+                                *[_sn_p(o.get(k)) for k in _SN_ROWS]), "orbl_fuse_rows")
+    if extras:
+        o["q_uv"] = o["q_uv"].reshape(-1, 2)
+    return o
+
+
+def fuse_candidates(tgt_kf, cur_id, tab, cap_cand=None, device=False, out=None, workspace=None):
+    """The candidates of SearchInNeighbors' second direction (src/LocalMapping.cc:445-470; orbl_fuse_candidates): the first occurrence of
+    every point of the listed targets that is not null, not bad and not stamped cur_id, in the reference's order.  tab: kf_slot_off,
+    kf_slot_pt, pt_bad, pt_fuse_cand.  cap_cand: default npts, which no call exceeds.  Host form: returns dict(cand_pt trimmed, counts[2],
+    pt_fuse_cand = a new copy of the stamps).  device=True: torch CUDA tensors (tgt_kf trimmed to the targets: its count is a host
+    integer), the stamps change IN PLACE, enqueued on the current stream, nothing synchronised; cand_pt comes at full capacity."""
+    L = _lib.load()
+    if device:
+        import torch
+        dev = tab["kf_slot_off"].device
+        n_tgt, nkf, nslots, npts = tgt_kf.numel(), tab["kf_slot_off"].numel() - 1, tab["kf_slot_pt"].numel(), tab["pt_bad"].numel()
+        cap = npts if cap_cand is None else int(cap_cand)
+        nbytes = C.c_size_t(0)
+        _lib.check(L.orbl_fuse_candidates_workspace(n_tgt, npts, C.byref(nbytes)), "orbl_fuse_candidates_workspace")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
+        assert ws.numel() >= nbytes.value
+        o = _sn_dev_out({} if out is None else out, (("cand_pt", np.int32, cap), ("counts", np.int32, 2), ("status", np.int32, 1)), dev)
+        _lib.check(L.orbl_fuse_candidates_device(n_tgt, _sn_p(tgt_kf), nkf, C.c_void_p(tab["kf_slot_off"].data_ptr()), nslots, _sn_p(tab["kf_slot_pt"]), npts,
+                                                 _sn_p(tab["pt_bad"]), _sn_p(tab["pt_fuse_cand"]), int(cur_id), cap, _sn_p(o["cand_pt"]), _sn_p(o["counts"]),
+                                                 _sn_p(o["status"]), C.c_void_p(ws.data_ptr()), _sn_stream()), "orbl_fuse_candidates_device")
+        return dict(o, pt_fuse_cand=tab["pt_fuse_cand"], _workspace=ws)
+    t = _sn_host(tab, ("kf_slot_off", "kf_slot_pt", "pt_bad"))
+    tg = _c(tgt_kf, np.int32).reshape(-1)
+    stamp = np.array(tab["pt_fuse_cand"], np.int32).reshape(-1)
+    npts = len(t["pt_bad"])
+    cap = npts if cap_cand is None else int(cap_cand)
+    cand, counts = np.zeros(max(cap, 1), np.int32), np.zeros(2, np.int32)
+    _lib.check(L.orbl_fuse_candidates(len(tg), _sn_p(tg), len(t["kf_slot_off"]) - 1, _addr(t["kf_slot_off"]), _sn_p(t["kf_slot_pt"]), npts, _sn_p(t["pt_bad"]),
+                                      _sn_p(stamp), int(cur_id), cap, _addr(cand) if cap else None, _addr(counts)), "orbl_fuse_candidates")
+    return dict(cand_pt=cand[:counts[0]], counts=counts, pt_fuse_cand=stamp)
+
+
+_SN_UPD_IN = ("kf_bad", "kf_center", "kf_slot_off", "kf_slot_pt", "kf_slot_level", "kf_slot_desc", "pt_bad", "X", "pt_ref_kf", "obs_off", "obs_kf", "obs_slot",
+              "scale_factors")
+_SN_UPD_INOUT = ("pt_desc", "pt_normal", "pt_min_dist", "pt_max_dist")
+
+
+def update_map_points_on_tables(what, tab, pt_mask=None, mask_kf=-1, device=False, out=None, workspace=None):
+    """MapPoint::ComputeDistinctiveDescriptors and / or UpdateNormalAndDepth (what = MP_DESC, MP_NORMAL_DEPTH or both) for the points that
+    pt_mask[npts] and / or the non-null slots of keyframe mask_kf select, read from the tables (orbl_update_map_points_on_tables).  tab:
+    kf_bad (may be None), kf_center, kf_slot_off, kf_slot_pt, kf_slot_level, kf_slot_desc, pt_bad, X, pt_ref_kf, obs_off, obs_kf, obs_slot,
+    scale_factors and the tables it rewrites: pt_desc, pt_normal, pt_min_dist, pt_max_dist.  Host form: those four come back as new copies
+    with best_obs and nd_written.  device=True: torch CUDA tensors, the four tables change IN PLACE, enqueued on the current stream,
+    nothing synchronised; returns best_obs, nd_written, status and the workspace."""
+    L = _lib.load()
+    desc, nd = bool(what & MP_DESC), bool(what & MP_NORMAL_DEPTH)
+    if device:
+        import torch
+        g = tab.get
+        dev = tab["obs_off"].device
+        nkf, nslots, npts, nobs = tab["kf_slot_off"].numel() - 1, tab["kf_slot_desc"].numel() // 32, tab["pt_bad"].numel(), tab["obs_kf"].numel()
+        nbytes = C.c_size_t(0)
+        _lib.check(L.orbl_update_map_points_on_tables_workspace(npts, nobs, C.byref(nbytes)), "orbl_update_map_points_on_tables_workspace")
+        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
+        assert ws.numel() >= nbytes.value
+        o = _sn_dev_out({} if out is None else out, (("best_obs", np.int32, npts), ("nd_written", np.uint8, npts), ("status", np.int32, 1)), dev)
+        sf = g("scale_factors")
+        _lib.check(L.orbl_update_map_points_on_tables_device(int(what), _sn_p(pt_mask), int(mask_kf), nkf, _sn_p(g("kf_bad")), _sn_p(g("kf_center")),
+                                                             C.c_void_p(tab["kf_slot_off"].data_ptr()), nslots, _sn_p(g("kf_slot_pt")), _sn_p(g("kf_slot_level")),
+                                                             _sn_p(tab["kf_slot_desc"]), npts, _sn_p(tab["pt_bad"]), _sn_p(g("X")), _sn_p(g("pt_ref_kf")), nobs,
+                                                             C.c_void_p(tab["obs_off"].data_ptr()), _sn_p(tab["obs_kf"]), _sn_p(tab["obs_slot"]), _sn_p(sf),
+                                                             sf.numel() if sf is not None else 0, *[_sn_p(g(k)) for k in _SN_UPD_INOUT], _sn_p(o["best_obs"]),
+                                                             _sn_p(o["nd_written"]), _sn_p(o["status"]), C.c_void_p(ws.data_ptr()), _sn_stream()),
+                   "orbl_update_map_points_on_tables_device")
+        return dict(o, _workspace=ws, **{k: g(k) for k in _SN_UPD_INOUT})
+    t = _sn_host(tab, _SN_UPD_IN)
+    dt = dict(_SN_TAB)
+    io = {k: (None if tab.get(k) is None else np.array(tab[k], dt[k]).reshape(-1)) for k in _SN_UPD_INOUT}                     # (always copies)
+    npts = len(t["pt_bad"])
+    pm = None if pt_mask is None else _c(pt_mask, np.uint8).reshape(-1)
+    assert pm is None or len(pm) == npts
+    best, wrote = np.full(npts, -1, np.int32), np.zeros(npts, np.uint8)
+    sf = t["scale_factors"]
+    _lib.check(L.orbl_update_map_points_on_tables(int(what), _sn_p(pm), int(mask_kf), len(t["kf_slot_off"]) - 1, _sn_p(t["kf_bad"]), _sn_p(t["kf_center"]),
+                                                  _addr(t["kf_slot_off"]), _sn_p(t["kf_slot_pt"]), _sn_p(t["kf_slot_level"]), _sn_p(t["kf_slot_desc"]), npts,
+                                                  _sn_p(t["pt_bad"]), _sn_p(t["X"]), _sn_p(t["pt_ref_kf"]), _addr(t["obs_off"]), _sn_p(t["obs_kf"]), _sn_p(t["obs_slot"]),
+                                                  _sn_p(sf), len(sf) if sf is not None else 0, *[_sn_p(io[k]) for k in _SN_UPD_INOUT], _sn_p(best) if desc else None,
+                                                  _sn_p(wrote) if nd else None), "orbl_update_map_points_on_tables")
+    r = dict(io, best_obs=best, nd_written=wrote)
+    if r["pt_desc"] is not None:
+        r["pt_desc"] = r["pt_desc"].reshape(-1, 32)
+    if r["pt_normal"] is not None:
+        r["pt_normal"] = r["pt_normal"].reshape(-1, 3)
+    return r
+
+
+def search_in_neighbors_on_tables(cur_kf, cur_id, tab, device=True, nn=20, nn2=5, th=3.0, log_scale_factor=None, conn_th=15):
+    """LocalMapping::SearchInNeighbors (src/LocalMapping.cc:398-488) on the resident map tables, with the reference's sequential semantics:
+      1. fuse_targets; n_tgt is read back.
+      2. a snapshot of the current keyframe's slot row (map_point_matches is taken once, :435, and the row changes during the loop).
+      3. per target, in list order: fuse_rows for the snapshot -> apply_map_edits_device -> update_map_points_on_tables(MP_DESC, pt_touched);
+         the 32 bytes of counts are read back for the next call's nobs, and the observation tables are swapped for the rebuilt ones.
+      4. fuse_candidates; the count is read back.
+      5. fuse_rows for the current keyframe over the candidates -> apply_map_edits_device.
+      6. the descriptors of the touched points.
+      7. update_map_points_on_tables(MP_DESC | MP_NORMAL_DEPTH, the non-null slots of cur_kf) (:474-485).
+      8. update_connections_device for the one keyframe (:487).
+    Those count read-backs - one per target keyframe plus three - are the ONLY host reads before the end; no table crosses to the host.
+    tab: a dict of torch CUDA tensors that is changed IN PLACE - every table named in fuse_targets, fuse_rows, fuse_candidates,
+    update_map_points_on_tables and apply_map_edits_device (kf_rank, pt_found / pt_visible, pt_replaced may be None), plus conn_off,
+    conn_kf, conn_w for update_connections_device; kf_K4 may be the float64 table of the BA builders (it is narrowed once).  The entries
+    obs_off, obs_kf, obs_slot are REPLACED by the rebuilt tables.  device=False: the tables are numpy arrays; they are uploaded, the same
+    chain runs, and a dict of new numpy tables comes back (a GPU is needed either way).
+    Returns dict(tab, tgt_kf (host list), n_fused: the reference's return value of every Fuse call - one per target, then the current
+    keyframe's -, cand_pt (host array), connections = what update_connections_device returned (its own status word included), status = the
+    OR of the status words of every other call: 0 unless some table entry was out of range)."""
+    import torch
+    if not device:
+        dt = dict(_SN_TAB)
+        up = {k: (None if v is None else (torch.as_tensor(_c(v, dt[k])).cuda() if k in dt else v)) for k, v in tab.items()}
+        r = search_in_neighbors_on_tables(cur_kf, cur_id, up, True, nn, nn2, th, log_scale_factor, conn_th)
+        torch.cuda.synchronize()
+        r["tab"] = {k: (v.cpu().numpy() if hasattr(v, "data_ptr") else v) for k, v in r["tab"].items()}
+        r["connections"] = {k: (v.cpu().numpy() if hasattr(v, "data_ptr") else v) for k, v in r["connections"].items() if k != "_workspace"}
+        return r
+    t = dict(tab)
+    if t["kf_K4"].dtype != torch.float32:
+        t["kf_K4"] = t["kf_K4"].to(torch.float32)
+    dev = t["obs_off"].device
+    statuses, n_fused, keep = [], [], []
+    tg = fuse_targets(cur_kf, cur_id, t, nn, nn2, device=True)
+    statuses.append(tg["status"])
+    n_tgt = int(tg["counts"][:1].cpu()[0])                             # host read 1
+    lo, hi = (int(v) for v in t["kf_slot_off"][int(cur_kf):int(cur_kf) + 2].cpu())       # (the offsets are static: read once, with n_tgt)
+    snapshot = t["kf_slot_pt"][lo:hi].clone()
+
+    def fuse(kf_word, pts):
+        rows = fuse_rows(kf_word, pts, t, th, log_scale_factor, device=True, extras=False)
+        ed = apply_map_edits_device(rows, dict(t, kf_slot_level=None, kf_slot_uv=None))          # (no oobs_level / oobs_uv: nothing here reads them)
+        t["obs_off"], full = ed.oobs_off, (ed.oobs_kf, ed.oobs_slot)
+        c = ed.counts.cpu()                                            # the 32 bytes of counts: the next call's nobs
+        n = int(c[0])
+        t["obs_kf"], t["obs_slot"] = full[0][:n], full[1][:n]
+        up = update_map_points_on_tables(MP_DESC, t, pt_mask=ed.pt_touched, device=True)
+        statuses.extend((rows["status"], ed.status, up["status"]))
+        keep.extend((rows, ed, up))
+        n_fused.append(int(c[4]))
+
+    for i in range(n_tgt):
+        fuse(tg["tgt_kf"][i:i + 1], snapshot)
+    cd = fuse_candidates(tg["tgt_kf"][:n_tgt], cur_id, t, device=True)
+    statuses.append(cd["status"])
+    n_cand = int(cd["counts"][:1].cpu()[0])
+    cur_word = torch.tensor([int(cur_kf)], dtype=torch.int32, device=dev)
+    fuse(cur_word, cd["cand_pt"][:n_cand])
+    up = update_map_points_on_tables(MP_DESC | MP_NORMAL_DEPTH, t, mask_kf=int(cur_kf), device=True)
+    statuses.append(up["status"])
+    row_off = torch.tensor([0, hi - lo], dtype=torch.int32, device=dev)              # (update_connections takes the slot rows of its targets only)
+    conn = update_connections_device(cur_word, row_off, t["kf_slot_pt"][lo:hi], t["kf_slot_off"].numel() - 1, t["obs_off"], t["obs_kf"], t["conn_off"], t["conn_kf"],
+                                     t["conn_w"], pt_bad=t["pt_bad"], kf_rank=t.get("kf_rank"), th=conn_th)
+    status = 0
+    for s in torch.stack([s.reshape(-1)[0] for s in statuses]).cpu().tolist():
+        status |= int(s) & 0xFFFFFFFF
+    for k in ("obs_off", "obs_kf", "obs_slot"):
+        tab[k] = t[k]
+    return dict(tab=tab, tgt_kf=tg["tgt_kf"][:n_tgt].cpu().tolist(), n_fused=n_fused, cand_pt=cd["cand_pt"][:n_cand].cpu().numpy(), connections=conn, status=status,
+                _keep=(keep, up, cd, tg, snapshot, cur_word, row_off))

@@ -843,6 +843,117 @@ int orbl_apply_map_edits_device(int nops, const int32_t* d_op_kind, const int32_
  * + 2 R(4 npts) + R(4 (blocks + 1)) + R(4 ents) the new list lengths and their scan, the workgroup sums, the gathered entries         */
 int orbl_apply_map_edits_workspace(int nops, int nkf, int npts, int nslots, int nobs, size_t* bytes);
 
+/* ---- LocalMapping::SearchInNeighbors on the resident tables (src/LocalMapping.cc:398-488): the four pieces a caller whose map tables
+ * stay on the device lacked between orbl_apply_map_edits and orbl_update_map_points.  The exact loop is, per target keyframe in list
+ * order: orbl_fuse_rows_device (the descriptors as they stand) -> orbl_apply_map_edits_device (the FUSE op tests the bad flags,
+ * IsInKeyFrame, Observations() and the slots at each row's own turn) -> orbl_update_map_points_on_tables_device(ORBL_MP_DESC,
+ * pt_touched).  Inside ONE keyframe's Fuse every search uses the descriptors held at entry (n_late_adds == 0 above), and across
+ * keyframes nothing else the projection reads changes: Replace and AddObservation leave position, normal and the depth range alone.
+ * The points of the first loop are a snapshot of the current keyframe's slot row taken BEFORE the loop (:435).  INTEGRATION.md section 4
+ * has the call sequence.  Each entry has a host form (host pointers, synchronous, one packed upload and one download; ORBHIP_EINVAL
+ * before any device work, ORBHIP_ENODEV without a GPU: no CPU fallback), a _device form (device pointers, enqueued on `stream`: no
+ * synchronisation, no allocation, no host read of the data; counts, NULL pointers and alignment checked on the host, the data
+ * bounds-checked on the device - an entry out of range counts as absent and raises a bit of *d_status, nullable and zeroed first:
+ * 1 = offsets, 2 = a keyframe out of range, 4 = a point out of range, 8 = a level out of range, 16 = a capacity exceeded, 32 = a slot
+ * its keyframe does not have) and a _workspace form (host arithmetic; R(x) = x rounded up to a multiple of 256).                      */
+
+/* The target keyframes (:400-431).  kf_bad[nkf] (nullable = none); every keyframe's ordered_connected_keyframes_ as ord_off[nkf + 1] /
+ * ord_kf[]; kf_fuse_target[nkf] (IN/OUT), the fuse_target_for_keyframe_ stamps.  Literally: for each of the first nn entries n of
+ * cur_kf's list, in order: skipped when kf_bad[n] or kf_fuse_target[n] == cur_id; otherwise n is pushed and stamped, and each of the
+ * first nn2 entries k2 of n's list is pushed WITHOUT a stamp unless kf_bad[k2], kf_fuse_target[k2] == cur_id or k2 == cur_kf.  The list
+ * therefore names a keyframe twice when a second neighbour is reached twice or is itself a later first neighbour, as the reference's
+ * does.  The reference calls it with nn = 20, nn2 = 5; at most nn (1 + nn2) entries result.  tgt_kf[cap_tgt]; counts[2] = {the wanted
+ * number of targets, the first neighbours among them}.  Host form: cur_kf and every ord_kf entry must be a keyframe (EINVAL);
+ * ORBHIP_ECAP with only counts[] written when cap_tgt is too small.  Device form: an entry that is no keyframe is skipped (bit 2),
+ * nothing is written beyond cap_tgt (bit 16).  One wave; the workspace is 0 bytes and may be NULL.                                    */
+int orbl_fuse_targets(int cur_kf, int cur_id, int nkf, const uint8_t* kf_bad, const int32_t* ord_off, const int32_t* ord_kf, int32_t* kf_fuse_target, int nn, int nn2,
+                      int cap_tgt, int32_t* tgt_kf, int32_t* counts);
+int orbl_fuse_targets_device(int cur_kf, int cur_id, int nkf, const uint8_t* d_kf_bad, int nord, const int32_t* d_ord_off, const int32_t* d_ord_kf,
+                             int32_t* d_kf_fuse_target, int nn, int nn2, int cap_tgt, int32_t* d_tgt_kf, int32_t* d_counts, uint32_t* d_status, void* d_workspace,
+                             void* stream);
+int orbl_fuse_targets_workspace(int nkf, size_t* bytes);
+
+/* The search of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:739-824) for ONE keyframe and a list of points, everything
+ * read from the tables, edit rows out.  The device form names the keyframe by a device pointer d_kf to its index, so a chain walks
+ * d_tgt_kf + t without a host copy of the target list.  pts[n], -1 = null.
+ *   Keyframe tables: kf_Tcw[nkf][12], kf_center[nkf][3] (double); kf_K4[nkf][4] {fx, fy, cx, cy} and kf_bounds[nkf][4] {min_x_, max_x_,
+ *   min_y_, max_y_} (float); kf_slot_off[nkf + 1]; kf_slot_uv[nslots][2] (float, the undistorted keypoints), kf_slot_level[nslots],
+ *   kf_slot_desc[nslots][32], the keyframe's descriptor rows.
+ *   Point tables: pt_Xw[npts][3], pt_normal[npts][3] (double); pt_min_dist[npts], pt_max_dist[npts] (float, raw: the 0.8 / 1.2 factors of
+ *   Get{Min,Max}DistanceInvariance are applied inside); pt_desc[npts][32].
+ *   scale_factors[n_levels], inv_level_sigma2[n_levels], log_scale_factor, th (the reference's default: 3.0).
+ * The arithmetic is the reference's float / double mix: p3Dc = Rcw p + tcw in double, each row (r0 x + r1 y) + r2 z, then + t; p3Dc[2]
+ * < 0 rejects; invz = (float)(1 / z), x = (float)(p3Dc[0] invz), u = fx x + cx in float; IsInImage is u >= min_x && u < max_x && v >=
+ * min_y && v < max_y; dist3D = (float)|PO| with PO = p - Ow; dist3D < 0.8f min or > 1.2f max rejects; PO.Pn < 0.5 dist3D in double
+ * rejects; level = ceilf(logf(max / dist3D) / log_scale_factor) clamped to [0, n_levels - 1].  Then KeyFrame::GetFeaturesInArea(u, v,
+ * th scale_factors[level]) (src/KeyFrame.cc:575-622), the level window [level - 1, level] and e2 inv_level_sigma2[lvl] > 5.99.  The
+ * least Hamming distance wins, the FIRST of equal ones in GetFeaturesInArea's output order: cells ix-major then iy, index order inside
+ * a cell.  DEPARTURE in form only: no grid table is read - a keypoint's own cell is Frame::PosInGrid (src/Frame.cc:309-320) of its
+ * position, which is how the reference's grid was filled, so the candidate list and its order are the same by construction.
+ * Row i, in orbl_apply_map_edits' layout: NOP (kind 0, op_pt = the point or -1, op_arg 0, op_kf = the keyframe, op_slot -1) for a
+ * null point, a failed gate, no candidate or a best distance > TH_LOW (50); otherwise FUSE (kind 4, op_pt, op_arg 0, op_kf, op_slot =
+ * the best keypoint) - whatever the point's bad flag or IsInKeyFrame is: the replay's skip test decides that at the right moment.
+ * Nullable outputs: best_idx[n] (-1 = none), best_dist[n] (256 = none), q_uv[n][2] and q_level[n] (-1 = a gate failed; then q_uv = 0):
+ * what orbl_fuse_batch takes and returns.  Every element is written; the outputs are the same bytes on every run.
+ * Host form: kf must be a keyframe, pts entries points or -1, the keyframe's kf_slot_level entries levels (EINVAL).  Device form: a
+ * point out of range is a NOP (bit 4), a keyframe out of range makes every row a NOP (bit 2), a keypoint with a negative level that the
+ * window would admit is skipped (bit 8).  Descriptor tables 4-byte aligned.  One wave per point; the workspace is 0 bytes, may be NULL. */
+int orbl_fuse_rows(int kf, int n, const int32_t* pts, int nkf, const double* kf_Tcw, const double* kf_center, const float* kf_K4, const float* kf_bounds,
+                   const int32_t* kf_slot_off, const float* kf_slot_uv, const int32_t* kf_slot_level, const uint8_t* kf_slot_desc, int npts, const double* pt_Xw,
+                   const double* pt_normal, const float* pt_min_dist, const float* pt_max_dist, const uint8_t* pt_desc, const float* scale_factors,
+                   const float* inv_level_sigma2, float log_scale_factor, int n_levels, float th, int32_t* op_kind, int32_t* op_pt, int32_t* op_arg, int32_t* op_kf,
+                   int32_t* op_slot, int32_t* best_idx, int32_t* best_dist, float* q_uv, int32_t* q_level);
+int orbl_fuse_rows_device(const int32_t* d_kf, int n, const int32_t* d_pts, int nkf, const double* d_kf_Tcw, const double* d_kf_center, const float* d_kf_K4,
+                          const float* d_kf_bounds, const int32_t* d_kf_slot_off, int nslots, const float* d_kf_slot_uv, const int32_t* d_kf_slot_level,
+                          const uint8_t* d_kf_slot_desc, int npts, const double* d_pt_Xw, const double* d_pt_normal, const float* d_pt_min_dist,
+                          const float* d_pt_max_dist, const uint8_t* d_pt_desc, const float* d_scale_factors, const float* d_inv_level_sigma2, float log_scale_factor,
+                          int n_levels, float th, int32_t* d_op_kind, int32_t* d_op_pt, int32_t* d_op_arg, int32_t* d_op_kf, int32_t* d_op_slot, int32_t* d_best_idx,
+                          int32_t* d_best_dist, float* d_q_uv, int32_t* d_q_level, uint32_t* d_status, void* d_workspace, void* stream);
+int orbl_fuse_rows_workspace(int n, size_t* bytes);
+
+/* The candidates of the second direction (:445-470): tgt_kf[n_tgt], the target list with its duplicates; kf_slot_off / kf_slot_pt;
+ * pt_bad[npts]; pt_fuse_cand[npts] (IN/OUT), the fuse_candidate_for_keyframe stamps.  cand_pt[cap_cand] = the first occurrence of every
+ * point that is non-null, not bad and not stamped cur_id at entry, the targets walked in list order and a target's slots in slot
+ * order; every emitted point ends stamped.  counts[2] = {the wanted number of candidates, n_tgt}.  No atomic decides a position (a
+ * minimum of (list position, slot) per point, then ordered scans): the outputs are the same bytes on every run.  Host form: EINVAL for
+ * a target that is no keyframe or a slot holding neither a point nor -1; ORBHIP_ECAP with only counts[] written when cap_cand is too
+ * small.  Device form: such targets and slots are skipped (bits 2, 4); nothing is written beyond cap_cand (bit 16) and the points
+ * beyond it stay unstamped.  n_tgt <= 2^24.  Workspace, 8-byte aligned: R(8 npts) + R(4 (n_tgt + 1)).                                 */
+int orbl_fuse_candidates(int n_tgt, const int32_t* tgt_kf, int nkf, const int32_t* kf_slot_off, const int32_t* kf_slot_pt, int npts, const uint8_t* pt_bad,
+                         int32_t* pt_fuse_cand, int cur_id, int cap_cand, int32_t* cand_pt, int32_t* counts);
+int orbl_fuse_candidates_device(int n_tgt, const int32_t* d_tgt_kf, int nkf, const int32_t* d_kf_slot_off, int nslots, const int32_t* d_kf_slot_pt, int npts,
+                                const uint8_t* d_pt_bad, int32_t* d_pt_fuse_cand, int cur_id, int cap_cand, int32_t* d_cand_pt, int32_t* d_counts, uint32_t* d_status,
+                                void* d_workspace, void* stream);
+int orbl_fuse_candidates_workspace(int n_tgt, int npts, size_t* bytes);
+
+/* MapPoint::ComputeDistinctiveDescriptors and / or UpdateNormalAndDepth (`what` as in orbl_update_map_points) for the points a mask
+ * selects, read straight from the tables and written IN PLACE.  The selection: pt_mask[npts] (nullable; orbl_apply_map_edits'
+ * pt_touched) and / or the non-null slots of keyframe mask_kf (-1 = none; :474-485) - at least one of the two.  What
+ * orbl_update_map_points takes per observation is gathered first: the descriptor of observation e from kf_slot_desc through (obs_kf,
+ * obs_slot), obs_kf_good from kf_bad (nullable = none), and per point the reference level - the kf_slot_level of the observation in
+ * pt_ref_kf[p], or of that keyframe's keypoint 0 when the list does not name it (the rule stated above).  The rest is
+ * orbl_update_map_points' own kernels, so the results are bit-identical to that entry on the same lists: pt_desc[npts][32],
+ * pt_normal[npts][3], pt_min_dist[npts], pt_max_dist[npts]; bad points, unselected points and empty lists are left alone.  Nullable
+ * outputs: best_obs[npts] (the list position of the chosen descriptor, -1 = unchanged; written for every point with ORBL_MP_DESC),
+ * nd_written[npts] (with ORBL_MP_NORMAL_DEPTH).  The lists must be alive and in the order the reference walks them (ascending kf_rank:
+ * the tables orbl_apply_map_edits returns).  kf_slot_desc is needed whatever `what` is; kf_center, kf_slot_level, pt_Xw, pt_ref_kf,
+ * scale_factors only for ORBL_MP_NORMAL_DEPTH; kf_slot_pt only with mask_kf.  Host form: EINVAL for an observation that names no
+ * keyframe or no slot of it, a pt_ref_kf that is neither a keyframe nor -1, a level out of range.  Device form: such an observation is
+ * absent (bits 2, 32).  Workspace, 16-byte aligned: R(npts) cleared by every call + R(npts) + 2 R(4 npts) + R(npts) + R(8 npts) +
+ * R(nobs) + R(32 nobs) + R(32 + 20 npts), the last one orbl_update_map_points' own.                                                   */
+int orbl_update_map_points_on_tables(int what, const uint8_t* pt_mask, int mask_kf, int nkf, const uint8_t* kf_bad, const double* kf_center, const int32_t* kf_slot_off,
+                                     const int32_t* kf_slot_pt, const int32_t* kf_slot_level, const uint8_t* kf_slot_desc, int npts, const uint8_t* pt_bad,
+                                     const double* pt_Xw, const int32_t* pt_ref_kf, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_slot,
+                                     const float* scale_factors, int n_levels, uint8_t* pt_desc, double* pt_normal, float* pt_min_dist, float* pt_max_dist,
+                                     int32_t* best_obs, uint8_t* nd_written);
+int orbl_update_map_points_on_tables_device(int what, const uint8_t* d_pt_mask, int mask_kf, int nkf, const uint8_t* d_kf_bad, const double* d_kf_center,
+                                            const int32_t* d_kf_slot_off, int nslots, const int32_t* d_kf_slot_pt, const int32_t* d_kf_slot_level,
+                                            const uint8_t* d_kf_slot_desc, int npts, const uint8_t* d_pt_bad, const double* d_pt_Xw, const int32_t* d_pt_ref_kf,
+                                            int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf, const int32_t* d_obs_slot, const float* d_scale_factors,
+                                            int n_levels, uint8_t* d_pt_desc, double* d_pt_normal, float* d_pt_min_dist, float* d_pt_max_dist, int32_t* d_best_obs,
+                                            uint8_t* d_nd_written, uint32_t* d_status, void* d_workspace, void* stream);
+int orbl_update_map_points_on_tables_workspace(int npts, int nobs, size_t* bytes);
+
 /* ---- LoopClosing::CorrectLoop, the part that moves the map (src/LoopClosing.cc:437-523): the corrected and non-corrected Sim3 of the
  * current keyframe's covisibility group, the correction of every map point those keyframes hold, UpdateNormalAndDepth of each moved
  * point, SetPose([R | t/s]) of each keyframe - with the exact semantics of the sequential loop.  Keyframes are 0..nkf-1, points 0..npts-1.
