@@ -92,18 +92,13 @@ def initialize_batch_device(kps1, off1, kps2, off2, matches12, K4, sigma, iterat
     ransac_sets[npairs, iterations, 8] int32.  out = dict of device tensors R21[npairs, 3, 3] float64, t21[npairs, 3] float64,
     P3D[n1_total, 3] float64, triangulated[n1_total] uint8, report[npairs * sizeof(orbt_init_report)] uint8, written on the
     current stream (the rows of pairs that fail stay as they were).  decode_reports() turns the report bytes into dicts."""
-    import torch
     L = _lib.load()
     npairs = off1.numel() - 1
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbt_initialize_workspace(npairs, kps1.shape[0], kps2.shape[0], int(iterations), C.byref(nbytes)), "orbt_initialize_workspace")
-    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=kps1.device)
-
-    def p(t):
-        return C.c_void_p(t.data_ptr())
+    ws = _lib.workspace("orbt_initialize_workspace", npairs, kps1.shape[0], kps2.shape[0], int(iterations), device=kps1.device, min_bytes=16)
+    p = _lib.ptr
     _lib.check(L.orbt_initialize_batch_device(npairs, p(kps1), p(off1), kps1.shape[0], p(kps2), p(off2), kps2.shape[0], p(matches12), p(K4),
                                               float(sigma), int(iterations), p(ransac_sets), p(out["R21"]), p(out["t21"]), p(out["P3D"]),
-                                              p(out["triangulated"]), p(out["report"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                              p(out["triangulated"]), p(out["report"]), p(ws), _lib.stream()),
                "orbt_initialize_batch_device")
     out["_workspace"] = ws                                       # (kept alive until the caller synchronises)
     return out

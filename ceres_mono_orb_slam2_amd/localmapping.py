@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import carray as _c, flat as _flat, ptr as _p, ptr_nonempty as _pn
 
 
 class _KF(C.Structure):              # orbl_keyframe
@@ -16,14 +17,6 @@ class _KF(C.Structure):              # orbl_keyframe
 
 class _FuseKF(C.Structure):          # orbl_fuse_keyframe
     _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("n", C.c_int), ("bounds", C.c_float * 4)]
-
-
-def _c(a, dt):
-    return np.ascontiguousarray(a, dt)
-
-
-def _addr(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def prepare_create_new_map_points(cur, neighbours, scale_factors, level_sigma2, ratio_factor, stop=None):
@@ -58,11 +51,9 @@ def prepare_create_new_map_points(cur, neighbours, scale_factors, level_sigma2, 
     st = None
     if stop is not None:
         assert stop.dtype == np.uint8 and stop.size >= 1
-        st = C.c_void_p(stop.ctypes.data)
-    L.orbl_create_new_map_points.argtypes = [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    a = (_addr(k1), _addr(d1), _addr(u1), n1, _addr(f1[0]), _addr(f1[1]), _addr(f1[2]), len(f1[0]), _addr(T1), _addr(K1), C.cast(nb, C.c_void_p), nn, _addr(sf), _addr(ls),
-         len(sf), float(ratio_factor), st, _addr(m), _addr(ok), _addr(X), C.byref(npr))
+        st = _p(stop)
+    a = (_p(k1), _p(d1), _p(u1), n1, _p(f1[0]), _p(f1[1]), _p(f1[2]), len(f1[0]), _p(T1), _p(K1), C.cast(nb, C.c_void_p), nn, _p(sf), _p(ls),
+         len(sf), float(ratio_factor), st, _p(m), _p(ok), _p(X), C.byref(npr))
 
     def call():
         _lib.check(L.orbl_create_new_map_points(*a), "orbl_create_new_map_points")
@@ -98,13 +89,11 @@ def fuse_batch(keyframes, q_uv, q_radius, q_level, mp_desc, inv_level_sigma2, si
     md = _c(mp_desc, np.uint8).reshape(M, 32)
     bi = np.full((max(T, 1), max(M, 1)), -1, np.int32); bd = np.full((max(T, 1), max(M, 1)), 256, np.int32)
     if sim3:
-        L.orbl_fuse_batch_sim3.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _lib.check(L.orbl_fuse_batch_sim3(C.cast(kf, C.c_void_p), T, _addr(uv), _addr(rad), _addr(lvl), M, _addr(md), int(n_levels), _addr(bi), _addr(bd)),
+        _lib.check(L.orbl_fuse_batch_sim3(C.cast(kf, C.c_void_p), T, _p(uv), _p(rad), _p(lvl), M, _p(md), int(n_levels), _p(bi), _p(bd)),
                    "orbl_fuse_batch_sim3")
         return bi[:T, :M], bd[:T, :M]
     ils = _c(inv_level_sigma2, np.float32)
-    L.orbl_fuse_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    _lib.check(L.orbl_fuse_batch(C.cast(kf, C.c_void_p), T, _addr(uv), _addr(rad), _addr(lvl), M, _addr(md), _addr(ils), len(ils), _addr(bi), _addr(bd)),
+    _lib.check(L.orbl_fuse_batch(C.cast(kf, C.c_void_p), T, _p(uv), _p(rad), _p(lvl), M, _p(md), _p(ils), len(ils), _p(bi), _p(bd)),
                "orbl_fuse_batch")
     return bi[:T, :M], bd[:T, :M]
 
@@ -141,11 +130,9 @@ def update_map_points(obs_off, obs_desc=None, obs_kf_good=None, X=None, ref_kf=N
     kc = _c(kf_center, np.float64).reshape(-1, 3) if kf_center is not None else None
     sf = _c(scale_factors, np.float32) if scale_factors is not None else None
     pg = _c(pt_good, np.uint8) if pt_good is not None else None
-    vp, i32 = C.c_void_p, C.c_int
-    L.orbl_update_map_points.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    _lib.check(L.orbl_update_map_points(npts, _addr(off), _addr(Xa), _addr(rk), _addr(rl), _addr(pg), nobs, _addr(ok_), _addr(desc), _addr(kg),
-                                        len(kc) if kc is not None else 0, _addr(kc), _addr(sf), len(sf) if sf is not None else 0, int(what),
-                                        _addr(o["best_obs"]), _addr(o["desc"]), _addr(o["normal"]), _addr(o["min_max"]), _addr(o["nd_written"])),
+    _lib.check(L.orbl_update_map_points(npts, _p(off), _p(Xa), _p(rk), _p(rl), _p(pg), nobs, _p(ok_), _p(desc), _p(kg),
+                                        len(kc) if kc is not None else 0, _p(kc), _p(sf), len(sf) if sf is not None else 0, int(what),
+                                        _p(o["best_obs"]), _p(o["desc"]), _p(o["normal"]), _p(o["min_max"]), _p(o["nd_written"])),
                "orbl_update_map_points")
     return o
 
@@ -153,23 +140,15 @@ def update_map_points(obs_off, obs_desc=None, obs_kf_good=None, X=None, ref_kf=N
 def update_map_points_device(obs_off, obs_desc, obs_kf_good, X, ref_kf, ref_level, obs_kf, kf_center, scale_factors, pt_good, what, out):
     """orbl_update_map_points_device on torch CUDA tensors (the same arguments as update_map_points; None where a pointer may be
     NULL); out = dict of device tensors (best_obs, desc, normal, min_max, nd_written), written on the current stream."""
-    import torch
     L = _lib.load()
     npts = obs_off.numel() - 1
     nobs = obs_desc.shape[0] if obs_desc is not None else (obs_kf.numel() if obs_kf is not None else 0)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_update_map_points_workspace(npts, C.byref(nbytes)), "orbl_update_map_points_workspace")
-    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=obs_off.device)
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-    vp, i32 = C.c_void_p, C.c_int
-    L.orbl_update_map_points_device.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    _lib.check(L.orbl_update_map_points_device(npts, p(obs_off), p(X), p(ref_kf), p(ref_level), p(pt_good), nobs, p(obs_kf), p(obs_desc), p(obs_kf_good),
-                                               kf_center.shape[0] if kf_center is not None else 0, p(kf_center), p(scale_factors),
-                                               scale_factors.numel() if scale_factors is not None else 0, int(what), p(out.get("best_obs")), p(out.get("desc")),
-                                               p(out.get("normal")), p(out.get("min_max")), p(out.get("nd_written")), p(ws),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_update_map_points_device")
+    ws = _lib.workspace("orbl_update_map_points_workspace", npts, device=obs_off.device, min_bytes=16)
+    _lib.check(L.orbl_update_map_points_device(npts, _p(obs_off), _p(X), _p(ref_kf), _p(ref_level), _p(pt_good), nobs, _p(obs_kf), _p(obs_desc), _p(obs_kf_good),
+                                               kf_center.shape[0] if kf_center is not None else 0, _p(kf_center), _p(scale_factors),
+                                               scale_factors.numel() if scale_factors is not None else 0, int(what), _p(out.get("best_obs")), _p(out.get("desc")),
+                                               _p(out.get("normal")), _p(out.get("min_max")), _p(out.get("nd_written")), _p(ws),
+                                               _lib.stream()), "orbl_update_map_points_device")
     out["_workspace"] = ws                                       # (kept alive until the caller synchronises)
     return out
 
@@ -210,9 +189,9 @@ def keyframe_culling(cand_kf, cand_flags, slot_off, slot_pt, slot_level, nkf, ob
     for k, dt, n in (("culled", np.uint8, ncand), ("n_redundant", np.int32, ncand), ("n_map_points", np.int32, ncand), ("pt_bad", np.uint8, npts),
                      ("pt_nobs", np.int32, npts), ("obs_erased", np.uint8, len(ok_))):
         assert o.get(k) is None or (o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == n), k
-    _lib.check(L.orbl_keyframe_culling(ncand, _addr(ck), _addr(cf), _addr(so), _addr(sp), _addr(sl), int(nkf), npts, _addr(oo), _addr(ok_), _addr(ol), _addr(pb),
-                                       _addr(pn), int(th_obs), float(ratio), _addr(o["culled"]), _addr(o["n_redundant"]), _addr(o["n_map_points"]),
-                                       _addr(o.get("pt_bad")), _addr(o.get("pt_nobs")), _addr(o.get("obs_erased"))), "orbl_keyframe_culling")
+    _lib.check(L.orbl_keyframe_culling(ncand, _p(ck), _p(cf), _p(so), _p(sp), _p(sl), int(nkf), npts, _p(oo), _p(ok_), _p(ol), _p(pb),
+                                       _p(pn), int(th_obs), float(ratio), _p(o["culled"]), _p(o["n_redundant"]), _p(o["n_map_points"]),
+                                       _p(o.get("pt_bad")), _p(o.get("pt_nobs")), _p(o.get("obs_erased"))), "orbl_keyframe_culling")
     return CullingResult(**o)
 
 
@@ -225,9 +204,7 @@ def keyframe_culling_device(cand_kf, cand_flags, slot_off, slot_pt, slot_level, 
     L = _lib.load()
     dev = cand_kf.device
     ncand, nslots, npts, nobs = cand_kf.numel(), slot_pt.numel(), obs_off.numel() - 1, obs_kf.numel()
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_keyframe_culling_workspace(ncand, nslots, npts, nobs, C.byref(nbytes)), "orbl_keyframe_culling_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("orbl_keyframe_culling_workspace", ncand, nslots, npts, nobs, device=dev)
     o = {} if out is None else out
     for k, dt, n in (("culled", torch.uint8, ncand), ("n_redundant", torch.int32, ncand), ("n_map_points", torch.int32, ncand)) + \
             ((("pt_bad", torch.uint8, npts), ("pt_nobs", torch.int32, npts), ("obs_erased", torch.uint8, nobs)) if final_state else ()):
@@ -235,13 +212,10 @@ def keyframe_culling_device(cand_kf, cand_flags, slot_off, slot_pt, slot_level, 
             o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
     status = torch.empty(1, dtype=torch.int32, device=dev)
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_keyframe_culling_device(ncand, p(cand_kf), p(cand_flags), nslots, p(slot_off), p(slot_pt), p(slot_level), int(nkf), npts, nobs, p(obs_off),
-                                              p(obs_kf), p(obs_level), p(pt_bad), p(pt_nobs), int(th_obs), float(ratio), p(o["culled"]), p(o["n_redundant"]),
-                                              p(o["n_map_points"]), p(o.get("pt_bad")), p(o.get("pt_nobs")), p(o.get("obs_erased")), p(status), p(ws),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_keyframe_culling_device")
+    _lib.check(L.orbl_keyframe_culling_device(ncand, _p(cand_kf), _p(cand_flags), nslots, _p(slot_off), _p(slot_pt), _p(slot_level), int(nkf), npts, nobs, _p(obs_off),
+                                              _p(obs_kf), _p(obs_level), _p(pt_bad), _p(pt_nobs), int(th_obs), float(ratio), _p(o["culled"]), _p(o["n_redundant"]),
+                                              _p(o["n_map_points"]), _p(o.get("pt_bad")), _p(o.get("pt_nobs")), _p(o.get("obs_erased")), _p(status), _p(ws),
+                                              _lib.stream()), "orbl_keyframe_culling_device")
     return CullingResult(status=status, _workspace=ws, **o)
 
 
@@ -289,10 +263,10 @@ def update_connections(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, conn_off
     for k, n in sizes.items():
         o.setdefault(k, np.zeros(n, np.int32))
         assert o[k].dtype == np.int32 and o[k].flags.c_contiguous and o[k].size == n, k
-    rc = L.orbl_update_connections(ntgt, _addr(tk), _addr(tf), _addr(so), _addr(sp), int(nkf), npts, _addr(oo), _addr(ok_), _addr(pb), _addr(kr), _addr(co), _addr(ck),
-                                   _addr(cw), _addr(po), _addr(pk), int(th), cap_aff, cap_conn, cap_ord, cap_link, _addr(o["tgt_status"]), _addr(o["tgt_parent"]),
-                                   _addr(o["aff_kf"]), _addr(o["conn_off"]), _addr(o["conn_kf"]), _addr(o["conn_w"]), _addr(o["ord_off"]), _addr(o["ord_kf"]),
-                                   _addr(o["ord_w"]), _addr(o.get("link_off")), _addr(o.get("link_kf")), _addr(o["counts"]))
+    rc = L.orbl_update_connections(ntgt, _p(tk), _p(tf), _p(so), _p(sp), int(nkf), npts, _p(oo), _p(ok_), _p(pb), _p(kr), _p(co), _p(ck),
+                                   _p(cw), _p(po), _p(pk), int(th), cap_aff, cap_conn, cap_ord, cap_link, _p(o["tgt_status"]), _p(o["tgt_parent"]),
+                                   _p(o["aff_kf"]), _p(o["conn_off"]), _p(o["conn_kf"]), _p(o["conn_w"]), _p(o["ord_off"]), _p(o["ord_kf"]),
+                                   _p(o["ord_w"]), _p(o.get("link_off")), _p(o.get("link_kf")), _p(o["counts"]))
     if rc == ECAP and not check:
         return dict(rc=rc, counts=o["counts"])
     _lib.check(rc, "orbl_update_connections")
@@ -318,10 +292,7 @@ def update_connections_device(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, c
     nprev = prev_kf.numel() if prev_kf is not None else 0
     links = prev_off is not None if links is None else links
     cap_aff, cap_conn, cap_ord, cap_link = _uc_default_caps(ntgt, int(nkf), nconn, links) if caps is None else caps
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_update_connections_workspace(ntgt, int(nkf), npts, nslots, nconn, C.byref(nbytes)), "orbl_update_connections_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_update_connections_workspace", ntgt, int(nkf), npts, nslots, nconn, device=dev, reuse=workspace)
     o = {} if out is None else out
     sizes = dict(tgt_status=ntgt, tgt_parent=ntgt, aff_kf=cap_aff, conn_off=cap_aff + 1, conn_kf=cap_conn, conn_w=cap_conn, ord_off=cap_aff + 1, ord_kf=cap_ord,
                  ord_w=cap_ord, counts=4, status=1)
@@ -331,14 +302,11 @@ def update_connections_device(tgt_kf, slot_off, slot_pt, nkf, obs_off, obs_kf, c
         if o.get(k) is None:
             o[k] = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
         assert o[k].dtype == torch.int32 and o[k].is_contiguous() and o[k].numel() == n, k
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_update_connections_device(ntgt, p(tgt_kf), p(tgt_flags), nslots, p(slot_off), p(slot_pt), int(nkf), npts, nobs, p(obs_off), p(obs_kf), p(pt_bad),
-                                                p(kf_rank), nconn, p(conn_off), p(conn_kf), p(conn_w), nprev, p(prev_off), p(prev_kf), int(th), cap_aff, cap_conn,
-                                                cap_ord, cap_link, p(o["tgt_status"]), p(o["tgt_parent"]), p(o["aff_kf"]), p(o["conn_off"]), p(o["conn_kf"]),
-                                                p(o["conn_w"]), p(o["ord_off"]), p(o["ord_kf"]), p(o["ord_w"]), p(o.get("link_off")), p(o.get("link_kf")),
-                                                p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+    _lib.check(L.orbl_update_connections_device(ntgt, _p(tgt_kf), _p(tgt_flags), nslots, _p(slot_off), _p(slot_pt), int(nkf), npts, nobs, _p(obs_off), _p(obs_kf), _p(pt_bad),
+                                                _p(kf_rank), nconn, _p(conn_off), _p(conn_kf), _p(conn_w), nprev, _p(prev_off), _p(prev_kf), int(th), cap_aff, cap_conn,
+                                                cap_ord, cap_link, _p(o["tgt_status"]), _p(o["tgt_parent"]), _p(o["aff_kf"]), _p(o["conn_off"]), _p(o["conn_kf"]),
+                                                _p(o["conn_w"]), _p(o["ord_off"]), _p(o["ord_kf"]), _p(o["ord_w"]), _p(o.get("link_off")), _p(o.get("link_kf")),
+                                                _p(o["counts"]), _p(o["status"]), _p(ws), _lib.stream()),
                "orbl_update_connections_device")
     r = dict(o)
     r.setdefault("link_off", None); r.setdefault("link_kf", None)
@@ -410,8 +378,8 @@ def set_bad_keyframes(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps=None, 
     for k, v in ({} if out is None else out).items():
         assert v.dtype == o[k].dtype and v.flags.c_contiguous and v.size == o[k].size, k
         o[k] = v
-    rc = L.orbl_set_bad_keyframes(ntgt, _addr(tk), _addr(tf), _addr(tm), nkf, *[_addr(a[k]) for k, _ in _BF_KF], npts, *[_addr(a.get(k)) for k, _ in _BF_PT],
-                                  _addr(a.get("obs_erased")), int(cap_ord), int(cap_child), *[_addr(o[k]) for k in _BF_OUT])
+    rc = L.orbl_set_bad_keyframes(ntgt, _p(tk), _p(tf), _p(tm), nkf, *[_p(a[k]) for k, _ in _BF_KF], npts, *[_p(a.get(k)) for k, _ in _BF_PT],
+                                  _p(a.get("obs_erased")), int(cap_ord), int(cap_child), *[_p(o[k]) for k in _BF_OUT])
     if rc == ECAP and not check:
         return BadFlagResult(rc=rc, counts=o["counts"], obs_erased=a.get("obs_erased"), **{k: a.get(k) for k in _BF_INOUT})
     _lib.check(rc, "orbl_set_bad_keyframes")
@@ -435,10 +403,7 @@ def set_bad_keyframes_device(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps
     nchild, nconn, nord = a["child_kf"].numel(), a["conn_kf"].numel(), a["ord_kf"].numel()
     npts, nslots, nobs = (a["obs_off"].numel() - 1, a["kf_slot_pt"].numel(), a["obs_kf"].numel()) if points else (0, 0, 0)
     cap_ord, cap_child = _bf_default_caps(nkf, nchild, nconn, nord, ntgt) if caps is None else caps
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_set_bad_keyframes_workspace(ntgt, nkf, nchild, nconn, nobs, C.byref(nbytes)), "orbl_set_bad_keyframes_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_set_bad_keyframes_workspace", ntgt, nkf, nchild, nconn, nobs, device=dev, reuse=workspace)
     o = {} if out is None else out
     sizes = dict(tgt_status=ntgt, oconn_off=nkf + 1, oconn_kf=nconn, oconn_w=nconn, oord_off=nkf + 1, oord_kf=cap_ord, oord_w=cap_ord, ochild_off=nkf + 1,
                  ochild_kf=cap_child, counts=6, status=1)
@@ -450,15 +415,12 @@ def set_bad_keyframes_device(tgt_kf, tables, tgt_flags=None, tgt_mask=None, caps
         o["tgt_Tcp"] = torch.empty((max(ntgt, 1), 12), dtype=torch.float64, device=dev)[:ntgt]
     if points and o.get("obs_erased") is None:
         o["obs_erased"] = torch.empty(max(nobs, 1), dtype=torch.uint8, device=dev)[:nobs]
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_set_bad_keyframes_device(ntgt, p(tgt_kf), p(tgt_flags), p(tgt_mask), nkf, p(a["kf_bad"]), p(a["kf_parent"]), p(a["kf_rank"]), p(a["kf_Tcw"]),
-                                               nchild, p(a["child_off"]), p(a["child_kf"]), nconn, p(a["conn_off"]), p(a["conn_kf"]), p(a["conn_w"]), nord,
-                                               p(a["ord_off"]), p(a["ord_kf"]), p(a["ord_w"]), npts, nslots, p(a["kf_slot_off"]), p(a["kf_slot_pt"]), p(a["pt_bad"]),
-                                               p(a["pt_nobs"]), p(a["pt_ref_kf"]), nobs, p(a["obs_off"]), p(a["obs_kf"]), p(a["obs_slot"]), p(o.get("obs_erased")),
-                                               int(cap_ord), int(cap_child), *[p(o[k]) for k in _BF_OUT], p(o["status"]), p(ws),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_set_bad_keyframes_device")
+    _lib.check(L.orbl_set_bad_keyframes_device(ntgt, _p(tgt_kf), _p(tgt_flags), _p(tgt_mask), nkf, _p(a["kf_bad"]), _p(a["kf_parent"]), _p(a["kf_rank"]), _p(a["kf_Tcw"]),
+                                               nchild, _p(a["child_off"]), _p(a["child_kf"]), nconn, _p(a["conn_off"]), _p(a["conn_kf"]), _p(a["conn_w"]), nord,
+                                               _p(a["ord_off"]), _p(a["ord_kf"]), _p(a["ord_w"]), npts, nslots, _p(a["kf_slot_off"]), _p(a["kf_slot_pt"]), _p(a["pt_bad"]),
+                                               _p(a["pt_nobs"]), _p(a["pt_ref_kf"]), nobs, _p(a["obs_off"]), _p(a["obs_kf"]), _p(a["obs_slot"]), _p(o.get("obs_erased")),
+                                               int(cap_ord), int(cap_child), *[_p(o[k]) for k in _BF_OUT], _p(o["status"]), _p(ws),
+                                               _lib.stream()), "orbl_set_bad_keyframes_device")
     return BadFlagResult(rc=0, status=o["status"], obs_erased=o.get("obs_erased"), _workspace=ws, **{k: a.get(k) for k in _BF_INOUT}, **{k: o[k] for k in _BF_OUT})
 
 
@@ -525,9 +487,9 @@ def apply_map_edits(ops, tables, cap_obs=None, out=None, check=True):
         assert k in o and o[k] is not None, "out[%r]: no such output (oobs_level / oobs_uv need the kf_slot_level pair)" % k
         assert v.dtype == o[k].dtype and v.flags.c_contiguous and v.size == o[k].size, k
         o[k] = v
-    rc = L.orbl_apply_map_edits(nops, *[_addr(v) for v in op], nkf, *[_addr(a[k]) for k in ("kf_slot_off", "kf_rank", "kf_slot_pt", "kf_slot_level", "kf_slot_uv")],
-                                npts, *[_addr(a[k]) for k in ("pt_bad", "pt_nobs", "pt_found", "pt_visible", "pt_replaced", "obs_off", "obs_kf", "obs_slot", "obs_dead")],
-                                cap_obs, *[_addr(o[k]) for k, _ in _ME_OUT])
+    rc = L.orbl_apply_map_edits(nops, *[_p(v) for v in op], nkf, *[_p(a[k]) for k in ("kf_slot_off", "kf_rank", "kf_slot_pt", "kf_slot_level", "kf_slot_uv")],
+                                npts, *[_p(a[k]) for k in ("pt_bad", "pt_nobs", "pt_found", "pt_visible", "pt_replaced", "obs_off", "obs_kf", "obs_slot", "obs_dead")],
+                                cap_obs, *[_p(o[k]) for k, _ in _ME_OUT])
     if rc == ECAP and not check:
         return MapEditResult(rc=rc, counts=o["counts"], **{k: a[k] for k in _ME_INOUT})
     _lib.check(rc, "orbl_apply_map_edits")
@@ -554,10 +516,7 @@ def apply_map_edits_device(ops, tables, cap_obs=None, out=None, workspace=None):
     nslots, nobs = a["kf_slot_pt"].numel(), a["obs_kf"].numel()
     attrs = a["kf_slot_level"] is not None
     cap_obs = nobs + nops if cap_obs is None else int(cap_obs)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_apply_map_edits_workspace(nops, nkf, npts, nslots, nobs, C.byref(nbytes)), "orbl_apply_map_edits_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_apply_map_edits_workspace", nops, nkf, npts, nslots, nobs, device=dev, reuse=workspace)
     o = {} if out is None else out
     sizes = dict(_me_sizes(nops, npts, cap_obs, attrs), status=1)
     tdt = {np.int32: torch.int32, np.uint8: torch.uint8, np.float32: torch.float32}
@@ -570,13 +529,10 @@ def apply_map_edits_device(ops, tables, cap_obs=None, out=None, workspace=None):
         if o.get(k) is None:
             o[k] = torch.empty(max(n, 1), dtype=tdt[dt], device=dev)[:n]
         assert o[k].dtype == tdt[dt] and o[k].is_contiguous() and o[k].numel() == n, k
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_apply_map_edits_device(nops, *[p(v) for v in op], nkf, p(a["kf_slot_off"]), p(a["kf_rank"]), nslots, p(a["kf_slot_pt"]), p(a["kf_slot_level"]),
-                                             p(a["kf_slot_uv"]), npts, p(a["pt_bad"]), p(a["pt_nobs"]), p(a["pt_found"]), p(a["pt_visible"]), p(a["pt_replaced"]), nobs,
-                                             p(a["obs_off"]), p(a["obs_kf"]), p(a["obs_slot"]), p(a["obs_dead"]), cap_obs, *[p(o[k]) for k, _ in _ME_OUT], p(o["status"]),
-                                             p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_apply_map_edits_device")
+    _lib.check(L.orbl_apply_map_edits_device(nops, *[_p(v) for v in op], nkf, _p(a["kf_slot_off"]), _p(a["kf_rank"]), nslots, _p(a["kf_slot_pt"]), _p(a["kf_slot_level"]),
+                                             _p(a["kf_slot_uv"]), npts, _p(a["pt_bad"]), _p(a["pt_nobs"]), _p(a["pt_found"]), _p(a["pt_visible"]), _p(a["pt_replaced"]), nobs,
+                                             _p(a["obs_off"]), _p(a["obs_kf"]), _p(a["obs_slot"]), _p(a["obs_dead"]), cap_obs, *[_p(o[k]) for k, _ in _ME_OUT], _p(o["status"]),
+                                             _p(ws), _lib.stream()), "orbl_apply_map_edits_device")
     return MapEditResult(rc=0, status=o["status"], _workspace=ws, **{k: a[k] for k in _ME_INOUT}, **{k: o[k] for k, _ in _ME_OUT})
 
 
@@ -595,10 +551,6 @@ _AP_INOUT = (("kf_Tcw", np.float64), ("kf_center", np.float64), ("kf_slot_pt", n
              ("pt_ref_kf", np.int32))
 _AP_IN = (("kf_slot_off", np.int32), ("obs_off", np.int32), ("obs_kf", np.int32), ("obs_slot", np.int32), ("obs_level", np.int32), ("kf_level0", np.int32),
           ("scale_factors", np.float32))
-
-
-def _flat(a, dt):
-    return None if a is None else _c(a, dt).reshape(-1)
 
 
 def local_ba_assemble(cur_kf, nbr_kf, tab, caps=None, out=None, check=True, device=False, **kw):
@@ -627,13 +579,10 @@ def local_ba_assemble(cur_kf, nbr_kf, tab, caps=None, out=None, check=True, devi
         o.setdefault(k, np.zeros(w * cap[c], dt))
         assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * cap[c], k
     o.setdefault("kf_role", np.zeros(nkf, np.uint8)); o.setdefault("pt_local", np.zeros(npts, np.uint8)); o.setdefault("counts", np.zeros(4, np.int32))
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
-    rc = L.orbl_local_ba_assemble(int(cur_kf), len(nb), a(nb), nkf, *[a(t[k]) for k in ("kf_id", "kf_bad", "kf_rank", "kf_Tcw", "kf_K4")], _addr(t["kf_slot_off"]),
-                                  a(t["kf_slot_pt"]), npts, a(t["X"]), a(t["pt_bad"]), a(t["pt_rank"]), _addr(t["obs_off"]), a(t["obs_kf"]), a(t["obs_uv"]),
-                                  a(t["obs_level"]), a(t["inv_level_sigma2"]), len(t["inv_level_sigma2"]), cap[0], cap[1], cap[2], _addr(o["counts"]),
-                                  *[a(o[k]) for k, _, _, _ in _LA_OUT], a(o["kf_role"]), a(o["pt_local"]))
+    rc = L.orbl_local_ba_assemble(int(cur_kf), len(nb), _pn(nb), nkf, *[_pn(t[k]) for k in ("kf_id", "kf_bad", "kf_rank", "kf_Tcw", "kf_K4")], _p(t["kf_slot_off"]),
+                                  _pn(t["kf_slot_pt"]), npts, _pn(t["X"]), _pn(t["pt_bad"]), _pn(t["pt_rank"]), _p(t["obs_off"]), _pn(t["obs_kf"]), _pn(t["obs_uv"]),
+                                  _pn(t["obs_level"]), _pn(t["inv_level_sigma2"]), len(t["inv_level_sigma2"]), cap[0], cap[1], cap[2], _p(o["counts"]),
+                                  *[_pn(o[k]) for k, _, _, _ in _LA_OUT], _pn(o["kf_role"]), _pn(o["pt_local"]))
     if rc == ECAP and not check:
         return dict(rc=rc, counts=o["counts"])
     _lib.check(rc, "orbl_local_ba_assemble")
@@ -655,10 +604,7 @@ def local_ba_assemble_device(cur_kf, nbr_kf, tab, caps=None, out=None, workspace
     n_nbr = nbr_kf.numel() if nbr_kf is not None else 0
     nkf, npts, nobs, nslots = tab["kf_id"].numel(), tab["X"].numel() // 3, tab["obs_kf"].numel(), tab["kf_slot_pt"].numel()
     cap = (nkf, npts, nobs) if caps is None else tuple(int(c) for c in caps)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_local_ba_assemble_workspace(nkf, npts, C.byref(nbytes)), "orbl_local_ba_assemble_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_local_ba_assemble_workspace", nkf, npts, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     tdt = {np.int32: torch.int32, np.float64: torch.float64, np.float32: torch.float32, np.uint8: torch.uint8}
     sizes = [(k, tdt[dt], w * cap[c]) for k, dt, w, c in _LA_OUT] + [("kf_role", torch.uint8, nkf), ("pt_local", torch.uint8, npts), ("counts", torch.int32, 4),
@@ -667,14 +613,11 @@ def local_ba_assemble_device(cur_kf, nbr_kf, tab, caps=None, out=None, workspace
         if o.get(k) is None:
             o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_local_ba_assemble_device(int(cur_kf), n_nbr, p(nbr_kf), nkf, p(g("kf_id")), p(g("kf_bad")), p(g("kf_rank")), p(g("kf_Tcw")), p(g("kf_K4")), nslots,
-                                               C.c_void_p(tab["kf_slot_off"].data_ptr()), p(g("kf_slot_pt")), npts, p(g("X")), p(g("pt_bad")), p(g("pt_rank")), nobs,
-                                               C.c_void_p(tab["obs_off"].data_ptr()), p(g("obs_kf")), p(g("obs_uv")), p(g("obs_level")), p(g("inv_level_sigma2")),
-                                               tab["inv_level_sigma2"].numel(), cap[0], cap[1], cap[2], p(o["counts"]), *[p(o[k]) for k, _, _, _ in _LA_OUT],
-                                               p(o["kf_role"]), p(o["pt_local"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+    _lib.check(L.orbl_local_ba_assemble_device(int(cur_kf), n_nbr, _pn(nbr_kf), nkf, _pn(g("kf_id")), _pn(g("kf_bad")), _pn(g("kf_rank")), _pn(g("kf_Tcw")), _pn(g("kf_K4")), nslots,
+                                               _p(tab["kf_slot_off"]), _pn(g("kf_slot_pt")), npts, _pn(g("X")), _pn(g("pt_bad")), _pn(g("pt_rank")), nobs,
+                                               _p(tab["obs_off"]), _pn(g("obs_kf")), _pn(g("obs_uv")), _pn(g("obs_level")), _pn(g("inv_level_sigma2")),
+                                               tab["inv_level_sigma2"].numel(), cap[0], cap[1], cap[2], _pn(o["counts"]), *[_pn(o[k]) for k, _, _, _ in _LA_OUT],
+                                               _pn(o["kf_role"]), _pn(o["pt_local"]), _pn(o["status"]), _pn(ws), _lib.stream()),
                "orbl_local_ba_assemble_device")
     r = dict(o)
     r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
@@ -712,14 +655,11 @@ def local_ba_apply(asm, poses7, pts3, obs_erase, tab, normals=True, out=None, de
         assert len(t["obs_level"]) == nobs
     else:
         o.update(normal=None, min_max=None, nd_written=None)
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
     sf = t["scale_factors"] if normals else None
-    _lib.check(L.orbl_local_ba_apply(ncam, a(ck), a(cl), a(p7), npl, a(lp), a(p3), nol, a(ls), a(er), nkf, a(io["kf_Tcw"]), a(io["kf_center"]), _addr(t["kf_slot_off"]),
-                                     a(io["kf_slot_pt"]), npts, a(io["X"]), a(io["pt_bad"]), a(io["pt_nobs"]), a(io["pt_ref_kf"]), _addr(t["obs_off"]), a(t["obs_kf"]),
-                                     a(t["obs_slot"]), a(t["obs_level"]), a(t["kf_level0"]), _addr(sf), len(sf) if sf is not None else 0, a(o["obs_erased"]),
-                                     _addr(o["normal"]), _addr(o["min_max"]), _addr(o["nd_written"]), _addr(o["counts"])), "orbl_local_ba_apply")
+    _lib.check(L.orbl_local_ba_apply(ncam, _pn(ck), _pn(cl), _pn(p7), npl, _pn(lp), _pn(p3), nol, _pn(ls), _pn(er), nkf, _pn(io["kf_Tcw"]), _pn(io["kf_center"]), _p(t["kf_slot_off"]),
+                                     _pn(io["kf_slot_pt"]), npts, _pn(io["X"]), _pn(io["pt_bad"]), _pn(io["pt_nobs"]), _pn(io["pt_ref_kf"]), _p(t["obs_off"]), _pn(t["obs_kf"]),
+                                     _pn(t["obs_slot"]), _pn(t["obs_level"]), _pn(t["kf_level0"]), _p(sf), len(sf) if sf is not None else 0, _pn(o["obs_erased"]),
+                                     _p(o["normal"]), _p(o["min_max"]), _p(o["nd_written"]), _p(o["counts"])), "orbl_local_ba_apply")
     r = dict(o)
     r.update(io)
     r["kf_Tcw"] = io["kf_Tcw"].reshape(-1, 12); r["X"] = io["X"].reshape(-1, 3)
@@ -742,10 +682,7 @@ def local_ba_apply_device(asm, poses7, pts3, obs_erase, tab, normals=True, out=N
         n = (c[0], c[2], c[3])
     ncam, npl, nol = (int(v) for v in n)
     nkf, npts, nobs, nslots = tab["kf_Tcw"].numel() // 12, tab["X"].numel() // 3, tab["obs_kf"].numel(), tab["kf_slot_pt"].numel()
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_local_ba_apply_workspace(nobs, C.byref(nbytes)), "orbl_local_ba_apply_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_local_ba_apply_workspace", nobs, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     sizes = [("obs_erased", torch.uint8, nobs), ("counts", torch.int32, 4), ("status", torch.int32, 1)]
     if normals:
@@ -754,18 +691,15 @@ def local_ba_apply_device(asm, poses7, pts3, obs_erase, tab, normals=True, out=N
         if o.get(k) is None:
             o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
     for k, _ in _AP_INOUT:
         assert g(k) is None or g(k).is_contiguous(), k
     sf = g("scale_factors") if normals else None
-    _lib.check(L.orbl_local_ba_apply_device(ncam, p(asm["cam_kf"]), p(asm["cam_local"]), p(poses7), npl, p(asm["lpt_pt"]), p(pts3), nol, p(asm["lobs_src"]), p(obs_erase),
-                                            nkf, p(g("kf_Tcw")), p(g("kf_center")), nslots, C.c_void_p(tab["kf_slot_off"].data_ptr()), p(g("kf_slot_pt")), npts, p(g("X")),
-                                            p(g("pt_bad")), p(g("pt_nobs")), p(g("pt_ref_kf")), nobs, C.c_void_p(tab["obs_off"].data_ptr()), p(g("obs_kf")), p(g("obs_slot")),
-                                            p(g("obs_level")), p(g("kf_level0")), None if sf is None else C.c_void_p(sf.data_ptr()), sf.numel() if sf is not None else 0,
-                                            p(o["obs_erased"]), *[None if o.get(k) is None else C.c_void_p(o[k].data_ptr()) for k in ("normal", "min_max", "nd_written")],
-                                            p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_local_ba_apply_device")
+    _lib.check(L.orbl_local_ba_apply_device(ncam, _pn(asm["cam_kf"]), _pn(asm["cam_local"]), _pn(poses7), npl, _pn(asm["lpt_pt"]), _pn(pts3), nol, _pn(asm["lobs_src"]), _pn(obs_erase),
+                                            nkf, _pn(g("kf_Tcw")), _pn(g("kf_center")), nslots, _p(tab["kf_slot_off"]), _pn(g("kf_slot_pt")), npts, _pn(g("X")),
+                                            _pn(g("pt_bad")), _pn(g("pt_nobs")), _pn(g("pt_ref_kf")), nobs, _p(tab["obs_off"]), _pn(g("obs_kf")), _pn(g("obs_slot")),
+                                            _pn(g("obs_level")), _pn(g("kf_level0")), _p(sf), sf.numel() if sf is not None else 0,
+                                            _pn(o["obs_erased"]), *[_p(o.get(k)) for k in ("normal", "min_max", "nd_written")],
+                                            _pn(o["counts"]), _pn(o["status"]), _pn(ws), _lib.stream()), "orbl_local_ba_apply_device")
     r = dict(o)
     for k in ("normal", "min_max", "nd_written"):
         r.setdefault(k, None)
@@ -821,15 +755,6 @@ _SN_TAB = (("kf_bad", np.uint8), ("kf_rank", np.int32), ("kf_Tcw", np.float64), 
 _SN_ROWS = ("op_kind", "op_pt", "op_arg", "op_kf", "op_slot", "best_idx", "best_dist", "q_uv", "q_level")
 
 
-def _sn_p(t):
-    """numpy array or torch tensor -> void*; None and empty ones -> NULL"""
-    if t is None:
-        return None
-    if hasattr(t, "data_ptr"):
-        return C.c_void_p(t.data_ptr()) if t.numel() else None
-    return _addr(t) if t.size else None
-
-
 def _sn_host(tab, keys):
     dt = dict(_SN_TAB)
     return {k: (None if tab.get(k) is None else _c(tab[k], dt[k]).reshape(-1)) for k in keys}
@@ -845,11 +770,6 @@ def _sn_dev_out(o, sizes, dev):
     return o
 
 
-def _sn_stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def fuse_targets(cur_kf, cur_id, tab, nn=20, nn2=5, cap_tgt=None, device=False, out=None):
     """The target keyframes of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:400-431; orbl_fuse_targets, include/orbslam_hip.h states
     the semantics).  tab: kf_bad (may be None), ord_off, ord_kf, kf_fuse_target.  cap_tgt: default nn (1 + nn2), which no call exceeds.
@@ -860,15 +780,15 @@ def fuse_targets(cur_kf, cur_id, tab, nn=20, nn2=5, cap_tgt=None, device=False, 
     if device:
         dev = tab["ord_off"].device
         o = _sn_dev_out({} if out is None else out, (("tgt_kf", np.int32, cap), ("counts", np.int32, 2), ("status", np.int32, 1)), dev)
-        _lib.check(L.orbl_fuse_targets_device(int(cur_kf), int(cur_id), tab["ord_off"].numel() - 1, _sn_p(tab.get("kf_bad")), tab["ord_kf"].numel(),
-                                              C.c_void_p(tab["ord_off"].data_ptr()), _sn_p(tab["ord_kf"]), C.c_void_p(tab["kf_fuse_target"].data_ptr()), int(nn), int(nn2),
-                                              cap, _sn_p(o["tgt_kf"]), _sn_p(o["counts"]), _sn_p(o["status"]), None, _sn_stream()), "orbl_fuse_targets_device")
+        _lib.check(L.orbl_fuse_targets_device(int(cur_kf), int(cur_id), tab["ord_off"].numel() - 1, _pn(tab.get("kf_bad")), tab["ord_kf"].numel(),
+                                              _p(tab["ord_off"]), _pn(tab["ord_kf"]), _p(tab["kf_fuse_target"]), int(nn), int(nn2),
+                                              cap, _pn(o["tgt_kf"]), _pn(o["counts"]), _pn(o["status"]), None, _lib.stream()), "orbl_fuse_targets_device")
         return dict(o, kf_fuse_target=tab["kf_fuse_target"])
     t = _sn_host(tab, ("kf_bad", "ord_off", "ord_kf"))
     stamp = np.array(tab["kf_fuse_target"], np.int32).reshape(-1)
     tgt, counts = np.zeros(max(cap, 1), np.int32), np.zeros(2, np.int32)
-    _lib.check(L.orbl_fuse_targets(int(cur_kf), int(cur_id), len(t["ord_off"]) - 1, _sn_p(t["kf_bad"]), _addr(t["ord_off"]), _sn_p(t["ord_kf"]), _addr(stamp), int(nn),
-                                   int(nn2), cap, _addr(tgt) if cap else None, _addr(counts)), "orbl_fuse_targets")
+    _lib.check(L.orbl_fuse_targets(int(cur_kf), int(cur_id), len(t["ord_off"]) - 1, _pn(t["kf_bad"]), _p(t["ord_off"]), _pn(t["ord_kf"]), _p(stamp), int(nn),
+                                   int(nn2), cap, _p(tgt) if cap else None, _p(counts)), "orbl_fuse_targets")
     return dict(tgt_kf=tgt[:counts[0]], counts=counts, kf_fuse_target=stamp)
 
 
@@ -892,18 +812,18 @@ def fuse_rows(kf, pts, tab, th=3.0, log_scale_factor=None, device=False, out=Non
         o = _sn_dev_out({} if out is None else out, [(k, np.float32 if k == "q_uv" else np.int32, 2 * n if k == "q_uv" else n) for k in names] + [("status", np.int32, 1)],
                         dev)
         assert tab["kf_K4"].element_size() == 4 and tab["kf_bounds"].element_size() == 4, "kf_K4 and kf_bounds are float32 tables"
-        _lib.check(L.orbl_fuse_rows_device(C.c_void_p(kf.data_ptr()), n, _sn_p(pts), tab["kf_slot_off"].numel() - 1, *[_sn_p(tab[k]) for k in _SN_ROW_KF[:4]],
-                                           C.c_void_p(tab["kf_slot_off"].data_ptr()), tab["kf_slot_level"].numel(), *[_sn_p(tab[k]) for k in _SN_ROW_SLOT],
-                                           tab["pt_max_dist"].numel(), *[_sn_p(tab[k]) for k in _SN_ROW_PT], lsf, tab["scale_factors"].numel(), float(th),
-                                           *[_sn_p(o.get(k)) for k in _SN_ROWS], _sn_p(o["status"]), None, _sn_stream()), "orbl_fuse_rows_device")
+        _lib.check(L.orbl_fuse_rows_device(_p(kf), n, _pn(pts), tab["kf_slot_off"].numel() - 1, *[_pn(tab[k]) for k in _SN_ROW_KF[:4]],
+                                           _p(tab["kf_slot_off"]), tab["kf_slot_level"].numel(), *[_pn(tab[k]) for k in _SN_ROW_SLOT],
+                                           tab["pt_max_dist"].numel(), *[_pn(tab[k]) for k in _SN_ROW_PT], lsf, tab["scale_factors"].numel(), float(th),
+                                           *[_pn(o.get(k)) for k in _SN_ROWS], _pn(o["status"]), None, _lib.stream()), "orbl_fuse_rows_device")
         return o
     t = _sn_host(tab, _SN_ROW_KF + _SN_ROW_SLOT + _SN_ROW_PT)
     pl = _c(pts, np.int32).reshape(-1)
     n = len(pl)
     o = {k: np.zeros(2 * n if k == "q_uv" else n, np.float32 if k == "q_uv" else np.int32) for k in names}
-    _lib.check(L.orbl_fuse_rows(int(kf), n, _sn_p(pl), len(t["kf_slot_off"]) - 1, *[_sn_p(t[k]) for k in _SN_ROW_KF[:4]], _addr(t["kf_slot_off"]),
-                                *[_sn_p(t[k]) for k in _SN_ROW_SLOT], len(t["pt_max_dist"]), *[_sn_p(t[k]) for k in _SN_ROW_PT], lsf, len(t["scale_factors"]), float(th),
-                                *[_sn_p(o.get(k)) for k in _SN_ROWS]), "orbl_fuse_rows")
+    _lib.check(L.orbl_fuse_rows(int(kf), n, _pn(pl), len(t["kf_slot_off"]) - 1, *[_pn(t[k]) for k in _SN_ROW_KF[:4]], _p(t["kf_slot_off"]),
+                                *[_pn(t[k]) for k in _SN_ROW_SLOT], len(t["pt_max_dist"]), *[_pn(t[k]) for k in _SN_ROW_PT], lsf, len(t["scale_factors"]), float(th),
+                                *[_pn(o.get(k)) for k in _SN_ROWS]), "orbl_fuse_rows")
     if extras:
         o["q_uv"] = o["q_uv"].reshape(-1, 2)
     return o
@@ -917,18 +837,14 @@ def fuse_candidates(tgt_kf, cur_id, tab, cap_cand=None, device=False, out=None, 
     integer), the stamps change IN PLACE, enqueued on the current stream, nothing synchronised; cand_pt comes at full capacity."""
     L = _lib.load()
     if device:
-        import torch
         dev = tab["kf_slot_off"].device
         n_tgt, nkf, nslots, npts = tgt_kf.numel(), tab["kf_slot_off"].numel() - 1, tab["kf_slot_pt"].numel(), tab["pt_bad"].numel()
         cap = npts if cap_cand is None else int(cap_cand)
-        nbytes = C.c_size_t(0)
-        _lib.check(L.orbl_fuse_candidates_workspace(n_tgt, npts, C.byref(nbytes)), "orbl_fuse_candidates_workspace")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-        assert ws.numel() >= nbytes.value
+        ws = _lib.workspace("orbl_fuse_candidates_workspace", n_tgt, npts, device=dev, reuse=workspace)
         o = _sn_dev_out({} if out is None else out, (("cand_pt", np.int32, cap), ("counts", np.int32, 2), ("status", np.int32, 1)), dev)
-        _lib.check(L.orbl_fuse_candidates_device(n_tgt, _sn_p(tgt_kf), nkf, C.c_void_p(tab["kf_slot_off"].data_ptr()), nslots, _sn_p(tab["kf_slot_pt"]), npts,
-                                                 _sn_p(tab["pt_bad"]), _sn_p(tab["pt_fuse_cand"]), int(cur_id), cap, _sn_p(o["cand_pt"]), _sn_p(o["counts"]),
-                                                 _sn_p(o["status"]), C.c_void_p(ws.data_ptr()), _sn_stream()), "orbl_fuse_candidates_device")
+        _lib.check(L.orbl_fuse_candidates_device(n_tgt, _pn(tgt_kf), nkf, _p(tab["kf_slot_off"]), nslots, _pn(tab["kf_slot_pt"]), npts,
+                                                 _pn(tab["pt_bad"]), _pn(tab["pt_fuse_cand"]), int(cur_id), cap, _pn(o["cand_pt"]), _pn(o["counts"]),
+                                                 _pn(o["status"]), _p(ws), _lib.stream()), "orbl_fuse_candidates_device")
         return dict(o, pt_fuse_cand=tab["pt_fuse_cand"], _workspace=ws)
     t = _sn_host(tab, ("kf_slot_off", "kf_slot_pt", "pt_bad"))
     tg = _c(tgt_kf, np.int32).reshape(-1)
@@ -936,8 +852,8 @@ def fuse_candidates(tgt_kf, cur_id, tab, cap_cand=None, device=False, out=None, 
     npts = len(t["pt_bad"])
     cap = npts if cap_cand is None else int(cap_cand)
     cand, counts = np.zeros(max(cap, 1), np.int32), np.zeros(2, np.int32)
-    _lib.check(L.orbl_fuse_candidates(len(tg), _sn_p(tg), len(t["kf_slot_off"]) - 1, _addr(t["kf_slot_off"]), _sn_p(t["kf_slot_pt"]), npts, _sn_p(t["pt_bad"]),
-                                      _sn_p(stamp), int(cur_id), cap, _addr(cand) if cap else None, _addr(counts)), "orbl_fuse_candidates")
+    _lib.check(L.orbl_fuse_candidates(len(tg), _pn(tg), len(t["kf_slot_off"]) - 1, _p(t["kf_slot_off"]), _pn(t["kf_slot_pt"]), npts, _pn(t["pt_bad"]),
+                                      _pn(stamp), int(cur_id), cap, _p(cand) if cap else None, _p(counts)), "orbl_fuse_candidates")
     return dict(cand_pt=cand[:counts[0]], counts=counts, pt_fuse_cand=stamp)
 
 
@@ -956,22 +872,18 @@ def update_map_points_on_tables(what, tab, pt_mask=None, mask_kf=-1, device=Fals
     L = _lib.load()
     desc, nd = bool(what & MP_DESC), bool(what & MP_NORMAL_DEPTH)
     if device:
-        import torch
         g = tab.get
         dev = tab["obs_off"].device
         nkf, nslots, npts, nobs = tab["kf_slot_off"].numel() - 1, tab["kf_slot_desc"].numel() // 32, tab["pt_bad"].numel(), tab["obs_kf"].numel()
-        nbytes = C.c_size_t(0)
-        _lib.check(L.orbl_update_map_points_on_tables_workspace(npts, nobs, C.byref(nbytes)), "orbl_update_map_points_on_tables_workspace")
-        ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
-        assert ws.numel() >= nbytes.value
+        ws = _lib.workspace("orbl_update_map_points_on_tables_workspace", npts, nobs, device=dev, min_bytes=16, reuse=workspace)
         o = _sn_dev_out({} if out is None else out, (("best_obs", np.int32, npts), ("nd_written", np.uint8, npts), ("status", np.int32, 1)), dev)
         sf = g("scale_factors")
-        _lib.check(L.orbl_update_map_points_on_tables_device(int(what), _sn_p(pt_mask), int(mask_kf), nkf, _sn_p(g("kf_bad")), _sn_p(g("kf_center")),
-                                                             C.c_void_p(tab["kf_slot_off"].data_ptr()), nslots, _sn_p(g("kf_slot_pt")), _sn_p(g("kf_slot_level")),
-                                                             _sn_p(tab["kf_slot_desc"]), npts, _sn_p(tab["pt_bad"]), _sn_p(g("X")), _sn_p(g("pt_ref_kf")), nobs,
-                                                             C.c_void_p(tab["obs_off"].data_ptr()), _sn_p(tab["obs_kf"]), _sn_p(tab["obs_slot"]), _sn_p(sf),
-                                                             sf.numel() if sf is not None else 0, *[_sn_p(g(k)) for k in _SN_UPD_INOUT], _sn_p(o["best_obs"]),
-                                                             _sn_p(o["nd_written"]), _sn_p(o["status"]), C.c_void_p(ws.data_ptr()), _sn_stream()),
+        _lib.check(L.orbl_update_map_points_on_tables_device(int(what), _pn(pt_mask), int(mask_kf), nkf, _pn(g("kf_bad")), _pn(g("kf_center")),
+                                                             _p(tab["kf_slot_off"]), nslots, _pn(g("kf_slot_pt")), _pn(g("kf_slot_level")),
+                                                             _pn(tab["kf_slot_desc"]), npts, _pn(tab["pt_bad"]), _pn(g("X")), _pn(g("pt_ref_kf")), nobs,
+                                                             _p(tab["obs_off"]), _pn(tab["obs_kf"]), _pn(tab["obs_slot"]), _pn(sf),
+                                                             sf.numel() if sf is not None else 0, *[_pn(g(k)) for k in _SN_UPD_INOUT], _pn(o["best_obs"]),
+                                                             _pn(o["nd_written"]), _pn(o["status"]), _p(ws), _lib.stream()),
                    "orbl_update_map_points_on_tables_device")
         return dict(o, _workspace=ws, **{k: g(k) for k in _SN_UPD_INOUT})
     t = _sn_host(tab, _SN_UPD_IN)
@@ -982,11 +894,11 @@ def update_map_points_on_tables(what, tab, pt_mask=None, mask_kf=-1, device=Fals
     assert pm is None or len(pm) == npts
     best, wrote = np.full(npts, -1, np.int32), np.zeros(npts, np.uint8)
     sf = t["scale_factors"]
-    _lib.check(L.orbl_update_map_points_on_tables(int(what), _sn_p(pm), int(mask_kf), len(t["kf_slot_off"]) - 1, _sn_p(t["kf_bad"]), _sn_p(t["kf_center"]),
-                                                  _addr(t["kf_slot_off"]), _sn_p(t["kf_slot_pt"]), _sn_p(t["kf_slot_level"]), _sn_p(t["kf_slot_desc"]), npts,
-                                                  _sn_p(t["pt_bad"]), _sn_p(t["X"]), _sn_p(t["pt_ref_kf"]), _addr(t["obs_off"]), _sn_p(t["obs_kf"]), _sn_p(t["obs_slot"]),
-                                                  _sn_p(sf), len(sf) if sf is not None else 0, *[_sn_p(io[k]) for k in _SN_UPD_INOUT], _sn_p(best) if desc else None,
-                                                  _sn_p(wrote) if nd else None), "orbl_update_map_points_on_tables")
+    _lib.check(L.orbl_update_map_points_on_tables(int(what), _pn(pm), int(mask_kf), len(t["kf_slot_off"]) - 1, _pn(t["kf_bad"]), _pn(t["kf_center"]),
+                                                  _p(t["kf_slot_off"]), _pn(t["kf_slot_pt"]), _pn(t["kf_slot_level"]), _pn(t["kf_slot_desc"]), npts,
+                                                  _pn(t["pt_bad"]), _pn(t["X"]), _pn(t["pt_ref_kf"]), _p(t["obs_off"]), _pn(t["obs_kf"]), _pn(t["obs_slot"]),
+                                                  _pn(sf), len(sf) if sf is not None else 0, *[_pn(io[k]) for k in _SN_UPD_INOUT], _pn(best) if desc else None,
+                                                  _pn(wrote) if nd else None), "orbl_update_map_points_on_tables")
     r = dict(io, best_obs=best, nd_written=wrote)
     if r["pt_desc"] is not None:
         r["pt_desc"] = r["pt_desc"].reshape(-1, 32)

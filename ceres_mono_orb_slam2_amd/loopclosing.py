@@ -1,30 +1,17 @@
 """LoopClosing's two map-moving steps on the GPU (include/orbslam_hip.h: orbl_correct_loop*, orbl_propagate_global_ba*): the pose and
 point correction of CorrectLoop (src/LoopClosing.cc:437-523) and the write-back of the global bundle adjustment (:681-739).
 There is no CPU fallback: without the library or a GPU the calls raise."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._lib import carray as _c, flat as _flat, ptr as _p, ptr_nonempty as _pn
 
 ML_OFFSETS, ML_KF, ML_PT, ML_RANK, ML_LEVEL, ML_SCW = 1, 2, 4, 8, 16, 32        # *d_status bits of orbl_correct_loop_device
 GB_KF, GB_CYCLE, GB_STALE = 1, 2, 4                                             # *d_status bits of orbl_propagate_global_ba_device
 
 
-def _c(a, dt):
-    return np.ascontiguousarray(a, dt)
-
-
 def _copy(a, dt, shape):
     return np.array(a, dtype=dt, order="C").reshape(shape)          # (always a copy: the in/out tables are returned, the caller's stay)
-
-
-def _opt(a, dt):
-    return None if a is None else _c(a, dt).reshape(-1)
-
-
-def _addr(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
 
 
 def correct_loop(kf_Tcw, conn_kf, Scw, slot_off, slot_pt, X, kf_center=None, conn_rank=None, pt_bad=None, pt_done=None, obs_off=None, obs_kf=None,
@@ -43,12 +30,12 @@ def correct_loop(kf_Tcw, conn_kf, Scw, slot_off, slot_pt, X, kf_center=None, con
     T = _copy(kf_Tcw, np.float64, (-1, 12)); nkf = len(T)
     Cn = None if kf_center is None else _copy(kf_center, np.float64, (-1, 3))
     ck = _c(conn_kf, np.int32).reshape(-1); nconn = len(ck)
-    cr = _opt(conn_rank, np.int32)
+    cr = _flat(conn_rank, np.int32)
     S = _c(Scw, np.float64).reshape(-1)
     so = _c(slot_off, np.int32).reshape(-1); sp = _c(slot_pt, np.int32).reshape(-1)
     Xn = _copy(X, np.float64, (-1, 3)); npts = len(Xn)
-    pb = _opt(pt_bad, np.uint8); pd = _opt(pt_done, np.uint8)
-    oo = _opt(obs_off, np.int32); ok_ = _opt(obs_kf, np.int32); rk = _opt(ref_kf, np.int32); rl = _opt(ref_level, np.int32); sf = _opt(scale_factors, np.float32)
+    pb = _flat(pt_bad, np.uint8); pd = _flat(pt_done, np.uint8)
+    oo = _flat(obs_off, np.int32); ok_ = _flat(obs_kf, np.int32); rk = _flat(ref_kf, np.int32); rl = _flat(ref_level, np.int32); sf = _flat(scale_factors, np.float32)
     nd = all(v is not None for v in (oo, ok_, rk, rl, sf))
     assert nd or all(v is None for v in (oo, ok_, rk, rl, sf)), "the normal / depth inputs are given as a set"
     assert len(S) == 7 and len(so) == nconn + 1 and len(sp) >= so[-1] and (Cn is None or len(Cn) == nkf) and (cr is None or len(cr) == nconn)
@@ -64,10 +51,10 @@ def correct_loop(kf_Tcw, conn_kf, Scw, slot_off, slot_pt, X, kf_center=None, con
         o["nd_written"] = np.zeros(npts, np.uint8) if nd_written is None else nd_written
         for k, dt, n in (("normal", np.float64, 3 * npts), ("min_max", np.float32, 2 * npts), ("nd_written", np.uint8, npts)):
             assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == n, k
-    _lib.check(L.orbl_correct_loop(nkf, _addr(T), _addr(Cn), nconn, _addr(ck), _addr(cr), _addr(S), _addr(so), _addr(sp), npts, _addr(Xn), _addr(pb), _addr(pd),
-                                   _addr(oo), _addr(ok_) if nd else None, _addr(rk), _addr(rl), _addr(sf), len(sf) if nd else 0, _addr(o["corrected"]),
-                                   _addr(o["non_corrected"]), _addr(o["pt_owner"]), _addr(o["normal"]), _addr(o["min_max"]), _addr(o["nd_written"]),
-                                   _addr(o["counts"])), "orbl_correct_loop")
+    _lib.check(L.orbl_correct_loop(nkf, _p(T), _p(Cn), nconn, _p(ck), _p(cr), _p(S), _p(so), _p(sp), npts, _p(Xn), _p(pb), _p(pd),
+                                   _p(oo), _p(ok_) if nd else None, _p(rk), _p(rl), _p(sf), len(sf) if nd else 0, _p(o["corrected"]),
+                                   _p(o["non_corrected"]), _p(o["pt_owner"]), _p(o["normal"]), _p(o["min_max"]), _p(o["nd_written"]),
+                                   _p(o["counts"])), "orbl_correct_loop")
     o.update(kf_Tcw=T, kf_center=Cn, X=Xn)
     return o
 
@@ -84,10 +71,7 @@ def correct_loop_device(kf_Tcw, conn_kf, Scw, slot_off, slot_pt, X, kf_center=No
     nkf, nconn, nslots, npts = kf_Tcw.numel() // 12, conn_kf.numel(), slot_pt.numel(), X.numel() // 3
     nd = obs_off is not None
     nobs = obs_kf.numel() if obs_kf is not None else 0
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_correct_loop_workspace(nkf, nconn, npts, C.byref(nbytes)), "orbl_correct_loop_workspace")
-    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_correct_loop_workspace", nkf, nconn, npts, device=dev, min_bytes=16, reuse=workspace)
     o = {} if out is None else dict(out)
     o.update({k: v for k, v in (("normal", normal), ("min_max", min_max), ("nd_written", nd_written)) if v is not None})
     sizes = [("corrected", torch.float64, 7 * nconn), ("non_corrected", torch.float64, 7 * nconn), ("pt_owner", torch.int32, npts), ("counts", torch.int32, 2),
@@ -98,16 +82,13 @@ def correct_loop_device(kf_Tcw, conn_kf, Scw, slot_off, slot_pt, X, kf_center=No
         if o.get(k) is None:
             o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     for t in (kf_Tcw, kf_center, X):
         assert t is None or (t.is_contiguous() and t.dtype == torch.float64)
-    _lib.check(L.orbl_correct_loop_device(nkf, p(kf_Tcw), p(kf_center), nconn, p(conn_kf), p(conn_rank), p(Scw), nslots, p(slot_off), p(slot_pt), npts, p(X),
-                                          p(pt_bad), p(pt_done), nobs, p(obs_off), p(obs_kf), p(ref_kf), p(ref_level), p(scale_factors),
-                                          scale_factors.numel() if scale_factors is not None else 0, p(o["corrected"]), p(o["non_corrected"]), p(o["pt_owner"]),
-                                          p(o.get("normal")), p(o.get("min_max")), p(o.get("nd_written")), p(o["counts"]), p(o["status"]), p(ws),
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_correct_loop_device")
+    _lib.check(L.orbl_correct_loop_device(nkf, _p(kf_Tcw), _p(kf_center), nconn, _p(conn_kf), _p(conn_rank), _p(Scw), nslots, _p(slot_off), _p(slot_pt), npts, _p(X),
+                                          _p(pt_bad), _p(pt_done), nobs, _p(obs_off), _p(obs_kf), _p(ref_kf), _p(ref_level), _p(scale_factors),
+                                          scale_factors.numel() if scale_factors is not None else 0, _p(o["corrected"]), _p(o["non_corrected"]), _p(o["pt_owner"]),
+                                          _p(o.get("normal")), _p(o.get("min_max")), _p(o.get("nd_written")), _p(o["counts"]), _p(o["status"]), _p(ws),
+                                          _lib.stream()), "orbl_correct_loop_device")
     r = dict(o)
     for k in ("normal", "min_max", "nd_written"):
         r.setdefault(k, None)
@@ -130,7 +111,7 @@ def propagate_global_ba(kf_Tcw, kf_gba_Tcw, kf_in_gba, kf_parent, origin_kf, X, 
     par = _c(kf_parent, np.int32).reshape(-1); org = _c(origin_kf, np.int32).reshape(-1)
     Cn = None if kf_center is None else _copy(kf_center, np.float64, (-1, 3))
     Xn = _copy(X, np.float64, (-1, 3)); npts = len(Xn)
-    pb = _opt(pt_bad, np.uint8); pin = _opt(pt_in_gba, np.uint8)
+    pb = _flat(pt_bad, np.uint8); pin = _flat(pt_in_gba, np.uint8)
     pgx = None if pt_gba_X is None else _c(pt_gba_X, np.float64).reshape(-1, 3)
     ref = _c(pt_ref_kf, np.int32).reshape(-1)
     assert len(G) == nkf and len(F) == nkf and len(par) == nkf and (Cn is None or len(Cn) == nkf) and len(ref) == npts
@@ -138,8 +119,8 @@ def propagate_global_ba(kf_Tcw, kf_gba_Tcw, kf_in_gba, kf_parent, origin_kf, X, 
     bef = np.zeros((nkf, 12)) if kf_bef_Tcw is None else kf_bef_Tcw
     assert bef.dtype == np.float64 and bef.flags.c_contiguous and bef.size == 12 * nkf
     o = dict(kf_bef_Tcw=bef, kf_reached=np.zeros(nkf, np.uint8), pt_moved=np.zeros(npts, np.uint8), counts=np.zeros(4, np.int32))
-    _lib.check(L.orbl_propagate_global_ba(nkf, _addr(T), _addr(G), _addr(F), _addr(par), len(org), _addr(org), _addr(Cn), npts, _addr(Xn), _addr(pb), _addr(pin),
-                                          _addr(pgx), _addr(ref), _addr(bef), _addr(o["kf_reached"]), _addr(o["pt_moved"]), _addr(o["counts"])),
+    _lib.check(L.orbl_propagate_global_ba(nkf, _p(T), _p(G), _p(F), _p(par), len(org), _p(org), _p(Cn), npts, _p(Xn), _p(pb), _p(pin),
+                                          _p(pgx), _p(ref), _p(bef), _p(o["kf_reached"]), _p(o["pt_moved"]), _p(o["counts"])),
                "orbl_propagate_global_ba")
     o.update(kf_Tcw=T, kf_gba_Tcw=G, kf_in_gba=F, kf_center=Cn, X=Xn)
     return o
@@ -154,10 +135,7 @@ def propagate_global_ba_device(kf_Tcw, kf_gba_Tcw, kf_in_gba, kf_parent, origin_
     L = _lib.load()
     dev = kf_Tcw.device
     nkf, npts, n_origin = kf_Tcw.numel() // 12, X.numel() // 3, origin_kf.numel()
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_propagate_global_ba_workspace(nkf, npts, C.byref(nbytes)), "orbl_propagate_global_ba_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_propagate_global_ba_workspace", nkf, npts, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     if kf_bef_Tcw is not None:
         o["kf_bef_Tcw"] = kf_bef_Tcw
@@ -166,14 +144,11 @@ def propagate_global_ba_device(kf_Tcw, kf_gba_Tcw, kf_in_gba, kf_parent, origin_
         if o.get(k) is None:
             o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     for t in (kf_Tcw, kf_gba_Tcw, kf_center, X):
         assert t is None or (t.is_contiguous() and t.dtype == torch.float64)
-    _lib.check(L.orbl_propagate_global_ba_device(nkf, p(kf_Tcw), p(kf_gba_Tcw), p(kf_in_gba), p(kf_parent), n_origin, p(origin_kf), p(kf_center), npts, p(X),
-                                                 p(pt_bad), p(pt_in_gba), p(pt_gba_X), p(pt_ref_kf), p(o["kf_bef_Tcw"]), p(o["kf_reached"]), p(o["pt_moved"]),
-                                                 p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+    _lib.check(L.orbl_propagate_global_ba_device(nkf, _p(kf_Tcw), _p(kf_gba_Tcw), _p(kf_in_gba), _p(kf_parent), n_origin, _p(origin_kf), _p(kf_center), npts, _p(X),
+                                                 _p(pt_bad), _p(pt_in_gba), _p(pt_gba_X), _p(pt_ref_kf), _p(o["kf_bef_Tcw"]), _p(o["kf_reached"]), _p(o["pt_moved"]),
+                                                 _p(o["counts"]), _p(o["status"]), _p(ws), _lib.stream()),
                "orbl_propagate_global_ba_device")
     r = dict(o)
     r.update(kf_Tcw=kf_Tcw, kf_gba_Tcw=kf_gba_Tcw, kf_in_gba=kf_in_gba, kf_center=kf_center, X=X, _workspace=ws)
@@ -189,10 +164,6 @@ _EG_OUT = (("vtx_kf", np.int32, 1, 0), ("lie7", np.float64, 7, 0), ("vtx_fixed",
            ("edge_Sji", np.float64, 7, 1), ("edge_kind", np.uint8, 1, 1))                                # (name, dtype, width, which capacity)
 _EG_ORDER = ("vtx_kf", "kf_vtx", "lie7", "vtx_fixed", "edge_j", "edge_i", "edge_Sji", "edge_kind")        # (the order of the C arguments)
 _EA_ND = ("obs_off", "obs_kf", "ref_level", "scale_factors")
-
-
-def _flat(a, dt):
-    return None if a is None else _c(a, dt).reshape(-1)
 
 
 def _eg_caps(t, nkf, caps):
@@ -235,12 +206,9 @@ def essential_graph_assemble(loop_kf, cur_kf, tab, min_weight=100, caps=None, ou
         o.setdefault(k, np.zeros(w * cap[c], dt))
         assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * cap[c], k
     o.setdefault("kf_vtx", np.zeros(nkf, np.int32)); o.setdefault("counts", np.zeros(4, np.int32))
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
-    rc = L.orbl_essential_graph_assemble(nkf, *[a(t[k]) for k, _ in _EG_KF], *[_addr(t[k]) if k.endswith("_off") else a(t[k]) for row in _EG_CSR for k in row], nconn,
-                                         a(t["conn_group_kf"]), a(t["corrected"]), a(t["non_corrected"]), ntgt, a(t["tgt_kf"]), _addr(t["link_off"]) if ntgt else None,
-                                         a(t["link_kf"]), int(loop_kf), int(cur_kf), int(min_weight), cap[0], cap[1], _addr(o["counts"]), *[a(o[k]) for k in _EG_ORDER])
+    rc = L.orbl_essential_graph_assemble(nkf, *[_pn(t[k]) for k, _ in _EG_KF], *[_p(t[k]) if k.endswith("_off") else _pn(t[k]) for row in _EG_CSR for k in row], nconn,
+                                         _pn(t["conn_group_kf"]), _pn(t["corrected"]), _pn(t["non_corrected"]), ntgt, _pn(t["tgt_kf"]), _p(t["link_off"]) if ntgt else None,
+                                         _pn(t["link_kf"]), int(loop_kf), int(cur_kf), int(min_weight), cap[0], cap[1], _p(o["counts"]), *[_pn(o[k]) for k in _EG_ORDER])
     if rc == ECAP and not check:
         return dict(rc=rc, counts=o["counts"])
     _lib.check(rc, "orbl_essential_graph_assemble")
@@ -262,10 +230,7 @@ def essential_graph_assemble_device(loop_kf, cur_kf, tab, min_weight=100, caps=N
     nkf = tab["kf_id"].numel()
     n = lambda k: 0 if g(k) is None else g(k).numel()
     cap = _eg_caps(tab, nkf, caps)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_essential_graph_assemble_workspace(nkf, C.byref(nbytes)), "orbl_essential_graph_assemble_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_essential_graph_assemble_workspace", nkf, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     tdt = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}
     sizes = [(k, tdt[dt], w * cap[c]) for k, dt, w, c in _EG_OUT] + [("kf_vtx", torch.int32, nkf), ("counts", torch.int32, 4), ("status", torch.int32, 1)]
@@ -273,17 +238,14 @@ def essential_graph_assemble_device(loop_kf, cur_kf, tab, min_weight=100, caps=N
         if o.get(k) is None:
             o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
     csr = []
     for row in _EG_CSR:
-        csr += [n(row[1]), C.c_void_p(tab[row[0]].data_ptr())] + [p(g(k)) for k in row[1:]]
+        csr += [n(row[1]), _p(tab[row[0]])] + [_pn(g(k)) for k in row[1:]]
     ntgt = n("tgt_kf")
-    _lib.check(L.orbl_essential_graph_assemble_device(nkf, *[p(g(k)) for k, _ in _EG_KF], *csr, n("conn_group_kf"), p(g("conn_group_kf")), p(g("corrected")), p(g("non_corrected")),
-                                                      ntgt, p(g("tgt_kf")), n("link_kf"), C.c_void_p(tab["link_off"].data_ptr()) if ntgt else None, p(g("link_kf")), int(loop_kf),
-                                                      int(cur_kf), int(min_weight), cap[0], cap[1], p(o["counts"]), *[p(o[k]) for k in _EG_ORDER], p(o["status"]), p(ws),
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_essential_graph_assemble_device")
+    _lib.check(L.orbl_essential_graph_assemble_device(nkf, *[_pn(g(k)) for k, _ in _EG_KF], *csr, n("conn_group_kf"), _pn(g("conn_group_kf")), _pn(g("corrected")),
+                                                      _pn(g("non_corrected")), ntgt, _pn(g("tgt_kf")), n("link_kf"), _p(tab["link_off"]) if ntgt else None, _pn(g("link_kf")), int(loop_kf),
+                                                      int(cur_kf), int(min_weight), cap[0], cap[1], _pn(o["counts"]), *[_pn(o[k]) for k in _EG_ORDER], _pn(o["status"]), _pn(ws),
+                                                      _lib.stream()), "orbl_essential_graph_assemble_device")
     r = dict(o)
     r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
     return r
@@ -322,12 +284,9 @@ def essential_graph_apply(vtx_kf, lie_orig, lie_opt, tab, normals=True, out=None
             assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == m, k
     else:
         o.update(normal=None, min_max=None, nd_written=None)
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
-    nda = (lambda x: None if x is None else _addr(x)) if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
-    _lib.check(L.orbl_essential_graph_apply(nv, a(vk), a(lo), a(ln), nkf, a(T), a(Cn), npts, a(Xn), a(pb), a(pd), a(pc), a(pr), *[nda(v) for v in nd], n_levels,
-                                            nda(o["normal"]), nda(o["min_max"]), nda(o["nd_written"]), a(o["pt_moved"]), _addr(o["counts"])), "orbl_essential_graph_apply")
+    nda = _p if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
+    _lib.check(L.orbl_essential_graph_apply(nv, _pn(vk), _pn(lo), _pn(ln), nkf, _pn(T), _pn(Cn), npts, _pn(Xn), _pn(pb), _pn(pd), _pn(pc), _pn(pr), *[nda(v) for v in nd], n_levels,
+                                            nda(o["normal"]), nda(o["min_max"]), nda(o["nd_written"]), _pn(o["pt_moved"]), _p(o["counts"])), "orbl_essential_graph_apply")
     r = dict(o)
     r.update(kf_Tcw=T, kf_center=Cn, X=Xn)
     return r
@@ -346,10 +305,7 @@ def essential_graph_apply_device(vtx_kf, lie_orig, lie_opt, tab, normals=True, o
     nv = vtx_kf.numel() if n_vtx is None else int(n_vtx)
     assert vtx_kf.numel() >= nv and lie_orig.numel() >= 7 * nv and lie_opt.numel() >= 7 * nv
     nobs = g("obs_kf").numel() if (normals and g("obs_kf") is not None) else 0
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_essential_graph_apply_workspace(nkf, nv, C.byref(nbytes)), "orbl_essential_graph_apply_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_essential_graph_apply_workspace", nkf, nv, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     sizes = [("pt_moved", torch.uint8, npts), ("counts", torch.int32, 2), ("status", torch.int32, 1)]
     if normals:
@@ -358,21 +314,15 @@ def essential_graph_apply_device(vtx_kf, lie_orig, lie_opt, tab, normals=True, o
         if o.get(k) is None:
             o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-
-    def q(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     for k in ("kf_Tcw", "kf_center", "X"):
         assert g(k) is None or (g(k).is_contiguous() and g(k).dtype == torch.float64), k
-    nd = [q(g(k)) if (normals and npts) else None for k in _EA_ND]
+    nd = [_p(g(k)) if (normals and npts) else None for k in _EA_ND]
     sf = g("scale_factors")
-    _lib.check(L.orbl_essential_graph_apply_device(nv, p(vtx_kf), p(lie_orig), p(lie_opt), nkf, p(g("kf_Tcw")), p(g("kf_center")), npts, p(g("X")), p(g("pt_bad")), p(g("pt_done")),
-                                                   p(g("pt_corr_ref")), p(g("pt_ref_kf")), nobs, nd[0], nd[1] if nobs else None, nd[2], nd[3],
+    _lib.check(L.orbl_essential_graph_apply_device(nv, _pn(vtx_kf), _pn(lie_orig), _pn(lie_opt), nkf, _pn(g("kf_Tcw")), _pn(g("kf_center")), npts, _pn(g("X")), _pn(g("pt_bad")),
+                                                   _pn(g("pt_done")), _pn(g("pt_corr_ref")), _pn(g("pt_ref_kf")), nobs, nd[0], nd[1] if nobs else None, nd[2], nd[3],
                                                    sf.numel() if (normals and sf is not None) else 0,
-                                                   *[q(o.get(k)) if (normals and npts) else None for k in ("normal", "min_max", "nd_written")], p(o["pt_moved"]), p(o["counts"]),
-                                                   p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_essential_graph_apply_device")
+                                                   *[_p(o.get(k)) if (normals and npts) else None for k in ("normal", "min_max", "nd_written")], _pn(o["pt_moved"]), _pn(o["counts"]),
+                                                   _pn(o["status"]), _pn(ws), _lib.stream()), "orbl_essential_graph_apply_device")
     r = dict(o)
     for k in ("normal", "min_max", "nd_written"):
         r.setdefault(k, None)
@@ -458,11 +408,8 @@ def global_ba_assemble(tab, ba_kf=None, ba_pt=None, is_robust=True, caps=None, o
         o.setdefault(k, np.zeros(w * dims[c], dt))
         assert o[k].dtype == dt and o[k].flags.c_contiguous and o[k].size == w * dims[c], k
     o.setdefault("counts", np.zeros(3, np.int32))
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
-    rc = L.orbl_global_ba_assemble(nbk, a(bk), nbp, a(bp), nkf, *[a(t[k]) for k, _ in _GA_KF], npts, *[a(t[k]) for k, _ in _GA_PT], len(t["inv_level_sigma2"]),
-                                   int(bool(is_robust)), cap[0], cap[1], cap[2], _addr(o["counts"]), *[a(o[k]) for k, _, _, _ in _GA_OUT])
+    rc = L.orbl_global_ba_assemble(nbk, _pn(bk), nbp, _pn(bp), nkf, *[_pn(t[k]) for k, _ in _GA_KF], npts, *[_pn(t[k]) for k, _ in _GA_PT], len(t["inv_level_sigma2"]),
+                                   int(bool(is_robust)), cap[0], cap[1], cap[2], _p(o["counts"]), *[_pn(o[k]) for k, _, _, _ in _GA_OUT])
     if rc == ECAP and not check:
         return dict(rc=rc, counts=o["counts"])
     _lib.check(rc, "orbl_global_ba_assemble")
@@ -482,10 +429,7 @@ def global_ba_assemble_device(tab, ba_kf=None, ba_pt=None, is_robust=True, caps=
     g = tab.get
     dev = tab["kf_id"].device
     nkf, npts, nobs, nbk, nbp, cap = _ga_sizes(tab, ba_kf, ba_pt, caps)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_global_ba_assemble_workspace(nkf, npts, nbk, nbp, C.byref(nbytes)), "orbl_global_ba_assemble_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_global_ba_assemble_workspace", nkf, npts, nbk, nbp, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     tdt = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}
     dims = {-1: nkf, -2: npts, 0: cap[0], 1: cap[1], 2: cap[2]}
@@ -494,13 +438,10 @@ def global_ba_assemble_device(tab, ba_kf=None, ba_pt=None, is_robust=True, caps=
         if o.get(k) is None:
             o[k] = torch.empty(max(m, 1), dtype=dt, device=dev)[:m]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-    _lib.check(L.orbl_global_ba_assemble_device(nbk, p(ba_kf), nbp, p(ba_pt), nkf, *[p(g(k)) for k, _ in _GA_KF], npts, p(g("X")), p(g("pt_bad")), nobs,
-                                                *[p(g(k)) for k, _ in _GA_PT[2:]], g("inv_level_sigma2").numel(), int(bool(is_robust)), cap[0], cap[1], cap[2],
-                                                p(o["counts"]), *[p(o[k]) for k, _, _, _ in _GA_OUT], p(o["status"]), p(ws),
-                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_global_ba_assemble_device")
+    _lib.check(L.orbl_global_ba_assemble_device(nbk, _pn(ba_kf), nbp, _pn(ba_pt), nkf, *[_pn(g(k)) for k, _ in _GA_KF], npts, _pn(g("X")), _pn(g("pt_bad")), nobs,
+                                                *[_pn(g(k)) for k, _ in _GA_PT[2:]], g("inv_level_sigma2").numel(), int(bool(is_robust)), cap[0], cap[1], cap[2],
+                                                _pn(o["counts"]), *[_pn(o[k]) for k, _, _, _ in _GA_OUT], _pn(o["status"]), _pn(ws),
+                                                _lib.stream()), "orbl_global_ba_assemble_device")
     r = dict(o)
     r["_workspace"] = ws                                         # (kept alive until the caller synchronises)
     return r
@@ -548,12 +489,9 @@ def global_ba_apply(cam_kf, gpt_pt, poses7, pts3, tab, stage=0, normals=True, ou
         gX = np.zeros((npts, 3)) if tab.get("pt_gba_X") is None else _copy(tab["pt_gba_X"], np.float64, (-1, 3))
         kin, pin = np.zeros(nkf, np.uint8), np.zeros(npts, np.uint8)
         assert len(gT) == nkf and len(gX) == npts
-
-    def a(x):
-        return None if x is None or x.size == 0 else _addr(x)
-    nda = (lambda x: None if x is None else _addr(x)) if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
-    _lib.check(L.orbl_global_ba_apply(len(ck), a(ck), a(p7), len(gp), a(gp), a(p3), int(stage), nkf, a(kb), a(T), a(Cn), npts, a(Xn), a(pb), a(gT), a(kin), a(gX), a(pin),
-                                      *[nda(v) for v in nd], n_levels, *[nda(v) for v in ndo], _addr(o["counts"])), "orbl_global_ba_apply")
+    nda = _p if npts else (lambda x: None)      # (no points: the set has no rows and is left out)
+    _lib.check(L.orbl_global_ba_apply(len(ck), _pn(ck), _pn(p7), len(gp), _pn(gp), _pn(p3), int(stage), nkf, _pn(kb), _pn(T), _pn(Cn), npts, _pn(Xn), _pn(pb), _pn(gT), _pn(kin),
+                                      _pn(gX), _pn(pin), *[nda(v) for v in nd], n_levels, *[nda(v) for v in ndo], _p(o["counts"])), "orbl_global_ba_apply")
     r = dict(o)
     if stage == 0:
         r.update(kf_Tcw=T, kf_center=Cn, X=Xn)
@@ -576,10 +514,7 @@ def global_ba_apply_device(cam_kf, gpt_pt, poses7, pts3, tab, stage=0, normals=T
     assert cam_kf.numel() >= ncam and poses7.numel() >= 7 * ncam and gpt_pt.numel() >= npb and pts3.numel() >= 3 * npb
     run_nd = bool(normals) and stage == 0 and npts > 0
     nobs = g("obs_kf").numel() if (run_nd and g("obs_kf") is not None) else 0
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbl_global_ba_apply_workspace(nkf, npts, C.byref(nbytes)), "orbl_global_ba_apply_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if workspace is None else workspace
-    assert ws.numel() >= nbytes.value
+    ws = _lib.workspace("orbl_global_ba_apply_workspace", nkf, npts, device=dev, reuse=workspace)
     o = {} if out is None else dict(out)
     sizes = [("counts", torch.int32, 3), ("status", torch.int32, 1)]
     if run_nd:
@@ -592,24 +527,18 @@ def global_ba_apply_device(cam_kf, gpt_pt, poses7, pts3, tab, stage=0, normals=T
         if o.get(k) is None:
             o[k] = torch.zeros(max(m, 1), dtype=dt, device=dev)[:m]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == m, k
-
-    def p(t):
-        return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-
-    def q(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
     for k in ("kf_Tcw", "kf_center", "X"):
         assert g(k) is None or (g(k).is_contiguous() and g(k).dtype == torch.float64), k
-    nd = [q(g(k)) if run_nd else None for k in _GP_ND]
+    nd = [_p(g(k)) if run_nd else None for k in _GP_ND]
     if not nobs:
         nd[2] = None
     sf = g("scale_factors")
     s0 = stage == 0
-    _lib.check(L.orbl_global_ba_apply_device(ncam, p(cam_kf), p(poses7), npb, p(gpt_pt), p(pts3), int(stage), nkf, p(g("kf_bad")), p(g("kf_Tcw")) if s0 else None,
-                                             p(g("kf_center")) if s0 else None, npts, p(g("X")) if s0 else None, p(g("pt_bad")),
-                                             *[p(o.get(k)) if stage else None for k in ("kf_gba_Tcw", "kf_in_gba", "pt_gba_X", "pt_in_gba")], nd[0], nobs, nd[1], nd[2], nd[3], nd[4],
-                                             sf.numel() if (run_nd and sf is not None) else 0, *[q(o.get(k)) if run_nd else None for k in ("normal", "min_max", "nd_written")],
-                                             p(o["counts"]), p(o["status"]), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbl_global_ba_apply_device")
+    _lib.check(L.orbl_global_ba_apply_device(ncam, _pn(cam_kf), _pn(poses7), npb, _pn(gpt_pt), _pn(pts3), int(stage), nkf, _pn(g("kf_bad")), _pn(g("kf_Tcw")) if s0 else None,
+                                             _pn(g("kf_center")) if s0 else None, npts, _pn(g("X")) if s0 else None, _pn(g("pt_bad")),
+                                             *[_pn(o.get(k)) if stage else None for k in ("kf_gba_Tcw", "kf_in_gba", "pt_gba_X", "pt_in_gba")], nd[0], nobs, nd[1], nd[2], nd[3], nd[4],
+                                             sf.numel() if (run_nd and sf is not None) else 0, *[_p(o.get(k)) if run_nd else None for k in ("normal", "min_max", "nd_written")],
+                                             _pn(o["counts"]), _pn(o["status"]), _pn(ws), _lib.stream()), "orbl_global_ba_apply_device")
     r = dict(o)
     for k in ("normal", "min_max", "nd_written"):
         r.setdefault(k, None)

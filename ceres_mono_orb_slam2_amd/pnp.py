@@ -114,19 +114,14 @@ def iterate_batch_device(p3d, p2d, max_err, off, K4, min_inliers, n_sets, sets, 
     int32, sets[n_candidates, iterations, 4] int32, the state best_count[n_candidates] int32 / best_mask[n_total] uint8 /
     best_Tcw[n_candidates, 4, 4] float64 (in/out), result[n_candidates * sizeof(orbt_pnp_result)] uint8 and inliers[n_total] uint8
     (out).  Returns the workspace tensor (keep it alive until the stream is synchronised)."""
-    import torch
     L = _lib.load()
     nc = off.numel() - 1
     iterations = sets.shape[1]
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbt_pnp_iterate_workspace(nc, p3d.shape[0], int(iterations), C.byref(nbytes)), "orbt_pnp_iterate_workspace")
-    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=p3d.device)
-
-    def p(t):
-        return C.c_void_p(t.data_ptr())
+    ws = _lib.workspace("orbt_pnp_iterate_workspace", nc, p3d.shape[0], int(iterations), device=p3d.device, min_bytes=16)
+    p = _lib.ptr
     _lib.check(L.orbt_pnp_iterate_batch_device(nc, p(p3d), p(p2d), p(max_err), p(off), p3d.shape[0], p(K4), p(min_inliers), p(n_sets), int(iterations),
                                                p(sets), p(best_count), p(best_mask), p(best_Tcw), p(result), p(inliers), p(ws),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbt_pnp_iterate_batch_device")
+                                               _lib.stream()), "orbt_pnp_iterate_batch_device")
     return ws
 
 

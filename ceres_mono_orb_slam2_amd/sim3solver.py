@@ -123,19 +123,14 @@ def iterate_batch_device(X1c, X2c, max_err1, max_err2, off, K1, K2, fix_scale, m
     uint8 / best_R[n_candidates, 3, 3] / best_t[n_candidates, 3] float64 / best_scale[n_candidates] float32 (in/out),
     result[n_candidates * sizeof(orbt_sim3_result)] uint8 and inliers[n_total] uint8 (out).  Returns the workspace tensor (keep it alive
     until the stream is synchronised)."""
-    import torch
     L = _lib.load()
     nc = off.numel() - 1
     iterations = sets.shape[1]
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbt_sim3_iterate_workspace(nc, X1c.shape[0], int(iterations), C.byref(nbytes)), "orbt_sim3_iterate_workspace")
-    ws = torch.empty(max(nbytes.value, 16), dtype=torch.uint8, device=X1c.device)
-
-    def p(t):
-        return C.c_void_p(t.data_ptr())
+    ws = _lib.workspace("orbt_sim3_iterate_workspace", nc, X1c.shape[0], int(iterations), device=X1c.device, min_bytes=16)
+    p = _lib.ptr
     _lib.check(L.orbt_sim3_iterate_batch_device(nc, p(X1c), p(X2c), p(max_err1), p(max_err2), p(off), X1c.shape[0], p(K1), p(K2), p(fix_scale),
                                                 p(min_inliers), p(n_sets), int(iterations), p(sets), p(best_count), p(best_mask), p(best_R), p(best_t),
-                                                p(best_scale), p(result), p(inliers), p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                p(best_scale), p(result), p(inliers), p(ws), _lib.stream()),
                "orbt_sim3_iterate_batch_device")
     return ws
 

@@ -227,9 +227,6 @@ def relocalization_search_by_bow(extractor, vocabulary, image, K4, bounds, candi
         img = _c(image, np.uint8); h, w = img.shape; ip, st = _addr(img), img.strides[0]
     else:
         img, h, w, ip, st = None, 0, 0, None, 0
-    L.orbt_relocalization_search_by_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
-                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
-                                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     with (_extractor_lock(extractor) if img is not None else contextlib.nullcontext()):
         _lib.check(L.orbt_relocalization_search_by_bow(extractor._h, vocabulary._h, ip, w, h, st, _addr(K4), _addr(bounds), C.cast(cs, C.c_void_p), nc, float(nnratio),
                                                        int(bool(check_ori)), _addr(kps), _addr(desc), cap, _addr(bw), _addr(bv), C.byref(nw), _addr(on), _addr(oo), _addr(oi),
@@ -390,9 +387,7 @@ def update_local_map_device(T, cap_kf, cap_pt, max_local_slots=None, packed=True
     npts, nkf = T["pt_bad"].numel(), T["kf_bad"].numel()
     nobs, ncov, nchild, nslots = T["obs_kf"].numel(), T["cov_kf"].numel(), T["child_kf"].numel(), T["kf_slot_pt"].numel()
     mls = nslots if max_local_slots is None else int(max_local_slots)
-    nbytes = C.c_size_t(0)
-    _lib.check(L.orbt_update_local_map_workspace(nkf, npts, mls, C.byref(nbytes)), "orbt_update_local_map_workspace")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("orbt_update_local_map_workspace", nkf, npts, mls, device=dev)
     o = {} if out is None else out
     tdt = {np.float64: torch.float64, np.float32: torch.float32, np.uint8: torch.uint8}
     want = [("frame_pt_out", torch.int32, n_kp), ("local_kf", torch.int32, cap_kf), ("local_pt", torch.int32, cap_pt), ("counts", torch.int32, 4)]
@@ -405,16 +400,14 @@ def update_local_map_device(T, cap_kf, cap_pt, max_local_slots=None, packed=True
             o[k] = torch.empty(max(n, 4), dtype=dt, device=dev)[:n]
         assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
     status = torch.empty(1, dtype=torch.int32, device=dev)
-
-    def p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
+    p = _lib.ptr
     g = T.get
     _lib.check(L.orbt_update_local_map_device(
         n_kp, p(g("frame_pt")), n_seen, p(g("seen_pt")), n_prev, p(g("prev_local_kf")), npts, p(g("pt_bad")), p(g("pt_nobs")), nobs, p(g("obs_off")), p(g("obs_kf")),
         p(g("pt_Xw")), p(g("pt_normal")), p(g("pt_min_dist")), p(g("pt_max_dist")), p(g("pt_desc")), nkf, p(g("kf_bad")), p(g("kf_rank")), p(g("kf_parent")), ncov,
         p(g("cov_off")), p(g("cov_kf")), nchild, p(g("child_off")), p(g("child_kf")), nslots, p(g("kf_slot_off")), p(g("kf_slot_pt")), mls, int(cap_kf), int(cap_pt),
-        p(o["frame_pt_out"]), p(o["local_kf"]), p(o["local_pt"]), C.c_void_p(o["counts"].data_ptr()), p(o.get("votes")), *[p(o.get(k)) for k, _, _ in _PACKED],
-        C.c_void_p(status.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "orbt_update_local_map_device")
+        p(o["frame_pt_out"]), p(o["local_kf"]), p(o["local_pt"]), p(o["counts"]), p(o.get("votes")), *[p(o.get(k)) for k, _, _ in _PACKED],
+        p(status), p(ws), _lib.stream()), "orbt_update_local_map_device")
     r = dict(o)
     for k, _, w in _PACKED:
         if r.get(k) is not None and w > 1:
@@ -428,7 +421,6 @@ def track_local_map_device(extractor, K4, bounds, Tcw, log_scale_factor, packed,
     mp_Xw, mp_normal, mp_min_dist, mp_max_dist, mp_desc, mp_state, slot_Xw, slot_state) - orbt_track_local_map_device.  n_mp: the number
     of rows to run over, at least the count of local map points (the capacity is always right: padding rows have mp_state 0).  The
     arrays are taken as the current torch stream leaves them.  Returns what track_local_map returns."""
-    import torch
     L = _lib.load()
     K4 = _c(K4, np.float32); bounds = _c(bounds, np.float32)
     T = np.ascontiguousarray(np.asarray(Tcw, np.float64).reshape(-1)[:12])
@@ -437,10 +429,10 @@ def track_local_map_device(extractor, K4, bounds, Tcw, log_scale_factor, packed,
     in_view = np.zeros(max(n, 1), np.uint8); match = np.full(max(n, 1), -1, np.int32)
     owner = np.full(max(nk, 1), -1, np.int32); outl = np.zeros(max(nk, 1), np.uint8)
     res = TrackResult()
-    p = lambda k: C.c_void_p(packed[k].data_ptr())                                  # noqa: E731
+    p = lambda k: _lib.ptr(packed[k])                                               # noqa: E731
     _lib.check(L.orbt_track_local_map_device(extractor._h, _addr(K4), _addr(bounds), _addr(T), float(log_scale_factor), p("mp_Xw"), p("mp_normal"), p("mp_min_dist"),
                                              p("mp_max_dist"), p("mp_desc"), p("mp_state"), n, p("slot_Xw"), p("slot_state"), nk, float(th), float(nnratio),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream), _addr(in_view), _addr(match), _addr(owner), _addr(outl), C.byref(res)),
+                                             _lib.stream(), _addr(in_view), _addr(match), _addr(owner), _addr(outl), C.byref(res)),
                "orbt_track_local_map_device")
     return dict(in_view=in_view[:n].view(np.bool_), match=match[:n], owner=owner[:nk], outlier=outl[:nk].view(np.bool_), pose7=np.array(res.pose7[:], np.float64),
                 nmatches=res.nmatches, n_inliers=res.n_inliers, n_correspondences=res.n_correspondences, n_in_view=res.reserved, greedy_rounds=res.greedy_rounds)

@@ -128,10 +128,7 @@ def lib():
     import __graft_entry__ as g
     g.build_hip()
     from ceres_mono_orb_slam2_amd import _lib
-    L = _lib.load()
-    vp, i32 = C.c_void_p, C.c_int
-    L.orbl_update_map_points.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    L.orbl_update_map_points_device.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    _lib.load()
     return _lib
 
 
