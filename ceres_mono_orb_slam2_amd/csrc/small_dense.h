@@ -4,6 +4,11 @@
 // squares), and the two-sided Jacobi for a symmetric 4 x 4 with signed eigenvalues (i_jacobi_sym4: Horn's N).
 // The summation order of every function is fixed here and restated in tests/npinit.py (jacobi, svd3, inv3), tests/nppnp.py and
 // tests/npsim3solver.py (jacobi_sym4).
+// Domain: every comparison below is homogeneous in A, so each routine is exact under power-of-two scaling (S, U or the eigenvalues
+// scale, V keeps its bits), and the routines are specified for ||A||_F within 2^+-200.  Outside that range the skip test
+// |gamma| <= 1e-15 sqrt(alpha beta) overflows or underflows: a 3 x 3 with singular values 3, 2, 1 times 1e150 makes alpha beta = inf, no
+// pair is rotated and i_svd3 returns 2.73, 1.83, 1.79.  No caller comes near (normalised coordinates, metric covariances).
+// tests/test_small_dense_reference.py and tests/test_gpu_small_dense.py pin all of it to an mpmath reference.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -146,6 +151,11 @@ __device__ __forceinline__ double i_sel3(const double (&B)[3][3], int i, int o) 
 
 // 3 x 3 SVD A = U diag(S) V^T, S descending (stable on ties), U's third column = u0 x u1 (so it is defined for rank 2), v2 signed
 // so that A v2 = S2 u2 holds.  U, V row-major with the singular vectors as columns.
+// For every finite A in the scale domain U and V are orthonormal and A = U diag(S) V^T to rounding, whatever the rank: a column with
+// S1 <= 2e-14 S0 supplies no left vector (it is rounding noise, or 0 / 0).  2e-14 S0 covers every column the null-column rule of
+// i_jacobi may have left unrotated (norm <= 1e-14 ||A||_F <= 1.74e-14 S0); dropping it moves U diag(S) V^T by at most 2e-14 S0.
+// u1 is then u0's complement along the coordinate axis least aligned with u0 (first on ties), normalised; S0 == 0 gives U = I.
+// S and the directions of V are never touched by this rule, and nothing changes where S1 > 2e-14 S0.
 __device__ inline void i_svd3(const double* A, double* U, double* S, double* V) {
   double B[3][3], W[3][3];
 #pragma unroll
@@ -171,8 +181,23 @@ __device__ inline void i_svd3(const double* A, double* U, double* S, double* V) 
   double u0[3], u1[3], u2[3], b2[3];
 #pragma unroll
   for (int i = 0; i < 3; i++) { u0[i] = i_sel3(B, i, o0) / S[0]; u1[i] = i_sel3(B, i, o1) / S[1]; b2[i] = i_sel3(B, i, o2); }
+  if (!(S[1] > 2e-14 * S[0])) {                                  // rank <= 1 to working precision (the comment above)
+    if (!(S[0] > 0.0)) { u0[0] = 1.0; u0[1] = 0.0; u0[2] = 0.0; }
+    const double a0 = fabs(u0[0]), a1 = fabs(u0[1]), a2 = fabs(u0[2]);
+    const int k = (a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);
+    const double uk = k == 0 ? u0[0] : k == 1 ? u0[1] : u0[2];
+    double w[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) w[i] = (i == k ? 1.0 : 0.0) - uk * u0[i];
+    const double wn = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) u1[i] = w[i] / wn;
+  }
   u2[0] = u0[1] * u1[2] - u0[2] * u1[1]; u2[1] = u0[2] * u1[0] - u0[0] * u1[2]; u2[2] = u0[0] * u1[1] - u0[1] * u1[0];
-  const double sg = ((b2[0] * u2[0] + b2[1] * u2[1]) + b2[2] * u2[2]) < 0 ? -1.0 : 1.0;
+  // b2 . u2 == 0 exactly (a zero third column: exactly planar points) leaves the sign free: V is then made proper like U (W is a product of
+  // rotations, so det V is the parity of the sort), and U V^T is a rotation whatever order the columns came out in
+  const double d2 = (b2[0] * u2[0] + b2[1] * u2[1]) + b2[2] * u2[2];
+  const double sg = d2 < 0 ? -1.0 : d2 > 0 ? 1.0 : ((o1 - o0 + 3) % 3 == 1 ? 1.0 : -1.0);
 #pragma unroll
   for (int i = 0; i < 3; i++) {
     U[3 * i] = u0[i]; U[3 * i + 1] = u1[i]; U[3 * i + 2] = u2[i];

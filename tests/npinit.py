@@ -143,9 +143,20 @@ def svd3(A):
     col = lambda M, k: M[r, :, o[:, k]]                                    # noqa: E731  (B, 3)
     with np.errstate(all="ignore"):
         u0 = col(Bm, 0) / S[:, 0:1]; u1 = col(Bm, 1) / S[:, 1:2]
+        # rank <= 1 to working precision: column 1 supplies no left vector; u1 = u0's complement along the axis least aligned with u0
+        low = ~(S[:, 1] > 2e-14 * S[:, 0])
+        e0 = np.zeros((nb, 3)); e0[:, 0] = 1.0
+        u0 = np.where((low & ~(S[:, 0] > 0.0))[:, None], e0, u0)
+        a = np.abs(u0)
+        k = np.where((a[:, 0] <= a[:, 1]) & (a[:, 0] <= a[:, 2]), 0, np.where(a[:, 1] <= a[:, 2], 1, 2))
+        w = np.eye(3)[k] - u0[r, k][:, None] * u0
+        wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
+        u1 = np.where(low[:, None], w / wn[:, None], u1)
     b2 = col(Bm, 2)
     u2 = np.stack([u0[:, 1] * u1[:, 2] - u0[:, 2] * u1[:, 1], u0[:, 2] * u1[:, 0] - u0[:, 0] * u1[:, 2], u0[:, 0] * u1[:, 1] - u0[:, 1] * u1[:, 0]], 1)
-    sg = np.where(((b2[:, 0] * u2[:, 0] + b2[:, 1] * u2[:, 1]) + b2[:, 2] * u2[:, 2]) < 0, -1.0, 1.0)
+    d2 = (b2[:, 0] * u2[:, 0] + b2[:, 1] * u2[:, 1]) + b2[:, 2] * u2[:, 2]
+    # d2 == 0 exactly (a zero third column) leaves the sign free: V is made proper like U (det V = the parity of the sort)
+    sg = np.where(d2 < 0, -1.0, np.where(d2 > 0, 1.0, np.where((o[:, 1] - o[:, 0] + 3) % 3 == 1, 1.0, -1.0)))
     U = np.stack([u0, u1, u2], 2)
     V = np.stack([col(W, 0), col(W, 1), sg[:, None] * col(W, 2)], 2)
     return U, S, V

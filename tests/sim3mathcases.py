@@ -317,10 +317,10 @@ def unpack(blob):
     return dev, host
 
 
-def build_probe(workdir):
+def build_probe(workdir, src=PROBE_SRC):
     import subprocess
-    exe = os.path.join(str(workdir), "sim3_math_probe")
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + PROBE_FLAGS + ["-o", exe, PROBE_SRC])
+    exe = os.path.join(str(workdir), os.path.splitext(os.path.basename(src))[0])
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + PROBE_FLAGS + ["-o", exe, src])
     return exe
 
 
