@@ -1975,6 +1975,121 @@ struct FrameOpsT {
     return counts[0];
   }
 
+  // The front of LoopClosing::ComputeSim3, src/LoopClosing.cc:250-277, for every candidate in ONE library call (orbl_loop_sim3_candidates):
+  //     std::vector<std::vector<MapPoint*> > map_point_matches_vector;
+  //     FrameOpsHip::LoopSim3Data<MapPoint> data;
+  //     int n_candidates = FrameOpsHip::LoopSim3Candidates(current_keyframe_, enough_consistent_candidates_, map_point_matches_vector, &data);
+  // matches_out[i] is the vector of :262 (for a bad candidate it stays empty, as the reference leaves it), data->discarded[i] the flag of
+  // :258 / :266, and rows [off[i], off[i + 1]) of data hold what Sim3Solver's constructor builds for candidate i (src/Sim3Solver.cc:73-109)
+  // in the layout orbt_sim3_iterate_batch_device and Sim3SolverT take.  The current keyframe, the candidates, the points in their slots and
+  // those points' observations of these keyframes are flattened; level_sigma2s_ is the current keyframe's (every keyframe copies the one
+  // extractor's).  SetNotErase (:255) stays with the caller.  Returns the number of candidates kept.
+  template <class MP> struct LoopSim3Data {
+    std::vector<bool> discarded; std::vector<int> nmatches;
+    std::vector<int32_t> off, matched_indices_1;                      // rows per candidate (CSR); matched_indices_1_ per row
+    std::vector<double> X1c, X2c;                                     // X3Dsc1_ / X3Dsc2_ [rows][3]
+    std::vector<float> max_err1, max_err2, K1, K2;                    // max_errors_1_ / _2_ [rows]; (fx, fy, cx, cy) [candidates][4]
+    std::vector<MP*> map_points_1, map_points_2;                      // map_points_1_ / _2_ [rows]
+  };
+  template <class KF, class MP>
+  static int LoopSim3Candidates(KF* current_keyframe, const std::vector<KF*>& candidates, std::vector<std::vector<MP*> >& matches_out, LoopSim3Data<MP>* data,
+                                float nnratio = 0.75f, bool check_orientation = true, int min_matches = 20) {
+    const int n_cand = (int)candidates.size();
+    matches_out.assign((size_t)n_cand, std::vector<MP*>());
+    *data = LoopSim3Data<MP>();
+    data->off.assign((size_t)n_cand + 1, 0);
+    if (n_cand == 0) return 0;
+    std::unordered_map<KF*, int> kf_at;
+    std::vector<KF*> kfs;
+    auto kf_index = [&](KF* kf) {
+      auto it = kf_at.find(kf);
+      if (it == kf_at.end()) { it = kf_at.emplace(kf, (int)kfs.size()).first; kfs.push_back(kf); }
+      return it->second;
+    };
+    const int32_t cur = kf_index(current_keyframe);
+    std::vector<int32_t> cand_kf((size_t)n_cand);
+    for (int c = 0; c < n_cand; c++) cand_kf[c] = kf_index(candidates[c]);
+    const int nkf = (int)kfs.size();
+    std::unordered_map<MP*, int> pt_at;
+    std::vector<MP*> pts;
+    std::vector<std::vector<MP*> > held((size_t)nkf);
+    std::vector<int32_t> slot_off(1, 0), slot_pt, slot_level, fv_off(1, 0), ent_off(1, 0), ent;
+    std::vector<uint32_t> node;
+    std::vector<float> angle, K4(4 * (size_t)nkf);
+    std::vector<uint8_t> desc, kf_bad((size_t)nkf), pt_bad;
+    std::vector<double> Tcw(12 * (size_t)nkf), X;
+    for (int k = 0; k < nkf; k++) {
+      KF* kf = kfs[k];
+      held[k] = kf->GetMapPointMatches();
+      const int n = (int)kf->undistort_keypoints_.size();
+      for (int i = 0; i < n; i++) {
+        MP* mp = i < (int)held[k].size() ? held[k][i] : nullptr;
+        int p = -1;
+        if (mp) {
+          auto it = pt_at.find(mp);
+          if (it == pt_at.end()) { it = pt_at.emplace(mp, (int)pts.size()).first; pts.push_back(mp); }
+          p = it->second;
+        }
+        slot_pt.push_back(p); slot_level.push_back(kf->undistort_keypoints_[i].octave); angle.push_back(kf->undistort_keypoints_[i].angle);
+        const uint8_t* d = kf->descriptors_.ptr(i);                   // (cv::Mat rows may be padded: copied row by row)
+        desc.insert(desc.end(), d, d + 32);
+      }
+      slot_off.push_back((int32_t)slot_pt.size());
+      for (auto it = kf->feature_vector_.begin(); it != kf->feature_vector_.end(); ++it) {
+        node.push_back((uint32_t)it->first);
+        for (auto v : it->second) ent.push_back((int32_t)v);
+        ent_off.push_back((int32_t)ent.size());
+      }
+      fv_off.push_back((int32_t)node.size());
+      kf_bad[k] = kf->isBad() ? 1 : 0;
+      const auto T = kf->GetPose();
+      for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) Tcw[12 * (size_t)k + 4 * r + c] = T(r, c);
+      K4[4 * (size_t)k] = kf->fx_; K4[4 * (size_t)k + 1] = kf->fy_; K4[4 * (size_t)k + 2] = kf->cx_; K4[4 * (size_t)k + 3] = kf->cy_;
+    }
+    const int npts = (int)pts.size();
+    std::vector<int32_t> obs_off(1, 0), obs_kf, obs_slot;
+    for (MP* mp : pts) {                                              // (only the observations GetIndexInKeyFrame can be asked about)
+      pt_bad.push_back(mp->isBad() ? 1 : 0);
+      const auto P = mp->GetWorldPos();
+      for (int k = 0; k < 3; k++) X.push_back(P[k]);
+      const auto observations = mp->GetObservations();
+      for (const auto& o : observations) {
+        auto it = kf_at.find(o.first);
+        if (it != kf_at.end()) { obs_kf.push_back(it->second); obs_slot.push_back((int32_t)o.second); }
+      }
+      obs_off.push_back((int32_t)obs_kf.size());
+    }
+    const std::vector<float> sigma2(current_keyframe->level_sigma2s_.begin(), current_keyframe->level_sigma2s_.end());
+    const int n1 = slot_off[cur + 1] - slot_off[cur];
+    const size_t cap_rows = (size_t)n_cand * (size_t)n1, nc = (size_t)n_cand;
+    std::vector<int32_t> m12(std::max<size_t>(cap_rows, 1), -1), nm(nc), status(nc), i1(std::max<size_t>(cap_rows, 1)), p1(i1.size()), p2(i1.size());
+    std::vector<double> X1(3 * i1.size()), X2(3 * i1.size());
+    std::vector<float> e1(i1.size()), e2(i1.size());
+    data->K1.assign(4 * nc, 0.f); data->K2.assign(4 * nc, 0.f);
+    int32_t counts[2] = {0, 0};
+    dropin::check(orbl_loop_sim3_candidates(cur, n_cand, cand_kf.data(), nkf, kf_bad.data(), Tcw.data(), K4.data(), slot_off.data(), slot_pt.data(), slot_level.data(),
+                                            angle.data(), desc.data(), fv_off.data(), node.data(), ent_off.data(), ent.data(), npts, pt_bad.data(), X.data(), obs_off.data(),
+                                            obs_kf.data(), obs_slot.data(), sigma2.data(), (int)sigma2.size(), nnratio, check_orientation ? 1 : 0, min_matches, n1,
+                                            (int)cap_rows, m12.data(), nm.data(), status.data(), data->K1.data(), data->K2.data(), data->off.data(), X1.data(), X2.data(),
+                                            e1.data(), e2.data(), i1.data(), p1.data(), p2.data(), counts),
+                  "orbl_loop_sim3_candidates");
+    const size_t rows = (size_t)counts[0];
+    data->discarded.resize(nc); data->nmatches.assign(nm.begin(), nm.end());
+    for (int c = 0; c < n_cand; c++) {
+      data->discarded[c] = status[c] != 0;
+      if (status[c] == 1) continue;                                   // (:257-260: SearchByBoW never ran, the vector stays empty)
+      const std::vector<MP*>& in2 = held[cand_kf[c]];
+      matches_out[c].assign((size_t)n1, static_cast<MP*>(nullptr));   // (:482-483)
+      for (int i = 0; i < n1; i++) { const int m = m12[(size_t)c * n1 + i]; if (m >= 0) matches_out[c][i] = in2[m]; }
+    }
+    data->matched_indices_1.assign(i1.begin(), i1.begin() + rows);
+    data->X1c.assign(X1.begin(), X1.begin() + 3 * rows); data->X2c.assign(X2.begin(), X2.begin() + 3 * rows);
+    data->max_err1.assign(e1.begin(), e1.begin() + rows); data->max_err2.assign(e2.begin(), e2.begin() + rows);
+    data->map_points_1.resize(rows); data->map_points_2.resize(rows);
+    for (size_t r = 0; r < rows; r++) { data->map_points_1[r] = pts[p1[r]]; data->map_points_2[r] = pts[p2[r]]; }
+    return counts[1];
+  }
+
   // LoopClosing::CorrectLoop, src/LoopClosing.cc:437-523, in ONE library call (orbl_correct_loop) followed by the UpdateConnections
   // drop-in: `FrameOpsHip::CorrectLoopPoses(current_keyframe_, current_connected_keyframes_, sophus_sim3_Scw_, sophus_corrected_sim3,
   // sophus_non_corrected_sim3);` under the mutex_map_update_ the caller holds, as the reference does.  Only the group's slots and the

@@ -406,3 +406,5 @@ int orbl_fuse_batch_sim3(const orbl_fuse_keyframe* kf, int n_kf, const float* q_
 #include "orb_essgraph.inc"
 // CeresOptimizer::BundleAdjustment's (GlobalBundleAdjustemnt) problem from the map tables and its write-back (orbl_global_ba_assemble*, orbl_global_ba_apply*)
 #include "orb_globalba.inc"
+// LoopClosing::ComputeSim3's front for every candidate: SearchByBoW, the gate, Sim3Solver's constructor data (orbl_loop_sim3_candidates*)
+#include "orb_loopsim3.inc"

@@ -580,3 +580,101 @@ def global_bundle_adjustment_on_tables(tab, ba_kf=None, ba_pt=None, n_iterations
     else:
         applied = global_ba_apply(asm["cam_kf"], asm["gpt_pt"], poses7, pts3, tab, stage=stage, normals=normals, out=out)
     return dict(assembled=asm, poses7=poses7, pts3=pts3, summary=summary, applied=applied)
+
+
+# ---- ComputeSim3's front: SearchByBoW, the gate and Sim3Solver's constructor data for every candidate ---------------------------------
+LS_OFFSETS, LS_KF, LS_PT, LS_LEVEL, LS_CAP, LS_SLOT = 1, 2, 4, 8, 16, 32        # *d_status bits of orbl_loop_sim3_candidates_device
+LS_KEPT, LS_BAD_KEYFRAME, LS_FEW_MATCHES = 0, 1, 2                              # cand_status
+# (key, dtype, width) of the tables, in the order the entry takes them
+_LS_KF = (("kf_bad", np.uint8, 1), ("kf_Tcw", np.float64, 12), ("kf_K4", np.float32, 4))
+_LS_SLOT = (("kf_slot_off", np.int32, 1), ("kf_slot_pt", np.int32, 1), ("kf_slot_level", np.int32, 1), ("kf_slot_angle", np.float32, 1), ("kf_slot_desc", np.uint8, 32))
+_LS_FV = (("kf_fv_off", np.int32, 1), ("fv_node", np.uint32, 1), ("fv_ent_off", np.int32, 1), ("fv_ent", np.int32, 1))
+_LS_PT = (("pt_bad", np.uint8, 1), ("X", np.float64, 3))
+_LS_OBS = (("obs_off", np.int32, 1), ("obs_kf", np.int32, 1), ("obs_slot", np.int32, 1))
+# (key, dtype, elements per candidate / per row, which of the two)
+_LS_OUT = (("match12", np.int32, None, "cand"), ("nmatches", np.int32, 1, "cand"), ("cand_status", np.int32, 1, "cand"), ("K1", np.float32, 4, "cand"),
+           ("K2", np.float32, 4, "cand"), ("off", np.int32, None, "off"), ("X1c", np.float64, 3, "row"), ("X2c", np.float64, 3, "row"), ("max_err1", np.float32, 1, "row"),
+           ("max_err2", np.float32, 1, "row"), ("row_i1", np.int32, 1, "row"), ("row_pt1", np.int32, 1, "row"), ("row_pt2", np.int32, 1, "row"), ("counts", np.int32, None, "two"))
+
+
+def _ls_out_size(kind, per, n_cand, cap1, cap_rows):
+    return {"cand": n_cand * (cap1 if per is None else per), "off": n_cand + 1, "row": cap_rows * (per or 1), "two": 2}[kind]
+
+
+def sim3_candidates(tab, cur_kf, cand_kf, nnratio=0.75, check_ori=True, min_matches=20, cap1=None, cap_rows=None, device=False, **kw):
+    """ComputeSim3's front for every candidate in one call (orbl_loop_sim3_candidates; include/orbslam_hip.h states the inputs and the
+    semantics): SearchByBoW(cur_kf, candidate), the min_matches gate and the rows Sim3Solver's constructor builds.  tab: the map tables
+    kf_bad (may be None), kf_Tcw [nkf, 12], kf_K4 [nkf, 4], kf_slot_off / kf_slot_pt / kf_slot_level / kf_slot_angle / kf_slot_desc
+    [nslots, 32], kf_fv_off / fv_node / fv_ent_off / fv_ent, pt_bad, X [npts, 3], obs_off / obs_kf / obs_slot, level_sigma2.  cap1
+    defaults to the current keyframe's slot count, cap_rows to n_cand times that.  Returns a dict: match12 [n_cand, cap1], nmatches,
+    cand_status, K1, K2 [n_cand, 4], off [n_cand + 1], counts = {rows, candidates kept} and, cut to counts[0] rows, X1c, X2c [rows, 3],
+    max_err1, max_err2, row_i1, row_pt1, row_pt2.  Raises OrbHipError (ORBHIP_ECAP) when a capacity is too small.
+    device=True: sim3_candidates_device on torch CUDA tensors."""
+    if device:
+        return sim3_candidates_device(tab, cur_kf, cand_kf, nnratio=nnratio, check_ori=check_ori, min_matches=min_matches, cap1=cap1, cap_rows=cap_rows, **kw)
+    L = _lib.load()
+    ck = _c(cand_kf, np.int32).reshape(-1)
+    t = {k: _flat(tab.get(k), dt) for k, dt, _ in _LS_KF + _LS_SLOT + _LS_FV + _LS_PT + _LS_OBS}
+    sig = _c(tab["level_sigma2"], np.float32).reshape(-1)
+    so = t["kf_slot_off"]
+    nkf, npts = len(so) - 1, len(t["pt_bad"])
+    assert len(t["kf_Tcw"]) == 12 * nkf and len(t["kf_K4"]) == 4 * nkf and len(t["kf_fv_off"]) == nkf + 1 and len(t["X"]) == 3 * npts and len(t["obs_off"]) == npts + 1
+    assert all(len(t[k]) == w * so[-1] for k, _, w in _LS_SLOT[1:]) and len(t["fv_ent_off"]) == len(t["fv_node"]) + 1
+    n1 = int(so[cur_kf + 1] - so[cur_kf]) if 0 <= cur_kf < nkf else 0
+    cap1 = n1 if cap1 is None else int(cap1)
+    cap_rows = len(ck) * n1 if cap_rows is None else int(cap_rows)
+    o = {k: np.zeros(_ls_out_size(kind, per, len(ck), cap1, cap_rows), dt) for k, dt, per, kind in _LS_OUT}
+    _lib.check(L.orbl_loop_sim3_candidates(int(cur_kf), len(ck), _p(ck), nkf, *[_p(t[k]) for k, _, _ in _LS_KF + _LS_SLOT + _LS_FV], npts,
+                                           *[_p(t[k]) for k, _, _ in _LS_PT + _LS_OBS], _p(sig), len(sig), float(nnratio), int(bool(check_ori)), int(min_matches),
+                                           cap1, cap_rows, *[_p(o[k]) for k, _, _, _ in _LS_OUT]), "orbl_loop_sim3_candidates")
+    rows = int(o["counts"][0])
+    for k, _, per, kind in _LS_OUT:
+        if kind == "row":
+            o[k] = o[k][:rows * per].reshape((rows, per) if per > 1 else (rows,))
+        elif kind == "cand" and per != 1:
+            o[k] = o[k].reshape(len(ck), -1)
+    return o
+
+
+def sim3_candidates_device(tab, cur_kf, cand_kf, nnratio=0.75, check_ori=True, min_matches=20, cap1=None, cap_rows=None, out=None, workspace=None):
+    """orbl_loop_sim3_candidates_device on torch CUDA tensors (the tables of sim3_candidates, flat or shaped, in its dtypes; cand_kf an
+    int32 tensor), enqueued on the current stream, nothing synchronised and nothing read back: cap1 and cap_rows are therefore the
+    caller's to give (cap1 at least the current keyframe's slot count).  out: optional dict of preset output tensors; workspace: an
+    optional uint8 tensor to reuse.  Returns a dict of device tensors: match12 [n_cand, cap1], nmatches, cand_status, K1, K2, off, X1c,
+    X2c [cap_rows, 3], max_err1, max_err2, row_i1, row_pt1, row_pt2 [cap_rows], counts [2], status (the LS_* bits) and the workspace
+    under "_workspace".  X1c, X2c, max_err1, max_err2, off, K1, K2 go to sim3solver.iterate_batch_device as they are."""
+    import torch
+    L = _lib.load()
+    assert cap1 is not None and cap_rows is not None, "the device form reads nothing back: give cap1 and cap_rows"
+    dev = tab["kf_Tcw"].device
+    n_cand = cand_kf.numel()
+    tt = {torch.uint8: np.uint8, torch.int32: np.int32, torch.float32: np.float32, torch.float64: np.float64}
+    for k, dt, _ in _LS_KF + _LS_SLOT + _LS_FV + _LS_PT + _LS_OBS + (("level_sigma2", np.float32, 1),):
+        v = tab.get(k)
+        assert v is None or (v.is_contiguous() and (tt.get(v.dtype) == dt or (dt == np.uint32 and v.dtype == torch.int32))), k
+    assert cand_kf.dtype == torch.int32 and cand_kf.is_contiguous()
+    nkf, nslots, nfv, nent = tab["kf_slot_off"].numel() - 1, tab["kf_slot_pt"].numel(), tab["fv_node"].numel(), tab["fv_ent"].numel()
+    npts, nobs = tab["pt_bad"].numel(), tab["obs_kf"].numel()
+    ws = _lib.workspace("orbl_loop_sim3_candidates_workspace", n_cand, int(cap1), device=dev, min_bytes=16, reuse=workspace)
+    to = {np.int32: torch.int32, np.float32: torch.float32, np.float64: torch.float64}
+    o = {} if out is None else dict(out)
+    sizes = [(k, to[dt], _ls_out_size(kind, per, n_cand, int(cap1), int(cap_rows))) for k, dt, per, kind in _LS_OUT] + [("status", torch.int32, 1)]
+    for k, dt, n in sizes:
+        if o.get(k) is None:
+            o[k] = torch.empty(max(n, 1), dtype=dt, device=dev)[:n]
+        assert o[k].dtype == dt and o[k].is_contiguous() and o[k].numel() == n, k
+    g = tab.get
+    _lib.check(L.orbl_loop_sim3_candidates_device(int(cur_kf), n_cand, _p(cand_kf), nkf, _p(g("kf_bad")), _p(g("kf_Tcw")), _p(g("kf_K4")), nslots, _p(g("kf_slot_off")),
+                                                  _pn(g("kf_slot_pt")), _pn(g("kf_slot_level")), _pn(g("kf_slot_angle")), _pn(g("kf_slot_desc")), nfv, _p(g("kf_fv_off")),
+                                                  _pn(g("fv_node")), nent, _p(g("fv_ent_off")), _pn(g("fv_ent")), npts, _pn(g("pt_bad")), _pn(g("X")), nobs,
+                                                  _p(g("obs_off")), _pn(g("obs_kf")), _pn(g("obs_slot")), _p(g("level_sigma2")), g("level_sigma2").numel(), float(nnratio),
+                                                  int(bool(check_ori)), int(min_matches), int(cap1), int(cap_rows), *[_pn(o[k]) for k, _, _, _ in _LS_OUT], _p(o["status"]),
+                                                  _p(ws), _lib.stream()), "orbl_loop_sim3_candidates_device")
+    r = dict(o)
+    r["match12"] = r["match12"].view(n_cand, -1) if cap1 else r["match12"]
+    for k in ("K1", "K2"):
+        r[k] = r[k].view(n_cand, 4)
+    for k in ("X1c", "X2c"):
+        r[k] = r[k].view(-1, 3)
+    r["_workspace"] = ws                                                                # (kept alive until the caller synchronises)
+    return r

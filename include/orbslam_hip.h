@@ -954,6 +954,77 @@ int orbl_update_map_points_on_tables_device(int what, const uint8_t* d_pt_mask, 
                                             uint8_t* d_nd_written, uint32_t* d_status, void* d_workspace, void* stream);
 int orbl_update_map_points_on_tables_workspace(int npts, int nobs, size_t* bytes);
 
+/* ---- LoopClosing::ComputeSim3, its front (src/LoopClosing.cc:250-277), on the resident tables for EVERY candidate in one call: per
+ * candidate ORBmatcher::SearchByBoW(current keyframe, candidate) (src/ORBmatcher.cc:470-580), the `nmatches < min_matches` gate (:265)
+ * and what Sim3Solver's constructor builds (src/Sim3Solver.cc:73-109).  The outputs are the d_X1c / d_X2c / d_max_err1 / d_max_err2 /
+ * d_off / d_K1 / d_K2 arguments of orbt_sim3_iterate_batch_device (n_total = cap_rows) and the P3D1c / P3D2c / offsets of
+ * ba_optimize_sim3_batch_device: a caller reads off[] alone (it needs every N to draw the sets) and goes on.  The three forms follow
+ * the conventions of the SearchInNeighbors entries above (host form / _device form with *d_status / _workspace form).
+ * Inputs, all read from the tables:
+ *   cur_kf; cand_kf[n_cand], n_cand in [1, 1024] - a candidate may be cur_kf or appear twice, every row is computed on its own;
+ *   kf_bad[nkf] (nullable = none), kf_Tcw[nkf][12], kf_K4[nkf][4] = (fx, fy, cx, cy);
+ *   kf_slot_off[nkf + 1] over kf_slot_pt[] (map_points_, -1 = none), kf_slot_level[] (undistort_keypoints_[i].octave),
+ *     kf_slot_angle[] (undistort_keypoints_[i].angle, float) and kf_slot_desc[][32].  A keyframe that takes part has at most 32768
+ *     slots (ORBT_SIM3_MAX_N);
+ *   every keyframe's feature_vector_ in orbv_transform's layout, concatenated: kf_fv_off[nkf + 1] over fv_node[] (ascending inside a
+ *     keyframe), fv_ent_off[nfv + 1] over fv_ent[] (the keypoint's index inside its keyframe, in list order).  A keyframe's feature
+ *     vector names a keypoint at most once, as DBoW2 builds it;
+ *   pt_bad[npts], pt_Xw[npts][3]; obs_off[npts + 1] over obs_kf[] / obs_slot[] (observations_);
+ *   level_sigma2[n_levels] (level_sigma2s_: one extractor, one table); nnratio (the reference: 0.75), check_ori (1), min_matches (20);
+ *   cap1: the row stride of match12, at least the current keyframe's slot count, at most 32768; cap_rows: the rows the packed outputs
+ *     hold, at most 32768 n_cand.
+ * Per candidate c, literally:
+ *   1. A candidate whose keyframe is bad is not searched (:257-260): cand_status 1.
+ *   2. SearchByBoW: the node merge of :498-560.  A feature of either side takes part when its slot holds a point that is not pt_bad.
+ *      Inside a node the current keyframe's entries, in list order, each take the closest entry of the candidate's list that no earlier
+ *      entry took (vbMatched2); of equal distances the first in list order (strict <); bestDist2 is the second smallest, an equal
+ *      distance counted, both from 256.  Accepted iff bestDist1 < 50 and (float)bestDist1 < nnratio * (float)bestDist2.  With check_ori
+ *      the bin of rot = angle1 - angle2 (+ 360 when negative), round(rot * (1.0f / 30)), 30 -> 0, and after ComputeThreeMaxima the
+ *      matches of the other bins are cleared - their vbMatched2 stayed set during the search, as in the reference.
+ *   3. nmatches < min_matches discards the candidate: cand_status 2.
+ *   4. Otherwise (cand_status 0) the constructor's loop, i1 ascending.  Row i1 is skipped when match12[i1] < 0, when slot i1 of the
+ *      current keyframe holds no point, when either point is bad, or when GetIndexInKeyFrame is negative on either side.
+ *      GetIndexInKeyFrame(point, keyframe) is obs_slot of the FIRST entry of the point's observation list that names the keyframe, -1
+ *      when none does - not the slot the point was found in.  The octave is kf_slot_level at THAT index, max_err = (float)(size_t)
+ *      (9.210 * (double)level_sigma2[octave]), and X = ((R(i,0) x + R(i,1) y) + R(i,2) z) + t(i) in double without fused multiply-add.
+ *      A kept candidate may end with fewer than min_matches rows: the reference builds its solver and iterate answers TOO_FEW.
+ * Outputs, every element written on every call:
+ *   match12[n_cand][cap1]: the candidate keyframe's slot or -1, after the rotation check (map_point_matches_vector[i], as slots);
+ *   nmatches[n_cand] (0 for cand_status 1); cand_status[n_cand]; K1[n_cand][4], K2[n_cand][4] = kf_K4 of the current keyframe and of the
+ *     candidate (K2: zeros for cand_status 1; K1: zeros in the device form when the current keyframe is not usable);
+ *   off[n_cand + 1]: the rows of candidate c are [off[c], off[c + 1]), empty for a discarded one;
+ *   X1c, X2c[cap_rows][3]; max_err1, max_err2[cap_rows]; row_i1 (matched_indices_1_), row_pt1, row_pt2[cap_rows] (the points); rows
+ *     behind the last one are zeros and -1;
+ *   counts[2] = {rows wanted, candidates kept}.
+ * No atomic decides a position: the same bytes on every run.
+ * Host form: ORBHIP_EINVAL for anything the tables must not hold (an index out of range, offsets that decrease, fv_node not ascending, a
+ * keypoint named twice, more than 32768 slots in a keyframe that takes part); ORBHIP_ECAP with only counts[] written when cap_rows is
+ * too small (counts[0] = the rows wanted) or cap1 is below the current keyframe's slot count (counts = {0, 0}, the message names it).
+ * Device form: an entry out of range counts as absent - a candidate that is no keyframe as a bad one (bit 2), a slot point that is no
+ * point as none (bit 4), an fv_ent or obs_slot its keyframe does not have as missing (bit 32), a level out of range as no row (bit 8),
+ * unusable offsets as an empty list (bit 1).  Bit 16: a keyframe that takes part has more than 32768 slots (it counts as bad), the
+ * current keyframe has more than cap1 (nothing is searched), or more than cap_rows rows were wanted - off[] and counts[] then state
+ * what was wanted and nothing is written beyond cap_rows.
+ * Workspace, with R(x) = x rounded up to a multiple of 256: R(128 n_cand) (the rotation histograms, cleared by every call)
+ * + R(n_cand cap1) (the bins) + 2 R(4 n_cand cap1) (the rows' keypoint indices) + R(4 (n_cand + 1)) (the row counts and their scan).   */
+int orbl_loop_sim3_candidates(int cur_kf, int n_cand, const int32_t* cand_kf, int nkf, const uint8_t* kf_bad, const double* kf_Tcw, const float* kf_K4,
+                              const int32_t* kf_slot_off, const int32_t* kf_slot_pt, const int32_t* kf_slot_level, const float* kf_slot_angle,
+                              const uint8_t* kf_slot_desc, const int32_t* kf_fv_off, const uint32_t* fv_node, const int32_t* fv_ent_off, const int32_t* fv_ent, int npts,
+                              const uint8_t* pt_bad, const double* pt_Xw, const int32_t* obs_off, const int32_t* obs_kf, const int32_t* obs_slot,
+                              const float* level_sigma2, int n_levels, float nnratio, int check_ori, int min_matches, int cap1, int cap_rows, int32_t* match12,
+                              int32_t* nmatches, int32_t* cand_status, float* K1, float* K2, int32_t* off, double* X1c, double* X2c, float* max_err1, float* max_err2,
+                              int32_t* row_i1, int32_t* row_pt1, int32_t* row_pt2, int32_t* counts);
+int orbl_loop_sim3_candidates_device(int cur_kf, int n_cand, const int32_t* d_cand_kf, int nkf, const uint8_t* d_kf_bad, const double* d_kf_Tcw, const float* d_kf_K4,
+                                     int nslots, const int32_t* d_kf_slot_off, const int32_t* d_kf_slot_pt, const int32_t* d_kf_slot_level,
+                                     const float* d_kf_slot_angle, const uint8_t* d_kf_slot_desc, int nfv, const int32_t* d_kf_fv_off, const uint32_t* d_fv_node,
+                                     int nent, const int32_t* d_fv_ent_off, const int32_t* d_fv_ent, int npts, const uint8_t* d_pt_bad, const double* d_pt_Xw,
+                                     int nobs, const int32_t* d_obs_off, const int32_t* d_obs_kf, const int32_t* d_obs_slot, const float* d_level_sigma2,
+                                     int n_levels, float nnratio, int check_ori, int min_matches, int cap1, int cap_rows, int32_t* d_match12, int32_t* d_nmatches,
+                                     int32_t* d_cand_status, float* d_K1, float* d_K2, int32_t* d_off, double* d_X1c, double* d_X2c, float* d_max_err1,
+                                     float* d_max_err2, int32_t* d_row_i1, int32_t* d_row_pt1, int32_t* d_row_pt2, int32_t* d_counts, uint32_t* d_status,
+                                     void* d_workspace, void* stream);
+int orbl_loop_sim3_candidates_workspace(int n_cand, int cap1, size_t* bytes);
+
 /* ---- LoopClosing::CorrectLoop, the part that moves the map (src/LoopClosing.cc:437-523): the corrected and non-corrected Sim3 of the
  * current keyframe's covisibility group, the correction of every map point those keyframes hold, UpdateNormalAndDepth of each moved
  * point, SetPose([R | t/s]) of each keyframe - with the exact semantics of the sequential loop.  Keyframes are 0..nkf-1, points 0..npts-1.
